@@ -17,7 +17,10 @@ GPU before the timed region). Prints ONE JSON line (see DESIGN.md "Measurement")
 --gpus N with N > 1 and no torch.distributed environment re-launches itself under torch.distributed.run (one rank per GPU, RCCL).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload reblur_ds|reblur_diffuse|relax_ds_sh|relax_ds|sigma_shadow] [--width 2560 --height 1440]
-                  [--graph] [--no-sky] [--no-cpu-baseline] [--no-parity]
+                  [--graph] [--no-sky] [--no-cpu-baseline] [--no-parity] [--dump-outputs DIR]
+
+--dump-outputs DIR writes the OUT_* planes the last timed step produced as DIR/<name>.npy (float32, a fixed seeded pixel sample when they exceed 64 MB), so that two
+builds can be compared output for output: the inputs depend on the arguments alone.
 """
 import argparse
 import json
@@ -118,6 +121,10 @@ WORKLOADS = {
     "relax_ds": ("RELAX_DIFFUSE_SPECULAR", (3840, 2160), RELAX_DS_BYTES_PER_PIXEL, None),
 }
 
+# --dump-outputs: the whole dump (every .npy file, headers included) stays below this
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 0
+
 
 def parse_args():
     ap = argparse.ArgumentParser()
@@ -143,7 +150,12 @@ def parse_args():
                     "(NRD_EXPERIMENT_L1_RESIDENT, csrc/hip/planes.h) computes the same values as the product and so measures each kernel's issue floor")
     ap.add_argument("--dry-plan", action="store_true", help="no GPU: print the multi-GPU plan of --gpus N ranks for this workload (strips, halo bands, bytes, RCCL operations) and exit")
     ap.add_argument("--no-parity", action="store_true", help="skip the GPU-vs-oracle comparison of the cpu_baseline frames")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the OUT_* planes of the last timed frame as DIR/<OUT_name>.npy (float32; "
+                    "at most %d MB in all: larger outputs are cut to the same fixed, seeded sample of pixels in every plane, shape [pixels, channels])" % (DUMP_LIMIT_BYTES // 10**6))
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def measure_copy_bandwidth(lib, nbytes=1 << 30, reps=10):
@@ -155,6 +167,32 @@ def measure_copy_bandwidth(lib, nbytes=1 << 30, reps=10):
     r = lib.nrdHipMeasureCopyBandwidth(nbytes, reps, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(out))
     assert r == 0, "nrdHipMeasureCopyBandwidth failed"
     return out.value
+
+
+def library_is_current():
+    """lib/libNRD_hip.so exists and was built from the present sources (the digest build.py records next to it). Only reads: a built tree is benchmarked as it is,
+    also by a user who may not write to it -- build_product() takes a lock file in lib/ even when there is nothing to build."""
+    out = native_build.product_path()
+    host, hip = native_build._sources()
+    digest = native_build._global_digest(host + hip, native_build._headers_digest())
+    if not (os.path.exists(out) and os.path.exists(out + ".digest")):
+        return False
+    with open(out + ".digest") as fp:
+        return fp.read() == digest
+
+
+def snapshot_outputs(planes, width, height):
+    """[(name, [H, W, C] device tensor)] -> {name: float32 array} for --dump-outputs. The whole planes when they fit DUMP_LIMIT_BYTES; otherwise every plane is cut to the
+    same pixels -- n row-major pixel indices drawn without replacement by numpy's PCG64 seeded with DUMP_SAMPLE_SEED, in ascending order -- as a [n, C] array."""
+    import numpy as np
+
+    pixels, channels = width * height, sum(t.shape[2] for _, t in planes)
+    budget = DUMP_LIMIT_BYTES - 256 * len(planes)  # (256 B per .npy header)
+    if pixels * channels * 4 <= budget:
+        return {name: t.float().cpu().numpy() for name, t in planes}
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(pixels, budget // (channels * 4), replace=False))
+    idx = torch.from_numpy(idx).to(planes[0][1].device)
+    return {name: t.reshape(pixels, -1).index_select(0, idx).float().cpu().numpy() for name, t in planes}
 
 
 def _usable_cores():
@@ -298,7 +336,7 @@ def main():
         dist.init_process_group(backend, timeout=datetime.timedelta(seconds=int(os.environ.get("NRD_DIST_TIMEOUT_S", "300"))))
         assert dist.get_world_size() == args.gpus
 
-    if rank == 0:
+    if rank == 0 and not library_is_current():
         native_build.build_product()
     if distributed:
         dist.barrier()
@@ -387,6 +425,11 @@ def main():
         step(f)
     fence()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the caller holds after the last timed frame, taken before the replays below overwrite it (halo sharding: the reassembled planes, complete after fence())
+        planes = [(rt.name, shard.complete_output(rt) if hasattr(shard, "complete_output") else t) for (rt, _, _, _), t in zip(scene.output_planes(name, W, H), outputs)]
+        dumped = snapshot_outputs(planes, W, H)
     graph_stats = ex.graph_stats()
     tile_fallback = ex.tile_fallback_stats()  # REBLUR TemporalAccumulation: tiles of the last frame whose surface-motion window did not fit the LDS window
 
@@ -577,6 +620,14 @@ def main():
         result["cpu_baseline"], result["parity"] = cpu_baseline(name, W, H, min(args.cpu_frames, distinct), seq, overrides, check_parity=not args.no_parity)
     else:
         result["cpu_baseline"], result["parity"] = None, None
+    if dumped is not None:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for key, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, key + ".npy"), arr)
+        result["dump_outputs"] = {"dir": args.dump_outputs, "frame": total - 1, "shapes": {key: list(arr.shape) for key, arr in dumped.items()},
+                                  "sampled": any(arr.ndim == 2 for arr in dumped.values())}
     print(json.dumps(result))
     if distributed:
         dist.barrier()
