@@ -7,17 +7,22 @@ PostBlur, TemporalStabilization) over one synthetic frame whose inputs are ALREA
 GPU before the timed region). Prints ONE JSON line (see DESIGN.md "Measurement"):
 
   value         Mpixels/s of the whole job = steps * 2560 * 1440 / wall time of the timed region (max over ranks)
+
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line. --full adds everything else
+(measured outside the timed region, which is the same in both):
+
   roofline      for the dominant kernel: algorithmic bytes per launch / its mean duration,
                 measured live with HIP events recorded on the executor's stream around every dispatch
   cpu_baseline  the CPU oracle (oracle/, kind "port": the reference has no CPU implementation) on the host cores,
                 on a bounded sample of the same workload (N = 1, rank 0 only)
   parity        the planes the cpu_baseline leg computes anyway (first frames of the same sequence, full size) compared with the GPU's: the library that is
                 timed is the library that is checked, and the expected maximum relative error is 0 (bit-identical user outputs)
+  passes, whole_chain, frame_ms, tile_fallback   per-pass durations, per-frame GPU times incl. a camera cut, TemporalAccumulation tiles left to the fallback kernel
 
 --gpus N with N > 1 and no torch.distributed environment re-launches itself under torch.distributed.run (one rank per GPU, RCCL).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload reblur_ds|reblur_diffuse|relax_ds_sh|relax_ds|sigma_shadow] [--width 2560 --height 1440]
-                  [--graph] [--no-sky] [--no-cpu-baseline] [--no-parity] [--dump-outputs DIR]
+                  [--graph] [--no-sky] [--full [--no-cpu-baseline] [--no-parity]] [--dump-outputs DIR]
 
 --dump-outputs DIR writes the OUT_* planes the last timed step produced as DIR/<name>.npy (float32, a fixed seeded pixel sample when they exceed 64 MB), so that two
 builds can be compared output for output: the inputs depend on the arguments alone.
@@ -134,7 +139,6 @@ def parse_args():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="reblur_ds", help="reblur_ds = the BASELINE.json metric (default); reblur_ds_perf = same in NRD's performance mode; relax_ds_sh = config 5 (4K)")
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sharding", choices=["halo", "allgather"], default=os.environ.get("NRD_SHARDING", "halo"),
                     help="multi-GPU scheme: halo = halo exchange between pass segments (point-to-point to the two neighbouring ranks), allgather = redundant halo compute + one all-gather per frame")
     ap.add_argument("--motion-bound", choices=("measure", "estimate"), default="measure", help="halo scheme: where the per-frame motion bound comes from -- measure: a device reduction over "
@@ -149,6 +153,9 @@ def parse_args():
     ap.add_argument("--uniform", action="store_true", help="tuning runs: every input plane constant (the value of one ground pixel), static camera -- the scene on which an L1-resident A/B build "
                     "(NRD_EXPERIMENT_L1_RESIDENT, csrc/hip/planes.h) computes the same values as the product and so measures each kernel's issue floor")
     ap.add_argument("--dry-plan", action="store_true", help="no GPU: print the multi-GPU plan of --gpus N ranks for this workload (strips, halo bands, bytes, RCCL operations) and exit")
+    ap.add_argument("--full", action="store_true", help="besides the headline value: the copy-bandwidth probe, the per-pass and per-frame replays (roofline, passes, whole_chain, "
+                    "frame_ms with the camera cut), tile_fallback, and the CPU baseline with its parity check; a plain run only sets up, warms up, times the steps and dumps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (and so without parity)")
     ap.add_argument("--no-parity", action="store_true", help="skip the GPU-vs-oracle comparison of the cpu_baseline frames")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the OUT_* planes of the last timed frame as DIR/<OUT_name>.npy (float32; "
                     "at most %d MB in all: larger outputs are cut to the same fixed, seeded sample of pixels in every plane, shape [pixels, channels])" % (DUMP_LIMIT_BYTES // 10**6))
@@ -340,7 +347,7 @@ def main():
         native_build.build_product()
     if distributed:
         dist.barrier()
-    copy_gbs = measure_copy_bandwidth(api.load_library())
+    copy_gbs = measure_copy_bandwidth(api.load_library()) if args.full else None
 
     name, default_size, bytes_per_pixel, overrides = WORKLOADS[args.workload]
     W, H = args.width or default_size[0], args.height or default_size[1]
@@ -359,7 +366,8 @@ def main():
             if torch.is_tensor(v) and v.dim() >= 2 and v.shape[0] == H and v.shape[1] == W:
                 seq[0][k] = v[py:py + 1, px:px + 1].expand_as(v).contiguous()
     torch.cuda.synchronize()
-    denoised_fraction = 1.0 - float(torch.stack([fr["is_sky"].float().mean() for fr in seq[:: max(1, len(seq) // 8)]]).mean())  # sky pixels leave at the tile test
+    if args.full:
+        denoised_fraction = 1.0 - float(torch.stack([fr["is_sky"].float().mean() for fr in seq[:: max(1, len(seq) // 8)]]).mean())  # sky pixels leave at the tile test
 
     inst = api.Instance([(0, scene.DENOISERS[name][0])])
     ex = HipExecutor(inst, W, H)
@@ -431,48 +439,49 @@ def main():
         planes = [(rt.name, shard.complete_output(rt) if hasattr(shard, "complete_output") else t) for (rt, _, _, _), t in zip(scene.output_planes(name, W, H), outputs)]
         dumped = snapshot_outputs(planes, W, H)
     graph_stats = ex.graph_stats()
-    tile_fallback = ex.tile_fallback_stats()  # REBLUR TemporalAccumulation: tiles of the last frame whose surface-motion window did not fit the LDS window
+    if args.full:
+        tile_fallback = ex.tile_fallback_stats()  # REBLUR TemporalAccumulation: tiles of the last frame whose surface-motion window did not fit the LDS window
 
-    # ---- per-pass durations for the roofline: the SAME frames once more with HIP events around every dispatch on the executor's stream (eager launches:
-    # events cannot bracket the nodes of a graph). Outside the timed region; the history carried over differs, the work per pass does not.
-    ex.set_profiling(True)
-    for f in range(args.warmup, total):
-        step(f)
-    fence()
-    timings = ex.collect_pass_timings()
-    ex.set_profiling(False)
-
-    # ---- per-frame GPU time (a real-time denoiser is judged on its worst frame): the timed frames once more with an event between consecutive
-    # frames (torch events on the executor's stream = torch's current stream), then a CAMERA CUT -- one CLEAR_AND_RESTART frame in mid-sequence (the clears + a frame whose
-    # every pixel is reconstructed by HistoryFix) -- and the frames that follow it while the history regrows
-    def timed_frames(frames):
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(frames) + 1)]
-        evs[0].record()
-        for i, run in enumerate(frames):
-            run()
-            evs[i + 1].record()
+        # ---- per-pass durations for the roofline: the SAME frames once more with HIP events around every dispatch on the executor's stream (eager launches:
+        # events cannot bracket the nodes of a graph). Outside the timed region; the history carried over differs, the work per pass does not.
+        ex.set_profiling(True)
+        for f in range(args.warmup, total):
+            step(f)
         fence()
-        return [evs[i].elapsed_time(evs[i + 1]) for i in range(len(frames))]
+        timings = ex.collect_pass_timings()
+        ex.set_profiling(False)
 
-    per_frame_ms = timed_frames([(lambda f=f: step(f)) for f in range(args.warmup, total)])
-    last = total - 1
+        # ---- per-frame GPU time (a real-time denoiser is judged on its worst frame): the timed frames once more with an event between consecutive
+        # frames (torch events on the executor's stream = torch's current stream), then a CAMERA CUT -- one CLEAR_AND_RESTART frame in mid-sequence (the clears + a frame whose
+        # every pixel is reconstructed by HistoryFix) -- and the frames that follow it while the history regrows
+        def timed_frames(frames):
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(frames) + 1)]
+            evs[0].record()
+            for i, run in enumerate(frames):
+                run()
+                evs[i + 1].record()
+            fence()
+            return [evs[i].elapsed_time(evs[i + 1]) for i in range(len(frames))]
 
-    def cut_frame(k):
-        def run():
-            frame = frame_of(last)
-            for rt, t, fmt in scene.user_planes(name, frame):
-                ex.bind(rt, t, fmt)
-            cs = scene.common_settings(frame["camera"], frame["camera"], W, H, last + 1 + k, **({"accumulationMode": int(api.AccumulationMode.CLEAR_AND_RESTART)} if k == 0 else {}))
-            assert inst.set_common_settings(cs) == api.Result.SUCCESS
-            shard.denoise() if shard is not None else ex.denoise()
-        return run
+        per_frame_ms = timed_frames([(lambda f=f: step(f)) for f in range(args.warmup, total)])
+        last = total - 1
 
-    cut_ms = timed_frames([cut_frame(k) for k in range(5)])
-    srt = sorted(per_frame_ms)
-    frame_ms = {"mean": round(sum(srt) / len(srt), 4), "p50": round(srt[len(srt) // 2], 4), "p99": round(srt[min(len(srt) - 1, int(0.99 * len(srt)))], 4), "max": round(srt[-1], 4), "min": round(srt[0], 4),
-                "frames": len(srt), "camera_cut": {"restart_frame_ms": round(cut_ms[0], 4), "following_frames_ms": [round(v, 4) for v in cut_ms[1:]],
-                                                  "what": "one CLEAR_AND_RESTART frame after the timed sequence (pool clears + every pixel through the history-fix reconstruction), then 4 frames of regrowing history"},
-                "note": "GPU time between consecutive frame boundaries (events on the executor's stream) of a replay of the timed frames, rank 0"}
+        def cut_frame(k):
+            def run():
+                frame = frame_of(last)
+                for rt, t, fmt in scene.user_planes(name, frame):
+                    ex.bind(rt, t, fmt)
+                cs = scene.common_settings(frame["camera"], frame["camera"], W, H, last + 1 + k, **({"accumulationMode": int(api.AccumulationMode.CLEAR_AND_RESTART)} if k == 0 else {}))
+                assert inst.set_common_settings(cs) == api.Result.SUCCESS
+                shard.denoise() if shard is not None else ex.denoise()
+            return run
+
+        cut_ms = timed_frames([cut_frame(k) for k in range(5)])
+        srt = sorted(per_frame_ms)
+        frame_ms = {"mean": round(sum(srt) / len(srt), 4), "p50": round(srt[len(srt) // 2], 4), "p99": round(srt[min(len(srt) - 1, int(0.99 * len(srt)))], 4), "max": round(srt[-1], 4), "min": round(srt[0], 4),
+                    "frames": len(srt), "camera_cut": {"restart_frame_ms": round(cut_ms[0], 4), "following_frames_ms": [round(v, 4) for v in cut_ms[1:]],
+                                                      "what": "one CLEAR_AND_RESTART frame after the timed sequence (pool clears + every pixel through the history-fix reconstruction), then 4 frames of regrowing history"},
+                    "note": "GPU time between consecutive frame boundaries (events on the executor's stream) of a replay of the timed frames, rank 0"}
     gc.enable()  # (the measured loops are over)
     gc.unfreeze()
 
@@ -490,85 +499,86 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     mpix_s = args.steps * W * H / elapsed / 1e6
 
-    # ---- roofline of the dominant kernel (live HIP-event timings of this very run)
-    rows = W * H if shard is None else shard.pixels_per_rank()
-    passes = {}
-    # one GPU: the tile-classification kernel writes the guide planes too (kernels_common.hip DecodeGuidesClassifyKernel) and there is no separate guide row
-    guides_in_classify = timings.get(HipExecutor.GUIDE_PREPARATION, (0.0, 0))[1] == 0
-    for shader, (ms, n) in timings.items():
-        bpp = bytes_per_pixel.get(shader)
-        if shader == HipExecutor.GUIDE_PREPARATION or (guides_in_classify and shader in ("REBLUR_ClassifyTiles.cs", "RELAX_ClassifyTiles.cs")):
-            bpp = GUIDE_BYTES_PER_PIXEL.get(name.split("_")[0])  # not part of the reference's compulsory traffic: a cost of this design (None: SIGMA / REFERENCE decode nothing)
-        if bpp is None or n == 0:
-            continue
-        avg_ms = ms / n
-        gbps = bpp * rows / (avg_ms * 1e-3) / 1e9
-        # (several launches of one shader -- the a-trous iterations -- are averaged; frac_* = this pass's algorithmic bytes against the 8 TB/s peak and against the copy rate measured above)
-        passes[shader] = {"avg_ms": round(avg_ms, 4), "launches": n, "bytes_per_launch": bpp * rows, "GBps": round(gbps, 1), "frac_of_peak": round(gbps / HBM_PEAK_GBS, 4),
-                          "frac_of_measured_copy": round(gbps / copy_gbs, 4)}
-    dominant = max(passes, key=lambda k: passes[k]["avg_ms"]) if passes else None
-    roofline = None
-    if dominant:
-        achieved = passes[dominant]["GBps"]
-        traffic, traffic_source, valu = None, None, None
-        # the recorded evidence (hardware counters, issue floors) carries the digest of the library it was taken from; `stale` = the library timed here is another one
-        digest_file = os.path.join(native_build.LIB_DIR, native_build.LIB_NAME + ".digest")
-        lib_digest = open(digest_file).read().strip() if os.path.exists(digest_file) and not os.environ.get("NRD_HIP_LIBRARY") else None
-        stale = {}
-        if world == 1 and os.path.exists(PMC_TRAFFIC_FILE):
-            entry = json.load(open(PMC_TRAFFIC_FILE)).get("%s_%dx%d%s" % (name, W, H, "_nosky" if args.no_sky else ""), {})
-            k = entry.get("kernels", {}).get(dominant)
-            if k:
-                stale["counters"] = entry.get("library_digest") is None or entry.get("library_digest") != lib_digest
-                traffic = int((2.0 * k["FETCH_SIZE_KiB"] + k["WRITE_SIZE_KiB"]) * 1024)
-                traffic_source = entry.get("source")
-                if k.get("SQ_INSTS_VALU"):
-                    # the OTHER roofline of a kernel that computes: executed VALU instructions against the issue rate of the chip -- a wave64 VALU instruction occupies its
-                    # SIMD-32 for 2 cycles (MI355X_MICROARCH.md "Per-instruction cycle constants": v_fma_f32), 256 CUs x 4 SIMDs, 2.4 GHz. The instruction count is the recorded
-                    # counter (SQ_INSTS_VALU / launch), the time is this run's: frac = the share of the kernel's time the VALU pipes would need if every instruction were an fma.
-                    issue_ms = k["SQ_INSTS_VALU"] * 2.0 / (VALU_SIMDS * VALU_CLOCK_GHZ * 1e9) * 1e3
-                    valu = {"executed_valu_per_wave": k["valu_per_wave"], "waves_per_launch": int(k["SQ_WAVES"]), "source": entry.get("source"),
-                            "fma_issue_bound_ms": round(issue_ms, 4), "frac": round(issue_ms / passes[dominant]["avg_ms"], 4),
-                            "what": "SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz) against this run's kernel time: the pure-FMA issue bound (selects, conversions, integer "
-                                    "instructions issue at 4, transcendentals at 8 cycles: the measured issue floor below is the tight bound)"}
-        # What the dominant kernel is bound by, measured directly (round 4; the counter-derived "VALU busy" of round 3 read up to 109 % and is gone): its time in
-        # a build whose loads all hit the L1, on a scene where that build computes the same values (bench.py --uniform, csrc/hip/planes.h NRD_EXPERIMENT_L1_RESIDENT).
-        issue_floor = None
-        if world == 1 and os.path.exists(ISSUE_FLOOR_FILE):
-            fl = json.load(open(ISSUE_FLOOR_FILE))
-            frag = {"TemporalAccumulation": "TemporalAccumulationKernel", "TemporalStabilization": "TemporalStabilizationKernel", "HistoryFix": "HistoryFixKernel", "HistoryClamping": "HistoryClampingKernel",
-                    "AtrousSmem": "AtrousSmemKernel", "PrePass": "PrePassKernel" if name.startswith("RELAX") else "ReblurSpatialKernel", "Blur": "ReblurSpatialKernel", "PostBlur": "ReblurSpatialKernel",
-                    "Atrous": "RelaxAtrousKernel"}.get(dominant.rsplit("_", 1)[-1].replace(".cs", ""))
-            rows_fl = next((v for k2, v in fl.get("workloads", {}).items() if k2.startswith(name + " ")), {})
-            hit = next((v for k2, v in rows_fl.items() if frag and frag in k2), None)  # (the first match: the window kernel precedes its fallback)
-            if hit:
-                issue_floor = dict(hit, source=fl.get("source"), what="uniform scene, every pixel denoised: this kernel's time / its time with every load an L1 hit (not measured in this run)")
-                stale["issue_floor"] = fl.get("library_digest") is None or fl.get("library_digest") != lib_digest
-        # what the evidence says bounds the kernel: at most 25 % above its L1-resident time -> instruction issue; beyond that the memory system behind the L1 (the request path of
-        # scattered taps / dependent round trips); HBM itself is a quarter busy (frac). `bound` names that; achieved / peak / frac stay the HBM roofline BASELINE.json asks for.
-        bound = "hbm"
-        if issue_floor and issue_floor.get("measured_over_floor"):
-            bound = "valu-issue" if issue_floor["measured_over_floor"] <= 1.25 else "l1-request"
-        roofline = {"bound": bound, "roofline_class": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                    "measured_copy_GBps": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved / copy_gbs, 4),
-                    "denoised_pixel_fraction": round(denoised_fraction, 4), "frac_denoised_pixels": round(achieved / HBM_PEAK_GBS * denoised_fraction, 4),
-                    "traffic": traffic, "traffic_source": traffic_source, "valu": valu, "issue_floor": issue_floor, "avg_kernel_ms": passes[dominant]["avg_ms"],
-                    "library_digest": lib_digest, "stale": (any(stale.values()) if stale else None), "stale_fields": sorted(k2 for k2, v in stale.items() if v),
-                    "algorithmic_bytes_per_launch": passes[dominant]["bytes_per_launch"],
-                    "note": "bound = what the recorded issue-floor evidence says limits the kernel (valu-issue: within 25 % of its L1-resident time; l1-request: the memory system behind the L1); "
-                            "achieved / peak / frac = its algorithmic bytes against the HBM peak (roofline_class), valu.frac = its executed VALU instructions against the chip's fma issue rate; "
-                            "traffic / valu / issue_floor are recorded measurements (profiles/), stamped with the digest of the library they were taken from: stale = not the library timed here; "
-                            "dominant = the pass with the longest average launch; per-pass durations from HIP events on the executor's stream (eager replay of the timed frames); "
-                            "frac counts the algorithmic bytes of EVERY pixel of the frame as the metric does, frac_denoised_pixels only those of the pixels that are not sky; "
-                            "measured_copy_GBps = the library's own 16-B/lane copy kernel on this GPU"}
-    # per frame: every pass once, except the dilated a-trous pass which runs (launches / steps) times
-    per_frame = {k: p["launches"] / args.steps for k, p in passes.items()}
-    gpu_ms = sum(p["avg_ms"] * per_frame[k] for k, p in passes.items())  # (includes the guide-decode kernel; the TemporalAccumulation row includes its fallback launch)
-    total_bpp = sum(bytes_per_pixel[k] * per_frame[k] for k in passes if k in bytes_per_pixel)
-    whole_chain = {"algorithmic_bytes_per_pixel": round(total_bpp, 1), "algorithmic_bytes_per_frame": int(total_bpp * W * H), "sum_kernel_ms": round(gpu_ms, 4),
-                   "GBps": round(total_bpp * rows / (gpu_ms * 1e-3) / 1e9, 1) if gpu_ms else None,
-                   "frac_of_peak": round(total_bpp * rows / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if gpu_ms else None,
-                   "frac_of_measured_copy": round(total_bpp * rows / (gpu_ms * 1e-3) / 1e9 / copy_gbs, 4) if gpu_ms else None}
+    if args.full:
+        # ---- roofline of the dominant kernel (live HIP-event timings of this very run)
+        rows = W * H if shard is None else shard.pixels_per_rank()
+        passes = {}
+        # one GPU: the tile-classification kernel writes the guide planes too (kernels_common.hip DecodeGuidesClassifyKernel) and there is no separate guide row
+        guides_in_classify = timings.get(HipExecutor.GUIDE_PREPARATION, (0.0, 0))[1] == 0
+        for shader, (ms, n) in timings.items():
+            bpp = bytes_per_pixel.get(shader)
+            if shader == HipExecutor.GUIDE_PREPARATION or (guides_in_classify and shader in ("REBLUR_ClassifyTiles.cs", "RELAX_ClassifyTiles.cs")):
+                bpp = GUIDE_BYTES_PER_PIXEL.get(name.split("_")[0])  # not part of the reference's compulsory traffic: a cost of this design (None: SIGMA / REFERENCE decode nothing)
+            if bpp is None or n == 0:
+                continue
+            avg_ms = ms / n
+            gbps = bpp * rows / (avg_ms * 1e-3) / 1e9
+            # (several launches of one shader -- the a-trous iterations -- are averaged; frac_* = this pass's algorithmic bytes against the 8 TB/s peak and against the copy rate measured above)
+            passes[shader] = {"avg_ms": round(avg_ms, 4), "launches": n, "bytes_per_launch": bpp * rows, "GBps": round(gbps, 1), "frac_of_peak": round(gbps / HBM_PEAK_GBS, 4),
+                              "frac_of_measured_copy": round(gbps / copy_gbs, 4)}
+        dominant = max(passes, key=lambda k: passes[k]["avg_ms"]) if passes else None
+        roofline = None
+        if dominant:
+            achieved = passes[dominant]["GBps"]
+            traffic, traffic_source, valu = None, None, None
+            # the recorded evidence (hardware counters, issue floors) carries the digest of the library it was taken from; `stale` = the library timed here is another one
+            digest_file = os.path.join(native_build.LIB_DIR, native_build.LIB_NAME + ".digest")
+            lib_digest = open(digest_file).read().strip() if os.path.exists(digest_file) and not os.environ.get("NRD_HIP_LIBRARY") else None
+            stale = {}
+            if world == 1 and os.path.exists(PMC_TRAFFIC_FILE):
+                entry = json.load(open(PMC_TRAFFIC_FILE)).get("%s_%dx%d%s" % (name, W, H, "_nosky" if args.no_sky else ""), {})
+                k = entry.get("kernels", {}).get(dominant)
+                if k:
+                    stale["counters"] = entry.get("library_digest") is None or entry.get("library_digest") != lib_digest
+                    traffic = int((2.0 * k["FETCH_SIZE_KiB"] + k["WRITE_SIZE_KiB"]) * 1024)
+                    traffic_source = entry.get("source")
+                    if k.get("SQ_INSTS_VALU"):
+                        # the OTHER roofline of a kernel that computes: executed VALU instructions against the issue rate of the chip -- a wave64 VALU instruction occupies its
+                        # SIMD-32 for 2 cycles (v_fma_f32: VALU_SIMDS / VALU_CLOCK_GHZ above), 256 CUs x 4 SIMDs, 2.4 GHz. The instruction count is the recorded
+                        # counter (SQ_INSTS_VALU / launch), the time is this run's: frac = the share of the kernel's time the VALU pipes would need if every instruction were an fma.
+                        issue_ms = k["SQ_INSTS_VALU"] * 2.0 / (VALU_SIMDS * VALU_CLOCK_GHZ * 1e9) * 1e3
+                        valu = {"executed_valu_per_wave": k["valu_per_wave"], "waves_per_launch": int(k["SQ_WAVES"]), "source": entry.get("source"),
+                                "fma_issue_bound_ms": round(issue_ms, 4), "frac": round(issue_ms / passes[dominant]["avg_ms"], 4),
+                                "what": "SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz) against this run's kernel time: the pure-FMA issue bound (selects, conversions, integer "
+                                        "instructions issue at 4, transcendentals at 8 cycles: the measured issue floor below is the tight bound)"}
+            # What the dominant kernel is bound by, measured directly (round 4; the counter-derived "VALU busy" of round 3 read up to 109 % and is gone): its time in
+            # a build whose loads all hit the L1, on a scene where that build computes the same values (bench.py --uniform, csrc/hip/planes.h NRD_EXPERIMENT_L1_RESIDENT).
+            issue_floor = None
+            if world == 1 and os.path.exists(ISSUE_FLOOR_FILE):
+                fl = json.load(open(ISSUE_FLOOR_FILE))
+                frag = {"TemporalAccumulation": "TemporalAccumulationKernel", "TemporalStabilization": "TemporalStabilizationKernel", "HistoryFix": "HistoryFixKernel", "HistoryClamping": "HistoryClampingKernel",
+                        "AtrousSmem": "AtrousSmemKernel", "PrePass": "PrePassKernel" if name.startswith("RELAX") else "ReblurSpatialKernel", "Blur": "ReblurSpatialKernel", "PostBlur": "ReblurSpatialKernel",
+                        "Atrous": "RelaxAtrousKernel"}.get(dominant.rsplit("_", 1)[-1].replace(".cs", ""))
+                rows_fl = next((v for k2, v in fl.get("workloads", {}).items() if k2.startswith(name + " ")), {})
+                hit = next((v for k2, v in rows_fl.items() if frag and frag in k2), None)  # (the first match: the window kernel precedes its fallback)
+                if hit:
+                    issue_floor = dict(hit, source=fl.get("source"), what="uniform scene, every pixel denoised: this kernel's time / its time with every load an L1 hit (not measured in this run)")
+                    stale["issue_floor"] = fl.get("library_digest") is None or fl.get("library_digest") != lib_digest
+            # what the evidence says bounds the kernel: at most 25 % above its L1-resident time -> instruction issue; beyond that the memory system behind the L1 (the request path of
+            # scattered taps / dependent round trips); HBM itself is a quarter busy (frac). `bound` names that; achieved / peak / frac stay the HBM roofline BASELINE.json asks for.
+            bound = "hbm"
+            if issue_floor and issue_floor.get("measured_over_floor"):
+                bound = "valu-issue" if issue_floor["measured_over_floor"] <= 1.25 else "l1-request"
+            roofline = {"bound": bound, "roofline_class": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                        "measured_copy_GBps": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved / copy_gbs, 4),
+                        "denoised_pixel_fraction": round(denoised_fraction, 4), "frac_denoised_pixels": round(achieved / HBM_PEAK_GBS * denoised_fraction, 4),
+                        "traffic": traffic, "traffic_source": traffic_source, "valu": valu, "issue_floor": issue_floor, "avg_kernel_ms": passes[dominant]["avg_ms"],
+                        "library_digest": lib_digest, "stale": (any(stale.values()) if stale else None), "stale_fields": sorted(k2 for k2, v in stale.items() if v),
+                        "algorithmic_bytes_per_launch": passes[dominant]["bytes_per_launch"],
+                        "note": "bound = what the recorded issue-floor evidence says limits the kernel (valu-issue: within 25 % of its L1-resident time; l1-request: the memory system behind the L1); "
+                                "achieved / peak / frac = its algorithmic bytes against the HBM peak (roofline_class), valu.frac = its executed VALU instructions against the chip's fma issue rate; "
+                                "traffic / valu / issue_floor are recorded measurements (profiles/), stamped with the digest of the library they were taken from: stale = not the library timed here; "
+                                "dominant = the pass with the longest average launch; per-pass durations from HIP events on the executor's stream (eager replay of the timed frames); "
+                                "frac counts the algorithmic bytes of EVERY pixel of the frame as the metric does, frac_denoised_pixels only those of the pixels that are not sky; "
+                                "measured_copy_GBps = the library's own 16-B/lane copy kernel on this GPU"}
+        # per frame: every pass once, except the dilated a-trous pass which runs (launches / steps) times
+        per_frame = {k: p["launches"] / args.steps for k, p in passes.items()}
+        gpu_ms = sum(p["avg_ms"] * per_frame[k] for k, p in passes.items())  # (includes the guide-decode kernel; the TemporalAccumulation row includes its fallback launch)
+        total_bpp = sum(bytes_per_pixel[k] * per_frame[k] for k in passes if k in bytes_per_pixel)
+        whole_chain = {"algorithmic_bytes_per_pixel": round(total_bpp, 1), "algorithmic_bytes_per_frame": int(total_bpp * W * H), "sum_kernel_ms": round(gpu_ms, 4),
+                       "GBps": round(total_bpp * rows / (gpu_ms * 1e-3) / 1e9, 1) if gpu_ms else None,
+                       "frac_of_peak": round(total_bpp * rows / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if gpu_ms else None,
+                       "frac_of_measured_copy": round(total_bpp * rows / (gpu_ms * 1e-3) / 1e9 / copy_gbs, 4) if gpu_ms else None}
 
     result = {
         "metric": "Mpixels/s %s @%s%s" % (name, {(2560, 1440): "1440p", (3840, 2160): "4K", (1920, 1080): "1080p"}.get((W, H), "%dx%d" % (W, H)),
@@ -585,7 +595,6 @@ def main():
         "dtype": "f32",
         "data": "synthetic",
         "numerics": "exact",  # one library, one arithmetic: what is timed here is bit-identical to the CPU oracle (see "parity")
-        "tile_fallback": {"tiles": tile_fallback[0], "of": tile_fallback[1], "what": "32x8-pixel tiles of the last frame's rect left to the plain TemporalAccumulation kernel (LDS window too small)"},
         "launch": "eager (one launch per pass, back to back)" if not use_graph else "hipGraph (%d launches, %d builds, %d node updates in the run)" % graph_stats,
         "rccl_ranks": world if distributed and backend == "nccl" else (0 if not distributed else None),
         "config": {"workload": "%s %dx%d, %s, analytic scene%s + 1rpp noise, moving camera" % (name, W, H, "default settings" if overrides is None else "settings %s" % overrides,
@@ -598,7 +607,7 @@ def main():
                                   "all-gather of the owned rows of every OUT_* plane after the last pass into separate complete planes (RCCL, asynchronous: it overlaps the whole next frame and is awaited by wait_outputs()), "
                                   "%.2f MB received per rank per frame, inside the timed region" % (shard.gathered_bytes / max(shard.gather_frames, 1) / 1e6) if args.sharding == "halo" else
                                   "in-place all-gather of every permanent and transient full-resolution plane and every output (FrameSharder)"),
-                   "halo_bytes_received_per_rank_per_frame": (int(shard.exchanged_bytes / max(total + args.steps + 5, 1)) if shard is not None and args.sharding == "halo" else None),
+                   "halo_bytes_received_per_rank_per_frame": (int(shard.exchanged_bytes / max(total + args.steps + 5 if args.full else total, 1)) if shard is not None and args.sharding == "halo" else None),
                    "gather_bytes_received_per_rank_per_frame": (int(shard.gathered_bytes / max(shard.gather_frames, 1)) if shard is not None and args.sharding == "halo" else None),
                    "motion_bound": (None if shard is None or args.sharding != "halo" else
                                     {"source": "device reduction per strip + MAX over ranks (nrdHipMeasureMotionRows)" if args.motion_bound == "measure" else "camera estimate (5 x 5 samples)",
@@ -606,20 +615,20 @@ def main():
                                      # (round 6) what the measured surface motion cannot bound -- virtual motion and look-back taps of the specular signal -- as the temporal kernels
                                      # reported it for the previous frame (nrdHipSetHistoryReachWord), and the sharded frames that turned out to have read beyond their halo
                                      "last_history_reach_rows": shard.history_reach_rows, "history_halo_violations": shard.history_halo_violations}),
-                   "storage": "reference pool formats (fp16 history, R10G10B10A2 normals), %.0f B/px/frame compulsory traffic" % total_bpp},
-        "roofline": roofline,
-        "whole_chain": whole_chain,
-        "passes": passes,
-        "frame_ms": frame_ms,
+                   # (the B/px come from the launches per frame the --full replay counts)
+                   "storage": "reference pool formats (fp16 history, R10G10B10A2 normals)" + (", %.0f B/px/frame compulsory traffic" % total_bpp if args.full else "")},
         # which regime of the temporal chain the timed frames are in: SURVEY section 8d specifies 32 warm-up frames + the mean of 64 (this file's
         # default); a shorter warm-up times frames whose history is still growing (maxAccumulatedFrameNum 30), with wider blur radii: slightly more work per frame
         "protocol": {"timed_frames": "%d..%d after the CLEAR_AND_RESTART frame 0" % (args.warmup, total - 1),
                      "regime": "steady state (history saturated: SURVEY 8d, 32 warm-up + 64 timed)" if args.warmup >= 30 else "accumulating (history below maxAccumulatedFrameNum = 30 during part of the timed frames)"},
     }
-    if not args.no_cpu_baseline and world == 1:
-        result["cpu_baseline"], result["parity"] = cpu_baseline(name, W, H, min(args.cpu_frames, distinct), seq, overrides, check_parity=not args.no_parity)
-    else:
-        result["cpu_baseline"], result["parity"] = None, None
+    if args.full:
+        result.update(tile_fallback={"tiles": tile_fallback[0], "of": tile_fallback[1], "what": "32x8-pixel tiles of the last frame's rect left to the plain TemporalAccumulation kernel (LDS window too small)"},
+                      roofline=roofline, whole_chain=whole_chain, passes=passes, frame_ms=frame_ms)
+        if not args.no_cpu_baseline and world == 1:
+            result["cpu_baseline"], result["parity"] = cpu_baseline(name, W, H, min(args.cpu_frames, distinct), seq, overrides, check_parity=not args.no_parity)
+        else:
+            result["cpu_baseline"], result["parity"] = None, None
     if dumped is not None:
         import numpy as np
 

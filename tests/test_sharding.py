@@ -919,7 +919,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, NRD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = 29500 + (os.getpid() % 100)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--width", "512", "--height", "600"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--width", "512", "--height", "600", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

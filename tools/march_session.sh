@@ -2,10 +2,11 @@
 # (round 6 development) A/B of the marching a-trous kernel on the GPU box: bash tools/march_session.sh TAG [pmc]
 cd "$(dirname "$0")/.." 2>/dev/null; export TMPDIR=/tmp
 tag=$1
-timeout 900 python -m pytest tests/test_relax.py -m gpu -x -q > gpurun_out/${tag}_pytest_relax.log 2>&1; tail -3 gpurun_out/${tag}_pytest_relax.log
+out=${OUT_DIR:-session_out}; mkdir -p $out
+timeout 900 python -m pytest tests/test_relax.py -m gpu -x -q > $out/${tag}_pytest_relax.log 2>&1; tail -3 $out/${tag}_pytest_relax.log
 trace() { local name=$1; shift; rm -rf /tmp/prof_t
-  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_t -o trace -- python bench.py --workload relax_ds_sh --steps 20 --warmup 8 --no-cpu-baseline "$@" > gpurun_out/${tag}_${name}_trace_bench.json 2> gpurun_out/${tag}_${name}_trace.err
-  python tools/rocprof_summary.py $(find /tmp/prof_t -name "*.db" | head -1) > gpurun_out/${tag}_${name}_kernel_stats.txt 2>&1; grep -i "atrous" gpurun_out/${tag}_${name}_kernel_stats.txt | cut -c1-150; tail -1 gpurun_out/${tag}_${name}_trace_bench.json | cut -c1-200; }
+  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_t -o trace -- python bench.py --full --workload relax_ds_sh --steps 20 --warmup 8 --no-cpu-baseline "$@" > $out/${tag}_${name}_trace_bench.json 2> $out/${tag}_${name}_trace.err
+  python tools/rocprof_summary.py $(find /tmp/prof_t -name "*.db" | head -1) > $out/${tag}_${name}_kernel_stats.txt 2>&1; grep -i "atrous" $out/${tag}_${name}_kernel_stats.txt | cut -c1-150; tail -1 $out/${tag}_${name}_trace_bench.json | cut -c1-200; }
 NRD_HIP_ATROUS_MARCH=0 trace off --no-parity
 trace on
 NRD_HIP_ATROUS_MARCH_SEG=4 trace seg4 --no-parity
