@@ -227,7 +227,7 @@ static uint32_t CreateExecutorImpl(void* instance, uint16_t resourceWidth, uint1
     // per-tile flags of the passes that run as a fast kernel plus a fallback kernel for the tiles the fast one declines (tiny: one byte per 32x8 pixels)
     e->tileFlags.w = (resourceWidth + 31) / 32;
     e->tileFlags.h = (resourceHeight + 7) / 8;
-    e->tileFlags.pitch = (uint32_t)e->tileFlags.w;
+    e->tileFlags.pitch = ((uint32_t)e->tileFlags.w + (uint32_t)TILE_FLAG_GROUP - 1u) / (uint32_t)TILE_FLAG_GROUP * (uint32_t)TILE_FLAG_GROUP; // the fallback kernels read whole groups of flags (planes.h AnyTileFlagUniform)
     if (hipMalloc((void**)&e->tileFlags.ptr, (size_t)e->tileFlags.pitch * (size_t)e->tileFlags.h) != hipSuccess) {
         if (e->arena && e->ownsArena)
             (void)hipFree(e->arena);

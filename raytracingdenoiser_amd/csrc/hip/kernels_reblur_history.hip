@@ -25,14 +25,7 @@ static const char* CheckSupportedHistory(const ReblurCB& c) {
     return nullptr;
 }
 
-NRD_D bool BlockHasGeometry(const Plane& tiles, int blockX, int blockY) {
-    const int tileY = (blockY * TILE_Y) >> 4, tileX0 = (blockX * TILE_X) >> 4;
-    bool any = false;
-    for (int t = 0; t < TILE_X / 16; t++)
-        if (tileX0 + t < tiles.w && tileY < tiles.h)
-            any |= LoadR8Unorm(tiles, tileX0 + t, tileY) == 0.0f;
-    return any;
-}
+static_assert(TILE_X == 32 && TILE_Y == 8, "planes.h LoadBlockTileBytes: a workgroup covers two 16x16 tiles of one tile row");
 
 // ================================================================================================ HistoryFix
 namespace hf {
@@ -220,11 +213,12 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF) void 
     const int px = tileX * TILE_X + tx, py = blockY * TILE_Y + ty;
     const int rw = c.gRectSizeMinusOne.x, rh = c.gRectSizeMinusOne.y;
 
-    if (!BlockHasGeometry(P.tiles, tileX, blockY))
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, tileX, blockY); // scalar, uniform per workgroup (planes.h)
+    if (!TileBytesHaveGeometry<2>(tileBytes))
         return;
     // the pixel's own inputs, requested in front of the tile fill (see ReblurTemporalStabilizationKernel; this pass ran 32 % above its L1-resident time)
     const int qx = min(px, rw), qy = min(max(py, 0), rh);
-    const float preTile = LoadR8Unorm(P.tiles, qx >> 4, qy >> 4);
+    const bool preSky = TileByteIsSky(tileBytes, tx >> 4); // a thread that stays has (qx, qy) = (px, py): one of the two tiles under this workgroup
     const float preViewZ = LoadR32F(P.viewZ, qx, qy);
     float preMaterialID;
     const float4 preNormalAndRoughness = LoadDecodedNormalRoughness(P.decodedNR, qx, qy, preMaterialID);
@@ -249,7 +243,7 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF) void 
 
     if (px > rw || py > rh || py < rr.rowBegin || py >= rr.rowEnd)
         return;
-    if (preTile != 0.0f)
+    if (preSky)
         return;
     HfPixel s;
     s.viewZ = UnpackViewZ(c, preViewZ);
@@ -376,13 +370,14 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_TS) void ReblurTem
     const int px = BlockTileX(rr) * TILE_X + tx, py = blockY * TILE_Y + ty;
     const int rw = c.gRectSizeMinusOne.x, rh = c.gRectSizeMinusOne.y;
 
-    if (!BlockHasGeometry(P.tiles, BlockTileX(rr), blockY))
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, BlockTileX(rr), blockY); // scalar, uniform per workgroup (planes.h)
+    if (!TileBytesHaveGeometry<2>(tileBytes))
         return;
     // The pixel's own inputs do not depend on the luma tile: they are requested in FRONT of the tile fill, so that one memory latency covers both. Behind the
     // barrier (rounds 1-3) they were a second, fully exposed latency in front of a third (the history fetch at the reprojected position): this pass ran 26 % above
     // the time of a build whose loads all hit the L1 (profiles/r04_c_reblur_ds_uniform_*_kernel_stats.txt). Clamped coordinates: threads outside the rect leave later.
     const int qx = min(px, rw), qy = min(max(py, 0), rh);
-    const float preTile = LoadR8Unorm(P.tiles, qx >> 4, qy >> 4);
+    const bool preSky = TileByteIsSky(tileBytes, tx >> 4); // a thread that stays has (qx, qy) = (px, py): one of the two tiles under this workgroup
     const float preViewZ = LoadR32F(P.viewZ, qx, qy);
     const float4 preMv = LoadRGBA16F(P.mv, qx, qy);
     float preMaterialID;
@@ -409,7 +404,7 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_TS) void ReblurTem
 
     if (px > rw || py > rh || py < rr.rowBegin || py >= rr.rowEnd)
         return;
-    if (preTile != 0.0f)
+    if (preSky)
         return;
     const float viewZ = UnpackViewZ(c, preViewZ);
     if (viewZ > c.gDenoisingRange)

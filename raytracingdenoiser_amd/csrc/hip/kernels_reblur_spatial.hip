@@ -22,6 +22,7 @@ namespace nrdhip {
 
 constexpr int TILE_X = 32;
 constexpr int TILE_Y = 8;
+static_assert(TILE_X == 32 && TILE_Y == 8, "planes.h LoadBlockTileBytes: a workgroup covers two 16x16 tiles of one tile row");
 
 // ================================================================================================ ClassifyTiles
 __global__ __launch_bounds__(256) void ReblurClassifyTilesKernel(Plane viewZ, Plane tiles, float viewZScale, float denoisingRange, int tilesPerRow, int tileRows) {
@@ -503,14 +504,20 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_SPATIAL) void Rebl
     typedef ReblurSignal<KIND> Sig;
     constexpr bool OCC = KIND == SIGNAL_OCCLUSION;
     typedef typename Sig::type S;
-    const int px = BlockTileX(rr) * TILE_X + (threadIdx.x % TILE_X);
+    const int tileX = BlockTileX(rr);
+    const int px = tileX * TILE_X + (threadIdx.x % TILE_X);
     // NRD_ALT_TILE_ORDER (A/B, round 6): the passes of the chain alternate their walk through the tile rows as the reference's NRD_CTA_ORDER_DEFAULT / _REVERSED do
     // (Common.hlsli:92-106: "helps to reuse data already stored in caches") -- PrePass top-down, TemporalAccumulation bottom-up, HistoryFix top-down, Blur bottom-up, PostBlur
     // top-down, TemporalStabilization bottom-up: every pass starts on the rows its predecessor wrote last
-    const int py = (BlockTileY(rr, NRD_ALT_TILE_ORDER && MODE == BLUR)) * TILE_Y + (threadIdx.x / TILE_X);
+    const int blockY = BlockTileY(rr, NRD_ALT_TILE_ORDER && MODE == BLUR);
+    const int py = blockY * TILE_Y + (threadIdx.x / TILE_X);
+    // a workgroup over sky tiles only leaves on a scalar test, before any vector-memory instruction (planes.h LoadTileBytesUniform)
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, tileX, blockY);
+    if (!TileBytesHaveGeometry<2>(tileBytes))
+        return;
     if (px > c.gRectSizeMinusOne.x || py > c.gRectSizeMinusOne.y || py < rr.rowBegin || py >= rr.rowEnd)
         return;
-    if (LoadR8Unorm(P.tiles, px >> 4, py >> 4) != 0.0f)
+    if (TileByteIsSky(tileBytes, (threadIdx.x % TILE_X) >> 4)) // a workgroup that straddles a sky tile and a geometry tile
         return;
 
     const float viewZpacked = LoadR32F(P.viewZ, px, py);
@@ -756,12 +763,16 @@ template <bool DIFF, bool SPEC, int BORDER, bool PERF, int KIND>
 __global__ __launch_bounds__(TILE_X* TILE_Y) void ReblurHitDistReconstructionKernel(ReblurCB c, HitDistPlanes P, RowRange rr) {
     typedef ReblurSignal<KIND> Sig;
     typedef typename Sig::type S;
-    const int px = BlockTileX(rr) * TILE_X + (threadIdx.x % TILE_X);
-    const int py = (BlockTileY(rr)) * TILE_Y + (threadIdx.x / TILE_X);
+    const int tileX = BlockTileX(rr), blockY = BlockTileY(rr);
+    const int px = tileX * TILE_X + (threadIdx.x % TILE_X);
+    const int py = blockY * TILE_Y + (threadIdx.x / TILE_X);
     const int rw = c.gRectSizeMinusOne.x, rh = c.gRectSizeMinusOne.y;
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, tileX, blockY); // scalar, uniform per workgroup (planes.h)
+    if (!TileBytesHaveGeometry<2>(tileBytes))
+        return;
     if (px > rw || py > rh || py < rr.rowBegin || py >= rr.rowEnd)
         return;
-    if (LoadR8Unorm(P.tiles, px >> 4, py >> 4) != 0.0f)
+    if (TileByteIsSky(tileBytes, (threadIdx.x % TILE_X) >> 4))
         return;
     const float centerZ = UnpackViewZ(c, LoadR32F(P.viewZ, px, py));
     if (centerZ > c.gDenoisingRange)

@@ -20,6 +20,7 @@ namespace nrdhip {
 
 constexpr int TILE_X = 32;
 constexpr int TILE_Y = 8;
+static_assert(TILE_X == 32 && TILE_Y == 8, "planes.h LoadBlockTileBytes: a workgroup covers two 16x16 tiles of one tile row");
 constexpr int BORDER = 1;
 constexpr int BUF_X = TILE_X + 2 * BORDER; // 34
 constexpr int BUF_Y = TILE_Y + 2 * BORDER; // 10
@@ -29,6 +30,9 @@ constexpr int BUF_STRIDE = BUF_X + 1;      // 35 float4 slots per row
 #ifndef NRD_TA_WIN_H
 #define NRD_TA_WIN_W 64 // at most 64: one lane per column when the window is filled
 #define NRD_TA_WIN_H 16
+#endif
+#ifndef NRD_TA_SKY_FLAG_STORE
+#define NRD_TA_SKY_FLAG_STORE 1 // (A/B switch, tools/build_variant.py; 0 is not a product build: the fallback statistics would count stale flags)
 #endif
 constexpr int WIN_W = NRD_TA_WIN_W;
 constexpr int WIN_H = NRD_TA_WIN_H;
@@ -119,24 +123,22 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
     // The pixel's own guides do not depend on the LDS tile: they are requested in FRONT of the fill (below, behind the uniform sky test), so that one memory latency
     // covers both; behind the barrier they were a second exposed latency in front of the window fill / the history footprints (the pass ran 19 % above the time of
     // a build whose loads all hit the L1, profiles/r04_c_reblur_ds_uniform_*_kernel_stats.txt)
-    float preTile = 0.0f, preViewZ = 0.0f, preMaterialID = 0.0f;
+    float preViewZ = 0.0f, preMaterialID = 0.0f;
     float4 preMv = F4(0.0f), preNormalAndRoughness = F4(0.0f);
     // ---- cooperative preload (clamped to the rect), skipped when every 16x16 tile under this block is sky
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, tileX, blockY); // scalar, uniform per workgroup (planes.h)
+    const bool preSky = TileByteIsSky(tileBytes, tx >> 4); // an active thread's pixel lies in one of the two tiles under this workgroup
     {
-        const int tileY = (blockY * TILE_Y) >> 4, tileX0 = (tileX * TILE_X) >> 4;
-        bool anyGeometry = false;
-        for (int t = 0; t < TILE_X / 16; t++)
-            if (tileX0 + t < P.tiles.w && tileY < P.tiles.h)
-                anyGeometry |= LoadR8Unorm(P.tiles, tileX0 + t, tileY) == 0.0f;
-        if (!anyGeometry) {
-            if (MODE == 1 && threadIdx.x == 0 && tileFlag)
+        if (!TileBytesHaveGeometry<2>(tileBytes)) {
+            // (the flag byte of a sky tile: one store of lane 0 that nothing waits for. NRD_TA_SKY_FLAG_STORE=0, an A/B build that leaves the byte stale, measures what
+            // it costs the exit: nothing that a kernel trace resolves -- profiles/HISTORY.md)
+            if (NRD_TA_SKY_FLAG_STORE && MODE == 1 && threadIdx.x == 0 && tileFlag)
                 *tileFlag = 0;
             return; // uniform across the block
         }
 
         if (MODE == 1) { // (the plain kernels sit at their register budget: there the guides are requested behind the barrier as before)
             const int qx = min(px, rw), qy = min(max(py, 0), rh);
-            preTile = LoadR8Unorm(P.tiles, qx >> 4, qy >> 4);
             preViewZ = LoadR32F(P.viewZ, qx, qy);
             preMv = LoadRGBA16F(P.mv, qx, qy);
             preNormalAndRoughness = LoadDecodedNormalRoughness(P.decodedNR, qx, qy, preMaterialID);
@@ -170,12 +172,11 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
     if (MODE != 1 && !active)
         return;
     if (MODE != 1) {
-        preTile = LoadR8Unorm(P.tiles, lpx >> 4, lpy >> 4);
-        if (preTile != 0.0f)
+        if (preSky)
             return;
         preViewZ = LoadR32F(P.viewZ, lpx, lpy);
     }
-    active = active && preTile == 0.0f; // (MODE 1: the prefetch position is (lpx, lpy) for every thread that stays)
+    active = active && !preSky;
     const float viewZ = UnpackViewZ(c, preViewZ);
     active = active && !(viewZ > c.gDenoisingRange);
     if (MODE != 1 && !active)
@@ -1039,9 +1040,9 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
 }
 
 // MODE 0 / 1: one workgroup per tile (XCD-aware order). MODE 2 (fallback behind the window kernel): one workgroup per FALLBACK_TILES tile columns, which walks
-// them and runs the pass on the flagged ones -- normally none: 4 us per launch where one workgroup per tile with a flag test in front cost 14 us
-// (profiles/r03_k_reblur_ds_kernel_stats.txt against r03_i_reblur_ds_kernel_stats.txt).
-constexpr int FALLBACK_TILES = 8;
+// them and runs the pass on the flagged ones -- normally none. One workgroup per tile with a flag test in front cost 14 us per launch, one per 8 tile columns
+// 4.5 us (profiles/r03_k_reblur_ds_kernel_stats.txt against r03_i_reblur_ds_kernel_stats.txt); one per 64 columns with a scalar flag scan: profiles/HISTORY.md.
+constexpr int FALLBACK_TILES = TILE_FLAG_GROUP;
 template <bool DIFF, bool SPEC, bool PERF, int KIND, bool SH, int WAVES, int MODE>
 __global__ __launch_bounds__(TILE_X* TILE_Y, WAVES) void ReblurTemporalAccumulationKernel(ReblurCB cArg, TaPlanes P, RowRange rr) {
     const int blockY = BlockTileY(rr, true);
@@ -1049,22 +1050,16 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, WAVES) void ReblurTemporalAccumulat
         ReblurTemporalAccumulationTile<DIFF, SPEC, PERF, KIND, SH, MODE>(cArg, P, rr, BlockTileX(rr), blockY);
         return;
     }
-    if (blockY >= P.tileFlags.h)
-        return;
-    // the FALLBACK_TILES flags of this workgroup with ONE memory latency: lane k of every wave reads flag k, the set bits are OR-ed across the wave
-    // (read one after the other, the eight dependent loads were the whole cost of this kernel: 14 us per launch with nothing to do, r03_j)
-    const int lane = threadIdx.x & 63, firstTile = (int)blockIdx.x * FALLBACK_TILES;
-    int mask = 0;
-    if (lane < FALLBACK_TILES && firstTile + lane < P.tileFlags.w)
-        mask = P.tileFlags.ptr[(uint32_t)blockY * P.tileFlags.pitch + (uint32_t)(firstTile + lane)] != 0 ? 1 << lane : 0;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        mask |= __shfl_xor(mask, m);
-    if (mask == 0)
-        return; // the window kernel has done all these tiles (uniform; the usual case)
+    // the flags of this workgroup's FALLBACK_TILES tile columns in one scalar request, OR-ed on the scalar unit (planes.h AnyTileFlagUniform): a workgroup that finds
+    // nothing -- the usual case -- issues no vector-memory instruction at all. (Round 3: eight dependent loads, 14 us per launch with nothing to do; one vector load per
+    // wave and 8 columns per workgroup, 4.5 us. This form launches a fifth of the waves and measures the same 4.5 us: what is left is the launch, profiles/HISTORY.md.)
+    const int firstTile = (int)blockIdx.x * FALLBACK_TILES;
+    if (!AnyTileFlagUniform(P.tileFlags, firstTile, min(blockY, P.tileFlags.h - 1)) || blockY >= P.tileFlags.h) // (one batch of kernel arguments, one flag request)
+        return; // the window kernel has done all these tiles (uniform)
+    const int endTile = min(FALLBACK_TILES, P.tileFlags.w - firstTile);
 #pragma nounroll
-    for (int k = 0; k < FALLBACK_TILES; k++) {
-        if (!(mask & (1 << k)))
+    for (int k = 0; k < endTile; k++) {
+        if (!TileFlagUniform(P.tileFlags, firstTile + k, blockY))
             continue;
         __syncthreads(); // the LDS tiles of the previous iteration are free
         ReblurTemporalAccumulationTile<DIFF, SPEC, PERF, KIND, SH, MODE>(cArg, P, rr, firstTile + k, blockY);
@@ -1144,7 +1139,8 @@ static const char* LaunchTemporalAccumulation(const PassArgs& a) {
     // single-signal denoisers (REBLUR_DIFFUSE: 0.126 + launch of the fallback against 0.112 -- the plain kernel already runs 3 waves and is VALU-bound, r03_i)
     constexpr bool HAS_WINDOW = DIFF && SPEC && !PERF && KIND == SIGNAL_RADIANCE;
     if (HAS_WINDOW && windowEnv && !wavesEnv) {
-        if (!a.tileFlags.ptr || (uint32_t)a.tileFlags.w * TILE_X < (uint32_t)P.viewZ.w || (uint32_t)a.tileFlags.h * TILE_Y < (uint32_t)P.viewZ.h)
+        if (!a.tileFlags.ptr || (uint32_t)a.tileFlags.w * TILE_X < (uint32_t)P.viewZ.w || (uint32_t)a.tileFlags.h * TILE_Y < (uint32_t)P.viewZ.h ||
+            a.tileFlags.pitch % TILE_FLAG_GROUP != 0 || ((uintptr_t)a.tileFlags.ptr & 255u) != 0) // (planes.h AnyTileFlagUniform: whole groups of flags are read at once)
             return "REBLUR temporal accumulation: the executor's tile-flag scratch is missing or too small";
         P.tileFlags = a.tileFlags;
         // both kernels of the pass only look at the flags of the rect's tile columns (dynamic resolution: columns beyond keep whatever an earlier, larger rect left)

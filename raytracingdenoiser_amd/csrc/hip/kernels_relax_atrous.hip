@@ -92,7 +92,8 @@ __global__ __launch_bounds__(256, NRD_WAVES_RELAX_ATROUS_SMEM) void RelaxAtrousS
     // Every thread the reference launches (8x8 groups over the rect) forwards the guides to the "previous frame" planes,
     // sky or not; threads of all-sky tiles read unwritten group-shared memory there, which we define as zero.
     const bool inGrid = px < ((rectW + 7) & ~7) && py < ((rectH + 7) & ~7);
-    const bool blockHasGeometry = RelaxBlockHasGeometry(P.tiles, BlockTileX(rows), blockY);
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, BlockTileX(rows), blockY); // scalar, uniform per workgroup (planes.h)
+    const bool blockHasGeometry = TileBytesHaveGeometry<2>(tileBytes);
 
     // (measured and dropped, r04_g: requesting the pixel's own small inputs in front of the tile fill as the temporal passes do -- 0.327 against 0.310 ms)
     if (blockHasGeometry) {
@@ -726,17 +727,11 @@ __global__ __launch_bounds__(256, NRD_WAVES_RELAX_ATROUS) void RelaxAtrousKernel
     const int blockX0 = BlockTileX(rows) * TILE_X, blockY0 = blockY * TILE_Y;
     const int px = blockX0 + tx, py = blockY0 + ty;
     const int rectW = c.shared.gRectSize.x, rectH = c.shared.gRectSize.y;
-    if (TILED || BANDED) {
-        // uniform early-outs: a workgroup beyond the rect, or over sky tiles only (TILE_X = 32 = two 16x16 tiles, TILE_Y = 8: one tile row)
-        if (blockX0 >= rectW || blockY0 >= rectH)
-            return;
-        bool anyGeometry = false;
-        for (int t = 0; t < TILE_X / 16; t++)
-            if ((blockX0 >> 4) + t < P.tiles.w && (blockY0 >> 4) < P.tiles.h)
-                anyGeometry |= LoadR8Unorm(P.tiles, (blockX0 >> 4) + t, blockY0 >> 4) == 0.0f;
-        if (!anyGeometry)
-            return;
-    }
+    // uniform early-outs: a workgroup beyond the rect, or over sky tiles only (TILE_X = 32 = two 16x16 tiles, TILE_Y = 8: one tile row); the tile bytes come
+    // through the scalar cache (planes.h LoadTileBytesUniform), so such a workgroup leaves before it has issued a vector-memory or LDS instruction
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, BlockTileX(rows), blockY);
+    if (blockX0 >= rectW || blockY0 >= rectH || !TileBytesHaveGeometry<2>(tileBytes))
+        return;
     if (TILED) {
         for (int i = threadIdx.x; i < TW * TH; i += 256) {
             const int lx = i % TW, ly = i / TW;
@@ -769,7 +764,7 @@ __global__ __launch_bounds__(256, NRD_WAVES_RELAX_ATROUS) void RelaxAtrousKernel
     const int pxv = BANDED && !active ? blockX0 : px, pyv = BANDED && !active ? blockY0 : py;
 #define px pxv
 #define py pyv
-    if (LoadR8Unorm(P.tiles, px >> 4, py >> 4) != 0.0f) {
+    if (TileByteIsSky(tileBytes, (px - blockX0) >> 4)) { // (px, py) lies under this workgroup
         if (!BANDED)
             return;
         active = false;
@@ -1134,9 +1129,10 @@ __global__ __launch_bounds__(march::THREADS, STEP == 8 ? 4 : 2) void RelaxAtrous
     uint64_t geometry = 0;
     for (int i = 0; i < numSteps; i++) {
         const int tileY = (segY0 + i * H) >> 4;
+        const uint32_t tileBytes = LoadTileBytesUniform<W / 16>(P.tiles, blockX0 >> 4, tileY); // scalar (planes.h); a tile outside the plane reads as sky
 #pragma unroll
         for (int t = 0; t < W / 16; t++)
-            if ((blockX0 >> 4) + t < P.tiles.w && tileY < P.tiles.h && segY0 + i * H < rectH && LoadR8U(P.tiles, (blockX0 >> 4) + t, tileY) == 0u)
+            if (segY0 + i * H < rectH && !TileByteIsSky(tileBytes, t))
                 geometry |= (uint64_t)1 << (2 * i + t);
     }
     if (geometry == 0)

@@ -80,11 +80,15 @@ struct HitDistPlanes {
 template <bool DIFF, bool SPEC, int BORDER>
 __global__ __launch_bounds__(256) void RelaxHitDistReconstructionKernel(HitDistPlanes P, RelaxCB c, RowRange rows) {
     const int blockY = BlockTileY(rows, true);
+    // a workgroup over sky tiles only leaves on a scalar test, before any vector-memory instruction (planes.h LoadTileBytesUniform)
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, BlockTileX(rows), blockY);
+    if (!TileBytesHaveGeometry<2>(tileBytes))
+        return;
     const int px = BlockTileX(rows) * TILE_X + (threadIdx.x & 31), py = blockY * TILE_Y + (threadIdx.x >> 5);
     const int rectW = c.shared.gRectSize.x, rectH = c.shared.gRectSize.y;
     if (px >= rectW || py >= rectH || py < rows.rowBegin || py >= rows.rowEnd)
         return;
-    if (LoadR8Unorm(P.tiles, px >> 4, py >> 4) != 0.0f)
+    if (TileByteIsSky(tileBytes, (threadIdx.x & 31) >> 4)) // a workgroup that straddles a sky tile and a geometry tile
         return;
     const float centerViewZ = RelaxUnpackViewZ(c, LoadR32F(P.viewZ, px, py));
     if (centerViewZ > c.shared.gDenoisingRange)
@@ -252,11 +256,15 @@ NRD_D PrePassGuides FetchPrePassGuides(const RelaxCB& c, const PrePassPlanes& P,
 template <bool DIFF, bool SPEC, bool SH, bool CB, bool FR, bool MAT = true, bool NT = false>
 __global__ __launch_bounds__(256, NRD_WAVES_RELAX_PREPASS) void RelaxPrePassKernel(PrePassPlanes P, RelaxCB c, RowRange rows) {
     const int blockY = BlockTileY(rows, true);
+    // a workgroup over sky tiles only leaves on a scalar test, before any vector-memory instruction (planes.h LoadTileBytesUniform)
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, BlockTileX(rows), blockY);
+    if (!TileBytesHaveGeometry<2>(tileBytes))
+        return;
     const int px = BlockTileX(rows) * TILE_X + (threadIdx.x & 31), py = blockY * TILE_Y + (threadIdx.x >> 5);
     const int rectW = c.shared.gRectSize.x, rectH = c.shared.gRectSize.y;
     if (px >= rectW || py >= rectH || py < rows.rowBegin || py >= rows.rowEnd)
         return;
-    if (LoadR8Unorm(P.tiles, px >> 4, py >> 4) != 0.0f)
+    if (TileByteIsSky(tileBytes, (threadIdx.x & 31) >> 4)) // a workgroup that straddles a sky tile and a geometry tile
         return;
     float centerViewZ = RelaxUnpackViewZ(c, LoadR32F(P.viewZ, px, py));
     if (centerViewZ > c.shared.gDenoisingRange)
@@ -503,16 +511,20 @@ template <bool DIFF, bool SPEC, bool SH>
 __global__ __launch_bounds__(256, NRD_WAVES_RELAX_HF) void RelaxHistoryFixKernel(HistoryFixPlanes P, RelaxCB c, RowRange rows) {
     const int blockY = BlockTileY(rows, false) /* (top-down: 0.0985 against 0.101 ms bottom-up, r04_v / r04_w) */;
     // (rotated tile order: the pixels with young history -- all this pass works on -- are the columns entering the screen and the silhouettes; passes.h BlockTileXRotated)
-    const int px = (NRD_RELAX_HF_ROTATE ? BlockTileXRotated(rows, blockY) : BlockTileX(rows)) * TILE_X + (threadIdx.x & 31), py = blockY * TILE_Y + (threadIdx.x >> 5);
+    const int tileX = NRD_RELAX_HF_ROTATE ? BlockTileXRotated(rows, blockY) : BlockTileX(rows);
+    // a workgroup over sky tiles only leaves on a scalar test, before any vector-memory instruction (planes.h LoadTileBytesUniform)
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, tileX, blockY);
+    if (!TileBytesHaveGeometry<2>(tileBytes))
+        return;
+    const int px = tileX * TILE_X + (threadIdx.x & 31), py = blockY * TILE_Y + (threadIdx.x >> 5);
     const int rectW = c.shared.gRectSize.x, rectH = c.shared.gRectSize.y;
     if (px >= rectW || py >= rectH || py < rows.rowBegin || py >= rows.rowEnd)
         return;
     // the three loads that decide whether the pixel has anything to do, requested together (one memory latency instead of two: in the steady state nearly every
     // pixel leaves here, and the pass ran 60 % above the time of a build whose loads all hit the L1, profiles/r04_c_relax_ds_sh_uniform_*_kernel_stats.txt)
-    const float tileFlag = LoadR8Unorm(P.tiles, px >> 4, py >> 4);
     float centerViewZ = RelaxUnpackViewZ(c, LoadR32F(P.viewZ, px, py));
     float historyLength = 255.0f * LoadR8Unorm(P.historyLength, px, py);
-    if (tileFlag != 0.0f)
+    if (TileByteIsSky(tileBytes, (threadIdx.x & 31) >> 4))
         return;
     if (centerViewZ > c.shared.gDenoisingRange || (historyLength > c.shared.gHistoryFixFrameNum || c.shared.gHistoryFixFrameNum == 1.0f))
         return;
@@ -700,10 +712,14 @@ NRD_D void AntiFireflySignal(const RelaxCB& c, const SignalPlanes& S, const Plan
 template <bool DIFF, bool SPEC>
 __global__ __launch_bounds__(256) void RelaxAntiFireflyKernel(AntiFireflyPlanes P, RelaxCB c, RowRange rows) {
     const int blockY = BlockTileY(rows, true);
+    // a workgroup over sky tiles only leaves on a scalar test, before any vector-memory instruction (planes.h LoadTileBytesUniform)
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, BlockTileX(rows), blockY);
+    if (!TileBytesHaveGeometry<2>(tileBytes))
+        return;
     const int px = BlockTileX(rows) * TILE_X + (threadIdx.x & 31), py = blockY * TILE_Y + (threadIdx.x >> 5);
     if (px >= c.shared.gRectSize.x || py >= c.shared.gRectSize.y || py < rows.rowBegin || py >= rows.rowEnd)
         return;
-    if (LoadR8Unorm(P.tiles, px >> 4, py >> 4) != 0.0f)
+    if (TileByteIsSky(tileBytes, (threadIdx.x & 31) >> 4)) // a workgroup that straddles a sky tile and a geometry tile
         return;
     if (RelaxUnpackViewZ(c, LoadR32F(P.viewZ, px, py)) > c.shared.gDenoisingRange)
         return;

@@ -86,7 +86,8 @@ __device__ __forceinline__ void RelaxTemporalAccumulationTile(const RelaxCB& cAr
 
     // (workgroups of the XCD-aware grid may lie beyond the frame: they have no pixels and no flag)
     uint8_t* const tileFlag = (MODE == 1 && tileX < P.tileFlags.w && blockY < P.tileFlags.h) ? P.tileFlags.ptr + (uint32_t)blockY * P.tileFlags.pitch + (uint32_t)tileX : nullptr;
-    if (!RelaxBlockHasGeometry(P.tiles, tileX, blockY)) { // uniform per workgroup
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, tileX, blockY); // scalar, uniform per workgroup (planes.h)
+    if (!TileBytesHaveGeometry<2>(tileBytes)) {
         if (MODE == 1 && threadIdx.x == 0 && tileFlag)
             *tileFlag = 0;
         return;
@@ -96,7 +97,7 @@ __device__ __forceinline__ void RelaxTemporalAccumulationTile(const RelaxCB& cAr
     // a second exposed latency in front of the third and fourth (previous-frame footprints at the surface-motion, then at the virtual-motion position): the
     // pass ran 39 % above the time of a build whose loads all hit the L1 (profiles/r04_c_relax_ds_sh_uniform_*_kernel_stats.txt).
     const int qx = min(px, rectW - 1), qy = min(max(py, 0), rectH - 1);
-    const float preTile = LoadR8Unorm(P.tiles, qx >> 4, qy >> 4);
+    const bool preSky = TileByteIsSky(tileBytes, tx >> 4); // a thread that stays has (qx, qy) = (px, py): one of the two tiles under this workgroup
     const float preViewZ = LoadR32F(P.viewZ, qx, qy);
     const float4 preMv = LoadRGBA16F(P.mv, qx, qy);
     float preMaterialID;
@@ -127,7 +128,7 @@ __device__ __forceinline__ void RelaxTemporalAccumulationTile(const RelaxCB& cAr
     bool active = !(px >= rectW || py >= rectH || py < rows.rowBegin || py >= rows.rowEnd);
     if (MODE != 1 && !active)
         return;
-    active = active && preTile == 0.0f; // (qx, qy) = (lpx, lpy) for every thread that stays
+    active = active && !preSky;
     if (MODE != 1 && !active)
         return;
     const float currentLinearZ = RelaxUnpackViewZ(c, preViewZ);
@@ -744,7 +745,7 @@ __device__ __forceinline__ void RelaxTemporalAccumulationTile(const RelaxCB& cAr
 
 // MODE 0 / 1: one workgroup per tile (XCD-aware order). MODE 2 (fallback behind the window kernel): one workgroup per FALLBACK_TILES tile columns, which walks
 // them and runs the pass on the flagged ones (kernels_reblur_ta.hip has the measurement behind this shape)
-constexpr int FALLBACK_TILES = 8;
+constexpr int FALLBACK_TILES = TILE_FLAG_GROUP;
 template <bool DIFF, bool SPEC, bool SH, int MODE, bool MAT = true>
 __global__ __launch_bounds__(256, NRD_WAVES_RELAX_TA) void RelaxTemporalAccumulationKernel(RelaxCB cArg, TaPlanes P, RowRange rows) {
     const int blockY = BlockTileY(rows, true);
@@ -752,22 +753,16 @@ __global__ __launch_bounds__(256, NRD_WAVES_RELAX_TA) void RelaxTemporalAccumula
         RelaxTemporalAccumulationTile<DIFF, SPEC, SH, MODE, MAT>(cArg, P, rows, BlockTileX(rows), blockY);
         return;
     }
-    if (blockY >= P.tileFlags.h)
-        return;
-    // the FALLBACK_TILES flags of this workgroup with ONE memory latency: lane k of every wave reads flag k, the set bits are OR-ed across the wave
-    // (read one after the other, the eight dependent loads were the whole cost of this kernel: 14 us per launch with nothing to do, r03_j)
-    const int lane = threadIdx.x & 63, firstTile = (int)blockIdx.x * FALLBACK_TILES;
-    int mask = 0;
-    if (lane < FALLBACK_TILES && firstTile + lane < P.tileFlags.w)
-        mask = P.tileFlags.ptr[(uint32_t)blockY * P.tileFlags.pitch + (uint32_t)(firstTile + lane)] != 0 ? 1 << lane : 0;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        mask |= __shfl_xor(mask, m);
-    if (mask == 0)
-        return; // the window kernel has done all these tiles (uniform; the usual case)
+    // the flags of this workgroup's FALLBACK_TILES tile columns in one scalar request, OR-ed on the scalar unit (planes.h AnyTileFlagUniform): a workgroup that finds
+    // nothing -- the usual case -- issues no vector-memory instruction at all. (Round 3: eight dependent loads, 14 us per launch with nothing to do; one vector load per
+    // wave and 8 columns per workgroup, 4.5 us. This form launches a fifth of the waves and measures the same 4.5 us: what is left is the launch, profiles/HISTORY.md.)
+    const int firstTile = (int)blockIdx.x * FALLBACK_TILES;
+    if (!AnyTileFlagUniform(P.tileFlags, firstTile, min(blockY, P.tileFlags.h - 1)) || blockY >= P.tileFlags.h) // (one batch of kernel arguments, one flag request)
+        return; // the window kernel has done all these tiles (uniform)
+    const int endTile = min(FALLBACK_TILES, P.tileFlags.w - firstTile);
 #pragma nounroll
-    for (int k = 0; k < FALLBACK_TILES; k++) {
-        if (!(mask & (1 << k)))
+    for (int k = 0; k < endTile; k++) {
+        if (!TileFlagUniform(P.tileFlags, firstTile + k, blockY))
             continue;
         __syncthreads(); // the LDS tiles of the previous iteration are free
         RelaxTemporalAccumulationTile<DIFF, SPEC, SH, MODE>(cArg, P, rows, firstTile + k, blockY);
@@ -838,7 +833,8 @@ const char* LaunchTemporalAccumulation(const PassArgs& a) {
     // keeps three waves per SIMD and its SIMDs 72 % busy with VALU work, so the L1 bytes the window saves buy little. Kept for A/B runs and for larger frames.
     static const bool windowEnv = getenv("NRD_HIP_RELAX_TA_WINDOW") && atoi(getenv("NRD_HIP_RELAX_TA_WINDOW")) != 0;
     if (windowEnv) {
-        if (!a.tileFlags.ptr || (uint32_t)a.tileFlags.w * TILE_X < (uint32_t)P.viewZ.w || (uint32_t)a.tileFlags.h * TILE_Y < (uint32_t)P.viewZ.h)
+        if (!a.tileFlags.ptr || (uint32_t)a.tileFlags.w * TILE_X < (uint32_t)P.viewZ.w || (uint32_t)a.tileFlags.h * TILE_Y < (uint32_t)P.viewZ.h ||
+            a.tileFlags.pitch % TILE_FLAG_GROUP != 0 || ((uintptr_t)a.tileFlags.ptr & 255u) != 0) // (planes.h AnyTileFlagUniform: whole groups of flags are read at once)
             return "RELAX TemporalAccumulation: the executor's tile-flag scratch is missing or too small";
         P.tileFlags = a.tileFlags;
         // both kernels of the pass only look at the flags of the rect's tile columns (dynamic resolution: columns beyond keep whatever an earlier, larger rect left)
@@ -998,13 +994,14 @@ __global__ __launch_bounds__(256, NRD_WAVES_RELAX_HC) void RelaxHistoryClampingK
     const int px = BlockTileX(rows) * TILE_X + tx, py = blockY * TILE_Y + ty;
     const int rectW = c.shared.gRectSize.x, rectH = c.shared.gRectSize.y;
 
-    if (!RelaxBlockHasGeometry(P.tiles, BlockTileX(rows), blockY))
+    const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, BlockTileX(rows), blockY); // scalar, uniform per workgroup (planes.h)
+    if (!TileBytesHaveGeometry<2>(tileBytes))
         return;
 
     // The pixel's own inputs do not depend on the LDS tiles: requested in FRONT of the fill, one memory latency covers both (behind the barrier they were a second,
     // exposed one: the pass ran 34 % above the time of a build whose loads all hit the L1, profiles/r04_c_relax_ds_sh_uniform_*_kernel_stats.txt). Undecoded SH texels.
     const int qx = min(px, rectW - 1), qy = min(max(py, 0), rectH - 1);
-    const float preTile = LoadR8Unorm(P.tiles, qx >> 4, qy >> 4);
+    const bool preSky = TileByteIsSky(tileBytes, tx >> 4); // a thread that stays has (qx, qy) = (px, py): one of the two tiles under this workgroup
     const float preHistoryLength = LoadR8Unorm(P.historyLength, qx, qy);
     float4 preSpec = F4(0.0f), preDiff = F4(0.0f);
     uint2 preSpecSh = make_uint2(0u, 0u), preSpecFastSh = make_uint2(0u, 0u), preDiffSh = make_uint2(0u, 0u), preDiffFastSh = make_uint2(0u, 0u);
@@ -1039,7 +1036,7 @@ __global__ __launch_bounds__(256, NRD_WAVES_RELAX_HC) void RelaxHistoryClampingK
 
     if (px >= rectW || py >= rectH || py < rows.rowBegin || py >= rows.rowEnd)
         return;
-    if (preTile != 0.0f)
+    if (preSky)
         return;
     const int lx = tx + hc::BORDER, ly = ty + hc::BORDER;
     const float centerValid = SPEC ? s_SpecNoisy[ly * hc::BUF_STRIDE + lx].w : s_DiffNoisy[ly * hc::BUF_STRIDE + lx].w;

@@ -297,11 +297,9 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void SigmaBlurKernel(SigmaCB c, Blu
     const int rw = c.gRectSizeMinusOne.x, rh = c.gRectSizeMinusOne.y;
 
     {
-        const int tileY = (blockY * TILE_Y) >> 4, tileX0 = (blockIdx.x * TILE_X) >> 4;
-        bool anyGeometry = false;
-        for (int t = 0; t < TILE_X / 16; t++)
-            anyGeometry |= InBounds(P.tiles, tileX0 + t, tileY) && LoadTileX(P.tiles, tileX0 + t, tileY) == 0.0f;
-        if (!anyGeometry)
+        // .x of the two RG8 tiles under this workgroup, through the scalar cache (planes.h LoadTileBytesUniform): uniform, in front of every vector-memory instruction
+        const uint32_t tileBytes = LoadTileBytesUniform<TILE_X / 16, 2>(P.tiles, (int)(blockIdx.x * TILE_X) >> 4, (blockY * TILE_Y) >> 4);
+        if (!TileBytesHaveGeometry<TILE_X / 16>(tileBytes))
             return;
         const int baseX = blockIdx.x * TILE_X - BORDER, baseY = blockY * TILE_Y - BORDER;
         for (int i = threadIdx.x; i < BUF_X * BUF_Y; i += TILE_X * TILE_Y) {
@@ -510,11 +508,9 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void SigmaTemporalStabilizationKern
     const int rw = c.gRectSizeMinusOne.x, rh = c.gRectSizeMinusOne.y;
 
     {
-        const int tileY = (blockY * TILE_Y) >> 4, tileX0 = (blockIdx.x * TILE_X) >> 4;
-        bool anyGeometry = false;
-        for (int t = 0; t < TILE_X / 16; t++)
-            anyGeometry |= InBounds(P.tiles, tileX0 + t, tileY) && LoadTileX(P.tiles, tileX0 + t, tileY) == 0.0f;
-        if (!anyGeometry)
+        // .x of the two RG8 tiles under this workgroup, through the scalar cache (planes.h LoadTileBytesUniform): uniform, in front of every vector-memory instruction
+        const uint32_t tileBytes = LoadTileBytesUniform<TILE_X / 16, 2>(P.tiles, (int)(blockIdx.x * TILE_X) >> 4, (blockY * TILE_Y) >> 4);
+        if (!TileBytesHaveGeometry<TILE_X / 16>(tileBytes))
             return;
         const int baseX = blockIdx.x * TILE_X - BORDER, baseY = blockY * TILE_Y - BORDER;
         for (int i = threadIdx.x; i < BUF_X * BUF_Y; i += TILE_X * TILE_Y) {

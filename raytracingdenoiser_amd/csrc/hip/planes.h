@@ -118,6 +118,76 @@ NRD_D void StoreR16U(const Plane& p, int x, int y, uint32_t v) { *TexelPtr<uint1
 NRD_D uint32_t LoadR8U(const Plane& p, int x, int y) { return *TexelPtr<const uint8_t>(p, x, y); }
 NRD_D void StoreR8U(const Plane& p, int x, int y, uint32_t v) { *TexelPtr<uint8_t>(p, x, y) = (uint8_t)v; }
 
+// ---- tile test, uniform per workgroup -------------------------------------------------------------------------------
+// The tile plane (R8_UNORM, one byte per 16x16 pixels, != 0 = sky) is written by the classification kernel and read-only afterwards; which of its bytes a
+// workgroup needs is the same for all its lanes. On the device the aligned dword that holds them is therefore read through the scalar cache (constant address
+// space, uniform address: s_load_dword), next to the kernel arguments and off the vector memory path, and the bytes are taken apart on the scalar unit: a sky
+// workgroup leaves before it has issued a single vector-memory or LDS instruction. Tile planes are pool planes: pointer and pitch are multiples of 256 bytes
+// (executor.hip PlanPool), so the dword is aligned and inside its row. A host compiler (tests/emu) reads the bytes one by one.
+// N = 1, 2 or 4 tiles in a row starting at (tileX0, tileY), tileX0 a multiple of N; BPT = bytes per tile texel (R8: 1; SIGMA's RG8 tile map: 2, the test looks
+// at .x), N * BPT <= 4. Byte t of the result is the byte of tile tileX0 + t; a tile outside the plane reads as 0xFF -- "not geometry", which is what skipping it
+// in the OR over the workgroup's tiles meant.
+template <int N, int BPT = 1>
+NRD_D uint32_t LoadTileBytesUniform(const Plane& tiles, int tileX0, int tileY) {
+    static_assert((N == 1 || N == 2 || N == 4) && (BPT == 1 || BPT == 2) && N * BPT <= 4, "the tiles under a workgroup lie in one aligned dword");
+    // (clamped, not branched: the request goes out as soon as the kernel arguments are there)
+    const int cx = min(tileX0, tiles.w - 1), cy = min(tileY, tiles.h - 1);
+    uint32_t bytes = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t offset = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__umul24((uint32_t)cy, tiles.pitch) + (((uint32_t)cx * BPT) & ~3u)));
+    typedef const uint32_t __attribute__((address_space(4))) ConstDword;
+    const uint32_t raw = *(ConstDword*)(uintptr_t)(tiles.ptr + offset) >> ((((uint32_t)cx * BPT) & 3u) * 8u);
+    for (int t = 0; t < N; t++)
+        bytes |= ((raw >> (8 * BPT * t)) & 0xFFu) << (8 * t);
+#else
+    for (int t = 0; t < N; t++)
+        bytes |= (cx + t < tiles.w ? (uint32_t)tiles.ptr[(uint32_t)cy * tiles.pitch + (uint32_t)(cx + t) * BPT] : 0xFFu) << (8 * t);
+#endif
+    uint32_t outside = (tileX0 >= tiles.w || tileY >= tiles.h) ? 0xFFFFFFFFu : 0u;
+    for (int t = 1; t < N; t++)
+        outside |= tileX0 + t >= tiles.w ? 0xFFu << (8 * t) : 0u;
+    return (bytes | outside) & (N == 4 ? 0xFFFFFFFFu : (1u << (8 * (N & 3))) - 1u);
+}
+// any of the N tiles has geometry (byte == 0)
+template <int N>
+NRD_D bool TileBytesHaveGeometry(uint32_t bytes) {
+    bool any = false;
+    for (int t = 0; t < N; t++)
+        any |= ((bytes >> (8 * t)) & 0xFFu) == 0u;
+    return any;
+}
+// the sky test of one lane whose pixel lies in tile t of the workgroup's N
+NRD_D bool TileByteIsSky(uint32_t bytes, int t) { return ((bytes >> (8 * t)) & 0xFFu) != 0u; }
+// the workgroup-level test of a 32x8 block (two 16x16 tiles side by side): block column / row -> tile bytes
+NRD_D uint32_t LoadBlockTileBytes(const Plane& tiles, int blockX, int blockY) { return LoadTileBytesUniform<2>(tiles, blockX * 2, blockY >> 1); }
+
+// ---- flag bytes of a split pass (passes.h PassArgs::tileFlags), uniform per workgroup -------------------------------------
+// The fallback kernel behind a window kernel normally finds nothing to do, so all it should cost is its launch: a workgroup reads the flags of
+// TILE_FLAG_GROUP tile columns of one tile row with ONE scalar request (s_load_dwordx16: the flag plane's pitch is a multiple of TILE_FLAG_GROUP bytes and its
+// base is allocation-aligned -- executor.hip, checked by the launchers) and ORs them on the scalar unit. The flags were written by the previous kernel and are
+// read-only in this one.
+constexpr int TILE_FLAG_GROUP = 64;
+NRD_D bool AnyTileFlagUniform(const Plane& flags, int firstTile, int row) { // any flag of [firstTile, firstTile + TILE_FLAG_GROUP) x {row} inside the plane's w columns set
+    const int count = min(flags.w - firstTile, TILE_FLAG_GROUP);
+    uint32_t any = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef uint32_t Dwords __attribute__((ext_vector_type(TILE_FLAG_GROUP / 4)));
+    typedef const Dwords __attribute__((address_space(4))) ConstDwords;
+    const uint32_t offset = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__umul24((uint32_t)row, flags.pitch) + (uint32_t)firstTile));
+    const Dwords v = *(ConstDwords*)(uintptr_t)(flags.ptr + offset);
+#pragma unroll
+    for (int i = 0; i < TILE_FLAG_GROUP / 4; i++) {
+        const int n = count - 4 * i; // columns of this dword inside the plane
+        any |= n >= 4 ? v[i] : (n > 0 ? v[i] & ((1u << (8 * n)) - 1u) : 0u);
+    }
+#else
+    for (int k = 0; k < count; k++)
+        any |= flags.ptr[(uint32_t)row * flags.pitch + (uint32_t)(firstTile + k)];
+#endif
+    return any != 0u;
+}
+NRD_D bool TileFlagUniform(const Plane& flags, int tile, int row) { return LoadTileBytesUniform<1>(flags, tile, row) != 0u; } // (tile, row) inside the plane
+
 // ---- R16_SFLOAT ---------------------------------------------------------------------------------------------------
 NRD_D float LoadR16F(const Plane& p, int x, int y) { return HalfBitsToFloat(*TexelPtr<const uint16_t>(p, x, y)); }
 NRD_D void StoreR16F(const Plane& p, int x, int y, float v) { *TexelPtr<uint16_t>(p, x, y) = FloatToHalfBits(v); }

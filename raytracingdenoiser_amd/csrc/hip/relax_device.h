@@ -199,13 +199,8 @@ NRD_D float4 LoadDenanifiedRGBA16F(float w, const Plane& p, int x, int y) {
 }
 
 // true when any of the 16x16 tiles overlapped by this workgroup's 32x8 block has geometry
-NRD_D bool RelaxBlockHasGeometry(const Plane& tiles, int blockX, int blockY) {
-    const int tileY = (blockY * RELAX_TILE_Y) >> 4, tileX0 = (blockX * RELAX_TILE_X) >> 4;
-    bool any = false;
-    for (int t = 0; t < RELAX_TILE_X / 16; t++)
-        if (tileX0 + t < tiles.w && tileY < tiles.h)
-            any |= LoadR8Unorm(tiles, tileX0 + t, tileY) == 0.0f;
-    return any;
-}
+// (a scalar test, uniform per workgroup: planes.h LoadTileBytesUniform)
+static_assert(RELAX_TILE_X == 32 && RELAX_TILE_Y == 8, "planes.h LoadBlockTileBytes: a workgroup covers two 16x16 tiles of one tile row");
+NRD_D bool RelaxBlockHasGeometry(const Plane& tiles, int blockX, int blockY) { return TileBytesHaveGeometry<2>(LoadBlockTileBytes(tiles, blockX, blockY)); }
 
 } // namespace nrdhip
