@@ -18,7 +18,8 @@
 // values the linked libNRD_hip.so was built with before including this file, as the reference asks for NRDEncoding.hlsli (NRD.hlsli:290-309); undefined, they take the
 // library's defaults R10G10B10A2_UNORM (oct-packed normal, 2 bits of material id) and LINEAR. All functions are __host__ __device__ (the same code serves a CPU reference of the
 // application) and use only fp32 arithmetic; "sanitize" keeps the reference default (true).
-// Include from a .hip / hipcc translation unit; needs nothing from libNRD_hip.so.
+// Include from a .hip / hipcc translation unit; needs nothing from libNRD_hip.so. Or let the library do it: NRDHip.h (nrdHipPackInputs / nrdHipResolveOutputs run these
+// functions over whole fp32 planes, for hosts that write no kernels).
 #pragma once
 
 #include <hip/hip_runtime.h>

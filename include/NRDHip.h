@@ -187,6 +187,102 @@ uint32_t nrdHipMeasureCopyBandwidth(uint64_t bytes, uint32_t repetitions, void* 
 // Last error text of this executor (never NULL).
 const char* nrdHipGetLastError(const NrdHipExecutor* executor);
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// Front end / back end on the device: what an application does with the reference's NRD.hlsli in its own shaders -- pack its fp32 G-buffer and noisy
+// signals into the planes nrdHipBindResource accepts, and turn the denoised OUT_* planes back into linear radiance -- as two fused kernels of the
+// library, for hosts that hold device buffers but write no HIP kernels (a tensor library). The arithmetic is include/NRD.hip.h, unfused IEEE with
+// correctly rounded division and square root; the stores are the codecs of the passes (fp16 round-to-nearest-even, UNORM floor(x * max + 0.5), SNORM
+// round half away from zero). Executor-free: no instance, no pool. One launch each, asynchronous on the given stream, no allocation and no
+// synchronisation (usable inside a HIP graph capture). Everything is validated before the first HIP call and nothing is enqueued on an error:
+//   a required plane (or one the chosen mode needs: direction, camera, albedo / Rf0, the matching output) with data == NULL     -> INVALID_ARGUMENT
+//   a format other than the one listed for the plane                                                                           -> UNSUPPORTED
+//   planes of different sizes, a row pitch below the row or not a multiple of the texel size, a misaligned pointer             -> INVALID_ARGUMENT
+//   a row pitch >= 16 MiB or pitch x height >= 4 GiB (the limits of nrdHipBindResource), an orthographic camera                -> UNSUPPORTED
+// nrdHipGetLastFrontEndError says which (per calling thread, never NULL). A plane with data == NULL is absent and costs nothing.
+//
+// Signal modes (which packer / unpacker of NRD.hip.h a signal goes through)
+#define NRD_HIP_SIGNAL_NONE 0u
+#define NRD_HIP_SIGNAL_REBLUR_RADIANCE 1u              // RADIANCE_HITDIST RGBA16_SFLOAT: YCoCg + normalised hit distance
+#define NRD_HIP_SIGNAL_REBLUR_SH 2u                    // SH0 + SH1 RGBA16_SFLOAT
+#define NRD_HIP_SIGNAL_REBLUR_OCCLUSION 3u             // HITDIST R16_UNORM: the normalised hit distance alone
+#define NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION 4u // DIFF_DIRECTION_HITDIST RGBA16_SNORM
+#define NRD_HIP_SIGNAL_RELAX_RADIANCE 5u               // RADIANCE_HITDIST RGBA16_SFLOAT: radiance + hit distance in world units
+#define NRD_HIP_SIGNAL_RELAX_SH 6u                     // SH0 + SH1 RGBA16_SFLOAT
+// How an SH pair (or a directional-occlusion texel) becomes a colour in the back end
+#define NRD_HIP_RESOLVE_SG_EXTRACT_COLOR 0u // NRD_SG_ExtractColor: the denoised colour, no normal involved
+#define NRD_HIP_RESOLVE_SH 1u               // NRD_SH_ResolveDiffuse / NRD_SH_ResolveSpecular
+#define NRD_HIP_RESOLVE_SG 2u               // NRD_SG_ResolveDiffuse / NRD_SG_ResolveSpecular
+
+typedef struct NrdHipFrontEndSignal {
+    uint32_t mode;                   // NRD_HIP_SIGNAL_*
+    NrdHipPlaneDesc radianceHitDist; // in,  RGBA32_SFLOAT: radiance.rgb, hit distance in world units (the occlusion modes read .w only)
+    NrdHipPlaneDesc direction;       // in,  RGBA32_SFLOAT: direction.xyz of the ray (SH and directional-occlusion modes)
+    NrdHipPlaneDesc out0;            // out, the format of the mode: IN_*_RADIANCE_HITDIST / IN_*_SH0 / IN_*_HITDIST / IN_DIFF_DIRECTION_HITDIST
+    NrdHipPlaneDesc out1;            // out, IN_*_SH1 RGBA16_SFLOAT (SH modes)
+} NrdHipFrontEndSignal;
+
+// REBLUR modes normalise the hit distance with REBLUR_FrontEnd_GetNormHitDist( hitDist, viewZ * viewZScale, hitDistParams, roughness ), roughness = 1 for
+// the diffuse signal and the pixel's linear roughness for the specular one; every packer runs with sanitize = true.
+// Demodulation: with albedo AND rf0 given, the radiance of each signal is divided by its NRD_MaterialFactors factor (of the raw normal and roughness and
+// the view vector below) before it is packed; commonSettings is needed for that alone.
+typedef struct NrdHipFrontEndDesc {
+    const void* commonSettings;         // const nrd::CommonSettings* of the frame (camera) or NULL
+    float hitDistParams[4];             // ReblurSettings::hitDistanceParameters
+    float viewZScale;                   // IN_VIEWZ = viewZ * viewZScale; 0 is read as 1
+    float tanOfLightAngularRadius;      // SIGMA_FrontEnd_PackPenumbra (directional light)
+    NrdHipPlaneDesc normalRoughness;    // in,  RGBA32_SFLOAT, required: world-space normal.xyz, linear roughness
+    NrdHipPlaneDesc viewZ;              // in,  R32_SFLOAT, required
+    NrdHipPlaneDesc materialID;         // in,  R32_SFLOAT: 0..3, kept by normal encoding 2 only
+    NrdHipPlaneDesc motion;             // in,  RGBA32_SFLOAT or RG32_SFLOAT (.zw = 0), clamped to +-65504
+    NrdHipPlaneDesc albedo, rf0;        // in,  RGBA32_SFLOAT (.rgb): demodulation
+    NrdHipPlaneDesc distanceToOccluder; // in,  R32_SFLOAT: 0 where NoL <= 0, the hit distance of the shadow ray, >= 65504 on a miss (NRD.hip.h SIGMA_FrontEnd_PackPenumbra)
+    NrdHipPlaneDesc translucency;       // in,  RGBA32_SFLOAT (.rgb)
+    NrdHipFrontEndSignal diffuse, specular;
+    NrdHipPlaneDesc outNormalRoughness; // out, IN_NORMAL_ROUGHNESS in the format of the library's normal encoding
+    NrdHipPlaneDesc outViewZ;           // out, IN_VIEWZ R32_SFLOAT
+    NrdHipPlaneDesc outMv;              // out, IN_MV RGBA16_SFLOAT (needs motion)
+    NrdHipPlaneDesc outPenumbra;        // out, IN_PENUMBRA R16_SFLOAT (needs distanceToOccluder)
+    NrdHipPlaneDesc outTranslucency;    // out, IN_TRANSLUCENCY RGBA8_UNORM (needs distanceToOccluder and translucency)
+} NrdHipFrontEndDesc;
+
+typedef struct NrdHipBackEndSignal {
+    uint32_t mode;       // NRD_HIP_SIGNAL_*
+    uint32_t resolve;    // NRD_HIP_RESOLVE_* (SH and directional-occlusion modes)
+    NrdHipPlaneDesc in0; // in,  OUT_*_RADIANCE_HITDIST / OUT_*_SH0 (RGBA16_SFLOAT or RGBA32_SFLOAT), OUT_*_HITDIST R16_UNORM, OUT_DIFF_DIRECTION_HITDIST RGBA16_SNORM
+    NrdHipPlaneDesc in1; // in,  OUT_*_SH1 (RGBA16_SFLOAT or RGBA32_SFLOAT; SH modes)
+    NrdHipPlaneDesc out; // out, RGBA32_SFLOAT: linear rgb, hit distance (R32_SFLOAT for the occlusion mode)
+} NrdHipBackEndSignal;
+
+// REBLUR radiance goes through REBLUR_BackEnd_UnpackRadianceAndNormHitDist, RELAX radiance and REBLUR occlusion are widened as they are, an SH pair
+// (REBLUR_BackEnd_UnpackSh / RELAX_BackEnd_UnpackSh) or a directional-occlusion texel (REBLUR_BackEnd_UnpackDirectionalOcclusion) is resolved as `resolve`
+// says into .rgb with its hit distance in .w. denormalizeHitDist != 0 turns the hit distance of the REBLUR modes back into world units (REBLUR_GetHitDist;
+// roughness 1 / the pixel's). N and the roughness are those of the bound IN_NORMAL_ROUGHNESS plane (NRD_LoadNormalRoughnessTexel +
+// NRD_FrontEnd_UnpackNormalAndRoughness). remodulate != 0 multiplies each resolved colour by its NRD_MaterialFactors factor (needs albedo, rf0 and the camera).
+// View vector, per pixel (x, y) of a w x h frame, in correctly rounded fp32 operations in exactly this order, nothing fused:
+//   uv = ( ( x + 0.5 ) / w, ( y + 0.5 ) / h )      Xv = ( ( uv.x * frustum.z + frustum.x ) * viewZ, ( uv.y * frustum.w + frustum.y ) * viewZ, viewZ )
+//   Xw.i = ( R[ i ][ 0 ] * Xv.x + R[ i ][ 1 ] * Xv.y ) + R[ i ][ 2 ] * Xv.z      V = -( Xw * ( 1 / sqrt( ( Xw.x * Xw.x + Xw.y * Xw.y ) + Xw.z * Xw.z ) ) )
+// with frustum and R = the rotation of view-to-world as the denoisers' constants hold them (gFrustum, gViewToWorld) for the given nrd::CommonSettings, whose
+// rectSize must be the size of the planes, and viewZ the value of the IN_VIEWZ plane. Perspective projections only.
+typedef struct NrdHipBackEndDesc {
+    const void* commonSettings;      // const nrd::CommonSettings* of the frame or NULL (needed wherever V is: specular SH / SG resolves, remodulation, factors, outViewVector)
+    float hitDistParams[4];          // ReblurSettings::hitDistanceParameters
+    uint32_t denormalizeHitDist;
+    uint32_t remodulate;
+    NrdHipPlaneDesc normalRoughness; // in,  IN_NORMAL_ROUGHNESS as bound (needed by SH / SG resolves, the specular hit distance, remodulation)
+    NrdHipPlaneDesc viewZ;           // in,  IN_VIEWZ R32_SFLOAT (needed by V and by denormalizeHitDist)
+    NrdHipPlaneDesc albedo, rf0;     // in,  RGBA32_SFLOAT (.rgb)
+    NrdHipBackEndSignal diffuse, specular;
+    NrdHipPlaneDesc shadow;          // in,  OUT_SHADOW_TRANSLUCENCY R8_UNORM or RGBA8_UNORM
+    NrdHipPlaneDesc outShadow;       // out, R32_SFLOAT or RGBA32_SFLOAT: SIGMA_BackEnd_UnpackShadow
+    NrdHipPlaneDesc outComposed;     // out, RGBA32_SFLOAT: diffuse.rgb + specular.rgb as written to their out planes, .w = 0
+    NrdHipPlaneDesc outViewVector;   // out, RGBA32_SFLOAT: V, .w = 0
+    NrdHipPlaneDesc outDiffFactor, outSpecFactor; // out, RGBA32_SFLOAT: the NRD_MaterialFactors factors, .w = 0
+} NrdHipBackEndDesc;
+
+uint32_t nrdHipPackInputs(const NrdHipFrontEndDesc* desc, void* hipStream);
+uint32_t nrdHipResolveOutputs(const NrdHipBackEndDesc* desc, void* hipStream);
+const char* nrdHipGetLastFrontEndError(void);
+
 #ifdef __cplusplus
 }
 #endif

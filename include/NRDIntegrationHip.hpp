@@ -64,6 +64,7 @@ public:
             return false;
         }
         m_Name = desc.name;
+        m_Stream = desc.hipStream;
         m_FrameIndex = 0;
         nrdHipGetPoolMemoryUsage(m_Executor, &m_PermanentPoolSize, &m_TransientPoolSize);
         return true;
@@ -97,6 +98,12 @@ public:
         return nrdHipDenoise(m_Executor, denoisers, denoisersNum) == (uint32_t)Result::SUCCESS;
     }
 
+    // Front end / back end on the device (NRDHip.h nrdHipPackInputs / nrdHipResolveOutputs) on this integration's stream: pack the application's fp32 buffers
+    // into the planes "Denoise" consumes, resolve its outputs into linear radiance. Asynchronous; false + GetLastFrontEndError() on an invalid descriptor.
+    inline bool PackInputs(const NrdHipFrontEndDesc& desc) { return nrdHipPackInputs(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
+    inline bool ResolveOutputs(const NrdHipBackEndDesc& desc) { return nrdHipResolveOutputs(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
+    inline const char* GetLastFrontEndError() const { return nrdHipGetLastFrontEndError(); }
+
     // Assumes that no work of this integration is in flight on the stream
     inline void Destroy() {
         if (m_Executor)
@@ -122,6 +129,7 @@ private:
     Instance* m_Instance = nullptr;
     NrdHipExecutor* m_Executor = nullptr;
     const char* m_Name = "";
+    void* m_Stream = nullptr;
     uint64_t m_PermanentPoolSize = 0, m_TransientPoolSize = 0;
     uint32_t m_FrameIndex = 0;
 };

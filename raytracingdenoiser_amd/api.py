@@ -260,6 +260,47 @@ class HipPlaneDesc(C.Structure):
     _fields_ = [("data", C.c_void_p), ("rowPitchBytes", C.c_uint32), ("format", C.c_uint32), ("width", C.c_uint16), ("height", C.c_uint16)]
 
 
+class SignalMode(enum.IntEnum):  # include/NRDHip.h NRD_HIP_SIGNAL_*
+    NONE = 0
+    REBLUR_RADIANCE = 1
+    REBLUR_SH = 2
+    REBLUR_OCCLUSION = 3
+    REBLUR_DIRECTIONAL_OCCLUSION = 4
+    RELAX_RADIANCE = 5
+    RELAX_SH = 6
+
+
+class ResolveMode(enum.IntEnum):  # include/NRDHip.h NRD_HIP_RESOLVE_*
+    SG_EXTRACT_COLOR = 0
+    SH = 1
+    SG = 2
+
+
+class HipFrontEndSignal(C.Structure):  # include/NRDHip.h NrdHipFrontEndSignal
+    _fields_ = [("mode", C.c_uint32), ("radianceHitDist", HipPlaneDesc), ("direction", HipPlaneDesc), ("out0", HipPlaneDesc), ("out1", HipPlaneDesc)]
+
+
+class HipFrontEndDesc(C.Structure):  # include/NRDHip.h NrdHipFrontEndDesc
+    _fields_ = [("commonSettings", C.c_void_p), ("hitDistParams", C.c_float * 4), ("viewZScale", C.c_float), ("tanOfLightAngularRadius", C.c_float),
+                ("normalRoughness", HipPlaneDesc), ("viewZ", HipPlaneDesc), ("materialID", HipPlaneDesc), ("motion", HipPlaneDesc), ("albedo", HipPlaneDesc), ("rf0", HipPlaneDesc),
+                ("distanceToOccluder", HipPlaneDesc), ("translucency", HipPlaneDesc), ("diffuse", HipFrontEndSignal), ("specular", HipFrontEndSignal),
+                ("outNormalRoughness", HipPlaneDesc), ("outViewZ", HipPlaneDesc), ("outMv", HipPlaneDesc), ("outPenumbra", HipPlaneDesc), ("outTranslucency", HipPlaneDesc)]
+
+
+class HipBackEndSignal(C.Structure):  # include/NRDHip.h NrdHipBackEndSignal
+    _fields_ = [("mode", C.c_uint32), ("resolve", C.c_uint32), ("in0", HipPlaneDesc), ("in1", HipPlaneDesc), ("out", HipPlaneDesc)]
+
+
+class HipBackEndDesc(C.Structure):  # include/NRDHip.h NrdHipBackEndDesc
+    _fields_ = [("commonSettings", C.c_void_p), ("hitDistParams", C.c_float * 4), ("denormalizeHitDist", C.c_uint32), ("remodulate", C.c_uint32),
+                ("normalRoughness", HipPlaneDesc), ("viewZ", HipPlaneDesc), ("albedo", HipPlaneDesc), ("rf0", HipPlaneDesc), ("diffuse", HipBackEndSignal), ("specular", HipBackEndSignal),
+                ("shadow", HipPlaneDesc), ("outShadow", HipPlaneDesc), ("outComposed", HipPlaneDesc), ("outViewVector", HipPlaneDesc), ("outDiffFactor", HipPlaneDesc),
+                ("outSpecFactor", HipPlaneDesc)]
+
+
+assert C.sizeof(HipPlaneDesc) == 24 and C.sizeof(HipFrontEndSignal) == 104 and C.sizeof(HipFrontEndDesc) == 552 and C.sizeof(HipBackEndSignal) == 80 and C.sizeof(HipBackEndDesc) == 432
+
+
 # ----------------------------------------------------------------------------------------------- library
 # every symbol the headers declare; tests assert each one resolves
 NRD_SYMBOLS = ["CreateInstance", "DestroyInstance", "GetLibraryDesc", "GetInstanceDesc", "SetCommonSettings", "SetDenoiserSettings",
@@ -280,7 +321,7 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipDenoise", "nrdHipGetPoolMemoryUsage", "nrdHipGetLastError", "nrdHipEvalNumerics", "nrdHipGetArenaSize",
                    "nrdHipCreateExecutorWithArena", "nrdHipSetProfiling", "nrdHipCollectPassTimings", "nrdHipSetOwnedRows", "nrdHipGetDispatchReach",
                    "nrdHipExecuteDispatchRange", "nrdHipPlanHaloExchange", "nrdHipSetGraphMode", "nrdHipGetGraphStats", "nrdHipGetTileFallbackStats", "nrdHipGetNumericsMode", "nrdHipMeasureCopyBandwidth",
-                   "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord"]
+                   "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError"]
 
 _libs = {}
 
@@ -347,6 +388,9 @@ def load_library(path=None):
         lib.nrdHipMeasureMotionRowsAsync.argtypes, lib.nrdHipMeasureMotionRowsAsync.restype = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p], C.c_uint32
     lib.nrdHipGetNumericsMode.argtypes, lib.nrdHipGetNumericsMode.restype = [], C.c_uint32
     lib.nrdHipMeasureCopyBandwidth.argtypes, lib.nrdHipMeasureCopyBandwidth.restype = [C.c_uint64, C.c_uint32, C.c_void_p, P(C.c_double)], C.c_uint32
+    lib.nrdHipPackInputs.argtypes, lib.nrdHipPackInputs.restype = [P(HipFrontEndDesc), C.c_void_p], C.c_uint32
+    lib.nrdHipResolveOutputs.argtypes, lib.nrdHipResolveOutputs.restype = [P(HipBackEndDesc), C.c_void_p], C.c_uint32
+    lib.nrdHipGetLastFrontEndError.argtypes, lib.nrdHipGetLastFrontEndError.restype = [], C.c_char_p
     _libs[path] = lib
     return lib
 

@@ -62,6 +62,28 @@ class HipExecutor:
         self._check(self.lib.nrdHipBindResource(self.handle, int(resource_type), C.byref(desc)), "nrdHipBindResource(%s)" % api.ResourceType(resource_type).name)
         self._bound[int(resource_type)] = tensor
 
+    def bind_packed(self, packed):
+        """binds what frontend.pack_inputs returned: {ResourceType: (tensor, Format)}"""
+        for resource_type, (tensor, fmt) in packed.items():
+            self.bind(resource_type, tensor, fmt)
+
+    def resolve(self, diffuse_mode=None, specular_mode=None, resolve=0, shadow=False, **kw):
+        """frontend.resolve_outputs on the planes bound to this executor: the OUT_* planes of the given signal modes (frontend.SignalMode; `resolve` = frontend.ResolveMode for the
+        SH modes), OUT_SHADOW_TRANSLUCENCY with shadow=True, IN_NORMAL_ROUGHNESS / IN_VIEWZ where bound, the camera of the last SetCommonSettings, on the executor's stream.
+        Further keywords (albedo, rf0, remodulate, denormalize_hit_dist, want, out, ...) are passed on. Returns fp32 tensors by name."""
+        from . import frontend
+
+        args = dict(normal_roughness=self._bound.get(int(api.ResourceType.IN_NORMAL_ROUGHNESS)), viewz=self._bound.get(int(api.ResourceType.IN_VIEWZ)),
+                    common_settings=getattr(self.instance, "last_common_settings", None), stream=self.stream, lib=self.lib)
+        for which, mode in (("diffuse", diffuse_mode), ("specular", specular_mode)):
+            if mode:
+                slot0, slot1 = frontend.signal_slots(which, mode, "OUT")
+                args[which] = dict(mode=mode, resolve=resolve, in0=self._bound[int(slot0)], in1=self._bound[int(slot1)] if slot1 is not None else None)
+        if shadow:
+            args["shadow"] = self._bound[int(api.ResourceType.OUT_SHADOW_TRANSLUCENCY)]
+        args.update(kw)
+        return frontend.resolve_outputs(**args)
+
     def denoise(self, identifiers=None):
         ids = identifiers if identifiers is not None else self.instance.identifiers
         arr = (C.c_uint32 * len(ids))(*ids)

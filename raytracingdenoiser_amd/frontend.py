@@ -1,0 +1,284 @@
+"""Front end / back end on the device: plumbing over nrdHipPackInputs / nrdHipResolveOutputs (include/NRDHip.h).
+
+pack_inputs() turns an application's fp32 buffers into the packed planes HipExecutor.bind accepts, resolve_outputs() turns the denoised OUT_* planes into
+linear fp32 radiance -- one kernel launch each, asynchronous on the current stream, usable inside torch.cuda.graph. This module allocates and calls the
+C-ABI; it computes nothing (no arithmetic on tensors, no fallback). Planes are CUDA tensors; numpy arrays are accepted as well, for a library whose "device
+memory" is host memory (the CPU emulation of the device sources that the test-suite builds).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import api
+
+F, R, SignalMode, ResolveMode = api.Format, api.ResourceType, api.SignalMode, api.ResolveMode
+HIT_DIST_PARAMS = (3.0, 0.1, 20.0, -25.0)  # ReblurSettings::hitDistanceParameters defaults
+
+_SH = (SignalMode.REBLUR_SH, SignalMode.RELAX_SH)
+_NR_DTYPE = {"RGBA8_UNORM": ("int32", 1), "RGBA8_SNORM": ("int32", 1), "R10_G10_B10_A2_UNORM": ("int32", 1), "RGBA16_UNORM": ("int16", 4), "RGBA16_SNORM": ("int16", 4)}
+# (first / second packed plane of a signal, per mode): dtype, channels, Format
+_SIGNAL_OUT = {SignalMode.REBLUR_RADIANCE: ("float16", 4, F.RGBA16_SFLOAT), SignalMode.REBLUR_SH: ("float16", 4, F.RGBA16_SFLOAT), SignalMode.REBLUR_OCCLUSION: ("int16", 1, F.R16_UNORM),
+               SignalMode.REBLUR_DIRECTIONAL_OCCLUSION: ("int16", 4, F.RGBA16_SNORM), SignalMode.RELAX_RADIANCE: ("float16", 4, F.RGBA16_SFLOAT), SignalMode.RELAX_SH: ("float16", 4, F.RGBA16_SFLOAT)}
+_SLOTS = {  # ResourceType of (out0 / in0, out1 / in1) per signal and mode family; "IN" / "OUT" is prepended
+    ("diffuse", "radiance"): ("DIFF_RADIANCE_HITDIST", None), ("specular", "radiance"): ("SPEC_RADIANCE_HITDIST", None), ("diffuse", "sh"): ("DIFF_SH0", "DIFF_SH1"),
+    ("specular", "sh"): ("SPEC_SH0", "SPEC_SH1"), ("diffuse", "occlusion"): ("DIFF_HITDIST", None), ("specular", "occlusion"): ("SPEC_HITDIST", None),
+    ("diffuse", "directional"): ("DIFF_DIRECTION_HITDIST", None)}
+
+
+def _family(mode):
+    mode = SignalMode(mode)
+    return "sh" if mode in _SH else "occlusion" if mode == SignalMode.REBLUR_OCCLUSION else "directional" if mode == SignalMode.REBLUR_DIRECTIONAL_OCCLUSION else "radiance"
+
+
+def signal_slots(which, mode, prefix):
+    """(ResourceType of the first plane, of the second or None) of signal `which` ("diffuse" / "specular") in `mode`, for prefix = "IN" or "OUT"."""
+    a, b = _SLOTS[(which, _family(mode))]
+    return R[prefix + "_" + a], (R[prefix + "_" + b] if b else None)
+
+
+# ---- array plumbing: torch tensors (CUDA) or numpy arrays ---------------------------------------------------------------------------------------------
+def _is_numpy(t):
+    return isinstance(t, np.ndarray)
+
+
+def _ptr_pitch(t):
+    if _is_numpy(t):
+        assert t.strides[-1] == t.itemsize and (t.ndim == 2 or t.strides[1] == t.shape[2] * t.itemsize), "rows must be dense"
+        return t.ctypes.data, t.strides[0]
+    assert t[0].is_contiguous(), "rows must be dense"
+    return t.data_ptr(), t.stride(0) * t.element_size()
+
+
+def _dtype_name(t):
+    return str(t.dtype).replace("torch.", "")
+
+
+def _empty(like, shape, dtype):
+    if _is_numpy(like):
+        return np.empty(shape, dtype=dtype)
+    import torch
+
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=like.device)
+
+
+def _plane(t, fmt):
+    ptr, pitch = _ptr_pitch(t)
+    return api.HipPlaneDesc(ptr, pitch, int(fmt), t.shape[1], t.shape[0])
+
+
+def _fp32_plane(t, channels, what):
+    """HipPlaneDesc of an fp32 [H, W, channels] ([H, W] for one channel) array"""
+    assert _dtype_name(t) == "float32", "%s must be float32" % what
+    assert (t.ndim == 2 and channels == 1) or (t.ndim == 3 and t.shape[2] == channels), "%s: expected %d channel(s) per pixel, got shape %s" % (what, channels, tuple(t.shape))
+    return _plane(t, {1: F.R32_SFLOAT, 2: F.RG32_SFLOAT, 4: F.RGBA32_SFLOAT}[channels])
+
+
+def rgba(xyz, w=None):
+    """[H, W, 3] (+ [H, W]) -> a new [H, W, 4] array: copies only (the planes of the C-ABI are RGBA32_SFLOAT)"""
+    out = _empty(xyz, tuple(xyz.shape[:2]) + (4,), "float32")
+    out[..., :3] = xyz
+    if w is None:
+        out[..., 3] = 0.0
+    else:
+        out[..., 3] = w
+    return out
+
+
+def _rgba_arg(t, what):
+    if isinstance(t, (tuple, list)):
+        t = rgba(*t)
+    elif t.ndim == 3 and t.shape[2] == 3:
+        t = rgba(t)
+    return t, _fp32_plane(t, 4, what)
+
+
+def _stream(like, stream):
+    if stream is not None:
+        return C.c_void_p(getattr(stream, "cuda_stream", stream))
+    if _is_numpy(like):
+        return C.c_void_p(0)
+    import torch
+
+    return C.c_void_p(torch.cuda.current_stream(like.device).cuda_stream)
+
+
+class _stream_scope:
+    """torch tensors: makes `stream` (a torch.cuda.Stream) the current one for the body, so that what the body allocates -- the widened [H, W, 4] copies of three-channel inputs,
+    which die when the call returns while the launch is still in flight -- is allocated, filled and released in the order of the stream the kernel runs on (the caching
+    allocator is stream-ordered). A raw stream handle (an int) cannot be made current: such a caller passes four-channel planes, or keeps to the current stream."""
+
+    def __init__(self, like, stream):
+        self.ctx = None
+        if stream is not None and not _is_numpy(like) and hasattr(stream, "cuda_stream"):
+            import torch
+
+            self.ctx = torch.cuda.stream(stream)
+
+    def __enter__(self):
+        if self.ctx is not None:
+            self.ctx.__enter__()
+
+    def __exit__(self, *exc):
+        if self.ctx is not None:
+            self.ctx.__exit__(*exc)
+
+
+def _check(lib, code, what):
+    r = api.Result(code)
+    if r != api.Result.SUCCESS:
+        raise RuntimeError("%s failed: %s (%s)" % (what, r.name, lib.nrdHipGetLastFrontEndError().decode()))
+
+
+def _settings_ptr(cs):
+    return C.cast(C.byref(cs), C.c_void_p) if cs is not None else None
+
+
+def _reuse(out, key, like, shape, dtype):
+    if out is not None and key in out:
+        t = out[key][0] if isinstance(out[key], tuple) else out[key]
+        assert tuple(t.shape) == tuple(shape) and _dtype_name(t) == dtype, "out[%s] has the wrong shape or dtype" % (key,)
+        return t
+    return _empty(like, shape, dtype)
+
+
+# ---- front end -------------------------------------------------------------------------------------------------------------------------------------------
+def pack_inputs(normal_roughness, viewz, *args, **kw):
+    """see describe_pack; launches on `stream` (a torch.cuda.Stream, or a raw handle with four-channel inputs only; default: the current stream) and returns the packed planes"""
+    with _stream_scope(viewz, kw.get("stream")):
+        res, d, keep = describe_pack(normal_roughness, viewz, *args, **kw)
+        lib = kw.get("lib") or api.load_library()
+        _check(lib, lib.nrdHipPackInputs(C.byref(d), _stream(viewz, kw.get("stream"))), "nrdHipPackInputs")
+    return res
+
+
+def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffuse=None, specular=None, albedo=None, rf0=None, distance_to_occluder=None, translucency=None,
+                  common_settings=None, hit_dist_params=HIT_DIST_PARAMS, viewz_scale=1.0, tan_of_light_angular_radius=0.0, out=None, stream=None, lib=None):
+    """The descriptor of one nrdHipPackInputs launch, without launching: (packed planes, api.HipFrontEndDesc, arrays the descriptor points into besides its arguments) -- for a
+    caller that launches the same frame layout repeatedly through the C-ABI itself. fp32 inputs: normal_roughness [H, W, 4] (or a (normal [H, W, 3], roughness [H, W]) pair), viewz [H, W], material_id [H, W],
+    motion [H, W, 4] or [H, W, 2], albedo / rf0 / translucency [H, W, 4] or [H, W, 3], distance_to_occluder [H, W]; diffuse / specular: dict(mode=SignalMode,
+    radiance_hitdist=[H, W, 4] or (radiance [H, W, 3], hit_dist [H, W]), direction=[H, W, 4] or [H, W, 3] for the SH / directional modes). albedo + rf0 +
+    common_settings switch demodulation on. Returns {ResourceType: (packed array, Format)}, ready for HipExecutor.bind_packed; `out` = a dict returned earlier, whose
+    arrays are written again instead of allocating."""
+    d = api.HipFrontEndDesc()
+    keep = []  # widened copies must outlive the launch call
+    nr, d.normalRoughness = _rgba_arg(normal_roughness, "normal_roughness")
+    keep.append(nr)
+    h, w = viewz.shape
+    d.viewZ = _fp32_plane(viewz, 1, "viewz")
+    d.commonSettings = _settings_ptr(common_settings)
+    d.hitDistParams[:] = hit_dist_params
+    d.viewZScale, d.tanOfLightAngularRadius = viewz_scale, tan_of_light_angular_radius
+    res = {}
+
+    def output(slot, shape, dtype, fmt):
+        t = _reuse(out, slot, viewz, shape, dtype)
+        res[slot] = (t, fmt)
+        return _plane(t, fmt)
+
+    nr_dtype, nr_ch = _NR_DTYPE[api.NORMAL_ROUGHNESS_FORMAT_NAME]
+    d.outNormalRoughness = output(R.IN_NORMAL_ROUGHNESS, (h, w) if nr_ch == 1 else (h, w, nr_ch), nr_dtype, F[api.NORMAL_ROUGHNESS_FORMAT_NAME])
+    d.outViewZ = output(R.IN_VIEWZ, (h, w), "float32", F.R32_SFLOAT)
+    if material_id is not None:
+        d.materialID = _fp32_plane(material_id, 1, "material_id")
+    if motion is not None:
+        d.motion = _fp32_plane(motion, motion.shape[2], "motion")
+        d.outMv = output(R.IN_MV, (h, w, 4), "float16", F.RGBA16_SFLOAT)
+    for name, t in (("albedo", albedo), ("rf0", rf0)):
+        if t is not None:
+            t, plane = _rgba_arg(t, name)
+            keep.append(t)
+            setattr(d, name, plane)
+    if distance_to_occluder is not None:
+        d.distanceToOccluder = _fp32_plane(distance_to_occluder, 1, "distance_to_occluder")
+        d.outPenumbra = output(R.IN_PENUMBRA, (h, w), "float16", F.R16_SFLOAT)
+        if translucency is not None:
+            t, d.translucency = _rgba_arg(translucency, "translucency")
+            keep.append(t)
+            d.outTranslucency = output(R.IN_TRANSLUCENCY, (h, w, 4), "uint8", F.RGBA8_UNORM)
+    for which, sig, dst in (("diffuse", diffuse, d.diffuse), ("specular", specular, d.specular)):
+        if sig is None:
+            continue
+        mode = SignalMode(sig["mode"])
+        dst.mode = int(mode)
+        t, dst.radianceHitDist = _rgba_arg(sig["radiance_hitdist"], which + " radiance_hitdist")
+        keep.append(t)
+        if sig.get("direction") is not None:
+            t, dst.direction = _rgba_arg(sig["direction"], which + " direction")
+            keep.append(t)
+        slot0, slot1 = signal_slots(which, mode, "IN")
+        dtype, ch, fmt = _SIGNAL_OUT[mode]
+        dst.out0 = output(slot0, (h, w) if ch == 1 else (h, w, ch), dtype, fmt)
+        if slot1 is not None:
+            dst.out1 = output(slot1, (h, w, 4), "float16", F.RGBA16_SFLOAT)
+    return res, d, keep + [common_settings]
+
+
+# ---- back end --------------------------------------------------------------------------------------------------------------------------------------------
+_IN_FORMAT = {("float16", 4): F.RGBA16_SFLOAT, ("float32", 4): F.RGBA32_SFLOAT, ("int16", 1): F.R16_UNORM, ("uint16", 1): F.R16_UNORM, ("int16", 4): F.RGBA16_SNORM, ("uint8", 1): F.R8_UNORM,
+              ("uint8", 4): F.RGBA8_UNORM}
+
+
+def _packed_plane(t, what):
+    key = (_dtype_name(t), 1 if t.ndim == 2 else t.shape[2])
+    assert key in _IN_FORMAT, "%s: no plane format for dtype %s with %d channel(s)" % (what, key[0], key[1])
+    return _plane(t, _IN_FORMAT[key])
+
+
+def resolve_outputs(**kw):
+    """see describe_resolve; launches on `stream` (as pack_inputs) and returns the fp32 planes"""
+    like = next(t for t in (kw.get("shadow"), kw.get("viewz"), kw.get("normal_roughness"), (kw.get("diffuse") or {}).get("in0"), (kw.get("specular") or {}).get("in0")) if t is not None)
+    with _stream_scope(like, kw.get("stream")):
+        res, d, keep = describe_resolve(**kw)
+        lib = kw.get("lib") or api.load_library()
+        _check(lib, lib.nrdHipResolveOutputs(C.byref(d), _stream(like, kw.get("stream"))), "nrdHipResolveOutputs")
+    return res
+
+
+def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=None, viewz=None, albedo=None, rf0=None, common_settings=None, hit_dist_params=HIT_DIST_PARAMS,
+                     denormalize_hit_dist=False, remodulate=False, want=(), out=None, stream=None, lib=None):
+    """The descriptor of one nrdHipResolveOutputs launch, without launching: (fp32 planes, api.HipBackEndDesc, arrays it points into besides its arguments). diffuse / specular: dict(mode=SignalMode, resolve=ResolveMode, in0=OUT_*_RADIANCE_HITDIST / _SH0 / _HITDIST / DIRECTION_HITDIST array,
+    in1=OUT_*_SH1 array) -- the arrays bound as outputs (fp16 / int16) or fp32 [H, W, 4]; shadow: the OUT_SHADOW_TRANSLUCENCY array (uint8 [H, W] or [H, W, 4]);
+    normal_roughness / viewz: the packed IN_NORMAL_ROUGHNESS / IN_VIEWZ arrays; want: any of "composed", "view_vector", "factors". Returns fp32 arrays under
+    "diffuse", "specular", "shadow", "composed", "view_vector", "diff_factor", "spec_factor"."""
+    d = api.HipBackEndDesc()
+    like = next(t for t in (shadow, viewz, normal_roughness, (diffuse or {}).get("in0"), (specular or {}).get("in0")) if t is not None)
+    h, w = like.shape[:2]
+    keep, res = [], {}
+    d.commonSettings = _settings_ptr(common_settings)
+    d.hitDistParams[:] = hit_dist_params
+    d.denormalizeHitDist, d.remodulate = int(bool(denormalize_hit_dist)), int(bool(remodulate))
+
+    def output(name, shape, fmt):
+        t = _reuse(out, name, like, shape, "float32")
+        res[name] = t
+        return _plane(t, fmt)
+
+    if normal_roughness is not None:
+        d.normalRoughness = _plane(normal_roughness, F[api.NORMAL_ROUGHNESS_FORMAT_NAME])
+    if viewz is not None:
+        d.viewZ = _fp32_plane(viewz, 1, "viewz")
+    for name, t in (("albedo", albedo), ("rf0", rf0)):
+        if t is not None:
+            t, plane = _rgba_arg(t, name)
+            keep.append(t)
+            setattr(d, name, plane)
+    for which, sig, dst in (("diffuse", diffuse, d.diffuse), ("specular", specular, d.specular)):
+        if sig is None:
+            continue
+        mode = SignalMode(sig["mode"])
+        dst.mode, dst.resolve = int(mode), int(sig.get("resolve", ResolveMode.SG_EXTRACT_COLOR))
+        dst.in0 = _packed_plane(sig["in0"], which + " in0")
+        if sig.get("in1") is not None:
+            dst.in1 = _packed_plane(sig["in1"], which + " in1")
+        dst.out = output(which, (h, w), F.R32_SFLOAT) if mode == SignalMode.REBLUR_OCCLUSION else output(which, (h, w, 4), F.RGBA32_SFLOAT)
+    if shadow is not None:
+        d.shadow = _packed_plane(shadow, "shadow")
+        d.outShadow = output("shadow", tuple(shadow.shape), F.R32_SFLOAT if shadow.ndim == 2 else F.RGBA32_SFLOAT)
+    if "composed" in want:
+        d.outComposed = output("composed", (h, w, 4), F.RGBA32_SFLOAT)
+    if "view_vector" in want:
+        d.outViewVector = output("view_vector", (h, w, 4), F.RGBA32_SFLOAT)
+    if "factors" in want:
+        d.outDiffFactor = output("diff_factor", (h, w, 4), F.RGBA32_SFLOAT)
+        d.outSpecFactor = output("spec_factor", (h, w, 4), F.RGBA32_SFLOAT)
+    return res, d, keep + [common_settings]

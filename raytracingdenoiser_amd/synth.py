@@ -212,7 +212,9 @@ def _pack_relax(out, name, radiance, hit_dist, direction):
 
 def render_frame(width, height, frame, device="cpu", static_camera=False, noise=True, seed=7, want=("reblur",), camera_frame=None):
     """Returns a dict with the packed planes and the camera (for CommonSettings). camera_frame: the frame index the camera pose is taken from
-    (default: frame) -- a camera that stops moving while the noise keeps changing."""
+    (default: frame) -- a camera that stops moving while the noise keeps changing. want "raw": additionally out["raw"], the fp32 values in front of the packers (what an
+    application holds: the input of frontend.pack_inputs) -- normal, roughness, material_id, albedo, diff / spec _radiance, _hit_dist (world units, 0 on the sky), _direction,
+    distance_to_occluder (0 where NoL <= 0, FP16_MAX on a miss)."""
     dev = torch.device(device)
     cam = Camera(width, height, frame if camera_frame is None else camera_frame, static=static_camera)
     ys, xs = torch.meshgrid(torch.arange(height, device=dev), torch.arange(width, device=dev), indexing="ij")
@@ -244,6 +246,9 @@ def render_frame(width, height, frame, device="cpu", static_camera=False, noise=
     if "materials" in want:  # material IDs 0..3 in bands of the world position (consumed when minMaterialForDiffuse / ForSpecular < 3 or a special material ID matches)
         material_id = torch.where(is_sky, torch.zeros_like(rough), torch.remainder(torch.floor(p[..., 0] * 0.9) + torch.floor(p[..., 2] * 0.9), 4.0))
     out["normal_roughness"] = pack_normal_roughness(n, rough, material_id).contiguous()
+    raw = None
+    if "raw" in want:
+        raw = out["raw"] = {"normal": n, "roughness": rough, "material_id": material_id, "albedo": alb}
     out["mv"] = torch.zeros((height, width, 4), dtype=torch.float16, device=dev)  # static scene, world-space MVs scaled by 0
     if "basecolor" in want:
         # IN_BASECOLOR_METALNESS (RGBA8_UNORM): the surface albedo as base colour, metalness in bands {0, 0.5, 1} of the world position
@@ -281,6 +286,8 @@ def render_frame(width, height, frame, device="cpu", static_camera=False, noise=
         nhd = torch.where(is_sky, torch.zeros_like(hit_d), _norm_hit_dist(hit_d, view_z, torch.ones_like(rough)))
         out["diff"] = torch.cat([_ycocg(rad), nhd.unsqueeze(-1)], -1).clamp(-FP16_MAX, FP16_MAX).to(torch.float16).contiguous()
         out["diff_sh1"] = _reblur_sh1(rad, wd)
+        if raw is not None:
+            raw.update(diff_radiance=rad, diff_hit_dist=torch.where(is_sky, torch.zeros_like(hit_d), hit_d), diff_direction=wd)
         # REBLUR_FrontEnd_PackDirectionalOcclusion (NRD.hlsli:776-787): (direction * normHitDist, normHitDist) as RGBA16_SNORM texels
         do = torch.cat([wd.clamp(-1.0, 1.0) * nhd.unsqueeze(-1), nhd.unsqueeze(-1)], -1).clamp(-1.0, 1.0) * 32767.0
         out["diff_direction_hitdist"] = torch.where(do >= 0, torch.floor(do + 0.5), -torch.floor(-do + 0.5)).to(torch.int16).contiguous()
@@ -304,6 +311,8 @@ def render_frame(width, height, frame, device="cpu", static_camera=False, noise=
         nhd = torch.where(is_sky, torch.zeros_like(hit_d), _norm_hit_dist(hit_d, view_z, rough))
         out["spec"] = torch.cat([_ycocg(rad), nhd.unsqueeze(-1)], -1).clamp(-FP16_MAX, FP16_MAX).to(torch.float16).contiguous()
         out["spec_sh1"] = _reblur_sh1(rad, ws)
+        if raw is not None:
+            raw.update(spec_radiance=rad, spec_hit_dist=torch.where(is_sky, torch.zeros_like(hit_d), hit_d), spec_direction=ws)
         if "relax" in want:
             _pack_relax(out, "spec", rad, torch.where(is_sky, torch.zeros_like(hit_d), hit_d), ws)
 
@@ -336,6 +345,9 @@ def render_frame(width, height, frame, device="cpu", static_camera=False, noise=
         pen = torch.where(ndl <= 0.0, torch.zeros_like(pen), pen)
         pen = torch.where(is_sky, torch.full_like(pen, FP16_MAX), pen)
         out["penumbra"] = pen.to(torch.float16).contiguous()
+        if raw is not None:
+            occluder = torch.where(torch.isinf(ts) | is_sky, torch.full_like(ts, FP16_MAX), ts.clamp(max=FP16_MAX))
+            raw["distance_to_occluder"] = torch.where((ndl <= 0.0) & ~is_sky, torch.zeros_like(occluder), occluder)
         # IN_TRANSLUCENCY for SIGMA_SHADOW_TRANSLUCENCY = SIGMA_FrontEnd_PackTranslucency (NRD.hlsli:848-855): x = "distance to occluder
         # >= FP16_MAX" (lit), yzw = saturate(translucency). The cyan sphere (roughness 0.45) is stained glass, everything else is opaque.
         lit = pen >= FP16_MAX

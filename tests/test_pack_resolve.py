@@ -1,0 +1,881 @@
+"""nrdHipPackInputs / nrdHipResolveOutputs (include/NRDHip.h, raytracingdenoiser_amd/frontend.py): the front end and the back end as kernels of the library.
+
+Every comparison is written once and runs on two backends: "hip" (the GPU, torch CUDA tensors, lib/libNRD_hip.so) and "emu" (the same device source compiled for the CPU,
+tests/emu, numpy arrays -- part of the CPU suite). Expected values never come from the code under test:
+  A  the reference's own NRD.hlsli through oracle/_ref (NRD_FrontEndProbe.cs), where it is built
+  B  include/NRD.hip.h evaluated on the host by tests/cpp/frontend_check --dump-host: 131 072 samples = one 512 x 256 frame, inputs included
+  C  tests/frontend_model.py, a float64 restatement of NRD.hlsli, for what the dump does not hold (the diffuse signal's roughness of 1, N from the packed texel)
+Bounds (none is new): emu == B bit for bit; hip == B bit for bit wherever tests/cpp/frontend_check.hip holds device == host bit for bit, else its 2e-4 relative / 1e-5 absolute
+below 0.05 on fp32 values and one code of the stored format on quantised ones; against C the bounds of tests/test_frontend_header.py."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import frontend_model as M
+import parity
+import test_frontend_header as TFH
+import test_host_constants as THC
+from oracle import driver as oracle_driver
+from raytracingdenoiser_amd import api, frontend, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F, R, S, RES = api.Format, api.ResourceType, api.SignalMode, api.ResolveMode
+W, H = 512, 256
+COUNT = W * H
+HDP = (3.0, 0.1, 20.0, -25.0)
+f32 = np.float32
+BACKENDS = [pytest.param("emu"), pytest.param("hip", marks=pytest.mark.gpu)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------- backends
+class Backend:
+    def __init__(self, name):
+        self.name = name
+        if name == "emu":
+            sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+            from emu import emu_run
+
+            self.lib = emu_run.load()
+        else:
+            self.lib = api.load_library()
+
+    def up(self, a):
+        a = np.ascontiguousarray(a)
+        return a.copy() if self.name == "emu" else torch.from_numpy(a).cuda()
+
+    def down(self, t):
+        if self.name == "emu":
+            return t
+        torch.cuda.synchronize()
+        return t.cpu().numpy()
+
+    def up_pitched(self, a, pad):
+        """a copy of `a` on the device inside a wider allocation: row pitch = (W + pad) texels, first row offset by one row, sentinel values around it"""
+        a = np.ascontiguousarray(a)
+        big = np.full((a.shape[0] + 2, a.shape[1] + pad) + tuple(a.shape[2:]), 77, dtype=a.dtype)
+        big[1:-1, : a.shape[1]] = a
+        big = big if self.name == "emu" else torch.from_numpy(big).cuda()
+        return big[1:-1, : a.shape[1]]
+
+    def padded(self, shape, dtype, pad, stamp):
+        """([H, W(, C)] view, the whole allocation): rows `pad` texels longer than the plane, one row more than the plane, everything stamped"""
+        big_shape = (shape[0] + 1, shape[1] + pad) + tuple(shape[2:])
+        big = np.full(big_shape, stamp, dtype=dtype)
+        big = big if self.name == "emu" else torch.from_numpy(big).cuda()
+        return big[: shape[0], : shape[1]], big
+
+
+@pytest.fixture(scope="module")
+def dump():
+    TFH._build()
+    path = os.path.join(os.path.dirname(TFH.EXE), "pack_resolve_dump.bin")
+    r = subprocess.run([TFH.EXE, "--dump-host", path, str(COUNT)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    d = TFH._load_dump(path, COUNT)
+    os.remove(path)
+    return d
+
+
+def img(d, *names, w=W, h=H):
+    """the named dump columns side by side as an [h, w, C] ([h, w] for one column) float32 crop of the 512 x 256 frame"""
+    cols = [np.asarray(d[n] if isinstance(n, str) else n).reshape(H, W, -1) for n in names]
+    a = np.concatenate(cols, axis=-1)[:h, :w]
+    return np.ascontiguousarray(a[..., 0] if a.shape[-1] == 1 else a)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------- codecs (numpy)
+def f16(a):
+    return np.asarray(a, f32).astype(np.float16)  # round to nearest even, denormals kept
+
+
+def unorm16(a):
+    return np.floor(np.clip(np.asarray(a, f32), 0, 1) * f32(65535) + f32(0.5)).astype(np.uint16).view(np.int16)
+
+
+def snorm16(a):
+    t = np.clip(np.asarray(a, f32), -1, 1) * f32(32767)
+    return np.where(t >= 0, np.floor(t + f32(0.5)), -np.floor(-t + f32(0.5))).astype(np.int16)
+
+
+def unorm8(a):
+    return np.floor(np.clip(np.asarray(a, f32), 0, 1) * f32(255) + f32(0.5)).astype(np.uint8)
+
+
+def codes(a):
+    """integer code of every stored value, monotone in the value: fp16 bit patterns in sign-magnitude order, UNORM / SNORM integers as they are"""
+    a = np.asarray(a)
+    if a.dtype == np.float16:
+        i = a.view(np.int16).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7FFF), i)
+    return a.astype(np.int64)
+
+
+def assert_codes(got, want, what, unorm=False):
+    """at most one code of the stored format apart"""
+    g, w_ = np.asarray(got), np.asarray(want)
+    assert g.dtype == w_.dtype and g.shape == w_.shape, (what, g.dtype, w_.dtype, g.shape, w_.shape)
+    if unorm:
+        g, w_ = g.view(np.uint16), w_.view(np.uint16)
+    dist = np.abs(codes(g) - codes(w_))
+    print("%-60s max code distance %d, %.4f %% equal" % (what, dist.max(), 100.0 * np.mean(dist == 0)))
+    assert dist.max() <= 1, "%s: %d codes apart at %s" % (what, dist.max(), np.unravel_index(int(np.argmax(dist)), dist.shape))
+
+
+def assert_bits(got, want, what):
+    g, w_ = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert g.dtype == w_.dtype and g.shape == w_.shape, (what, g.dtype, w_.dtype, g.shape, w_.shape)
+    same = g.view(np.uint8) == w_.view(np.uint8)
+    print("%-60s bit for bit: %s" % (what, bool(same.all())))
+    assert same.all(), "%s: %d of %d bytes differ" % (what, int((~same).sum()), same.size)
+
+
+def assert_platform(got, want, what):
+    """tests/cpp/frontend_check.hip:233-239: 2e-4 relative, 1e-5 absolute below 0.05 (results behind exp / log / pow of two math libraries)"""
+    g, w_ = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    err = np.abs(g - w_) / np.maximum(np.maximum(np.abs(g), np.abs(w_)), 0.05)
+    print("%-60s max error %.3g (allowed 2e-4)" % (what, err.max()))
+    assert np.all(np.isfinite(g)) and err.max() <= 2e-4, "%s: %.3g" % (what, err.max())
+
+
+def assert_model(got, want, rel, what, floor=1.0):
+    """tests/test_frontend_header.py close(): |got - want| / max(|want|, floor)"""
+    err = np.abs(np.asarray(got, np.float64) - want) / np.maximum(np.abs(want), floor)
+    print("%-60s max error %.3g (allowed %.3g)" % (what, err.max(), rel))
+    assert np.all(np.isfinite(got)) and err.max() <= rel, "%s: %.3g (allowed %.3g)" % (what, err.max(), rel)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------- 1. validation
+def _plane(a, fmt, w=None, h=None, pitch=None):
+    return api.HipPlaneDesc(a.ctypes.data, a.strides[0] if pitch is None else pitch, int(fmt), a.shape[1] if w is None else w, a.shape[0] if h is None else h)
+
+
+def _front_desc(keep, w=64, h=32):
+    nr, z, rad, o0 = np.zeros((h, w, 4), f32), np.ones((h, w), f32), np.zeros((h, w, 4), f32), np.zeros((h, w, 4), np.float16)
+    word, zo = np.zeros((h, w), np.int32), np.zeros((h, w), f32)
+    keep += [nr, z, rad, o0, word, zo]
+    d = api.HipFrontEndDesc()
+    d.hitDistParams[:] = HDP
+    d.normalRoughness, d.viewZ = _plane(nr, F.RGBA32_SFLOAT), _plane(z, F.R32_SFLOAT)
+    d.outNormalRoughness, d.outViewZ = _plane(word, F[api.NORMAL_ROUGHNESS_FORMAT_NAME]), _plane(zo, F.R32_SFLOAT)
+    d.specular.mode = int(S.REBLUR_RADIANCE)
+    d.specular.radianceHitDist, d.specular.out0 = _plane(rad, F.RGBA32_SFLOAT), _plane(o0, F.RGBA16_SFLOAT)
+    return d
+
+
+def _ortho_settings(w, h):
+    cs = api.CommonSettings(resourceSize=(w, h), rectSize=(w, h), resourceSizePrev=(w, h), rectSizePrev=(w, h))
+    for m in (cs.viewToClipMatrix, cs.worldToViewMatrix):
+        for k in (0, 5, 10, 15):
+            m[k] = 1.0
+    return cs
+
+
+def test_validation_rules_return_their_codes_without_a_device():
+    """every rule of the header comment, on the real library with no GPU present: the code, a non-empty text, and (there being no device) nothing enqueued"""
+    lib = api.load_library()
+    RC = api.Result
+    keep = []
+
+    def pack(mutate):
+        d = _front_desc(keep)
+        mutate(d)
+        code = RC(lib.nrdHipPackInputs(C.byref(d), None))
+        text = lib.nrdHipGetLastFrontEndError().decode()
+        assert text, "no error text for %s" % code.name
+        return code
+
+    def set_(path, **kw):
+        def f(d):
+            obj = d
+            for p in path.split(".")[:-1]:
+                obj = getattr(obj, p)
+            plane = getattr(obj, path.split(".")[-1])
+            for k, v in kw.items():
+                setattr(plane, k, v)
+        return f
+
+    assert RC(lib.nrdHipPackInputs(None, None)) == RC.INVALID_ARGUMENT and lib.nrdHipGetLastFrontEndError()
+    assert pack(set_("normalRoughness", data=None)) == RC.INVALID_ARGUMENT  # a required plane
+    assert pack(set_("viewZ", data=None)) == RC.INVALID_ARGUMENT
+    assert pack(set_("viewZ", format=int(F.R16_SFLOAT))) == RC.UNSUPPORTED  # a format that is not listed
+    assert pack(set_("specular.out0", format=int(F.RGBA32_SFLOAT))) == RC.UNSUPPORTED
+    assert pack(set_("outNormalRoughness", format=int(F.RGBA16_SFLOAT))) == RC.UNSUPPORTED
+    assert pack(set_("viewZ", width=63)) == RC.INVALID_ARGUMENT  # mismatched sizes
+    assert pack(set_("specular.out0", height=31)) == RC.INVALID_ARGUMENT
+    assert pack(set_("normalRoughness", rowPitchBytes=64 * 16 + 8)) == RC.INVALID_ARGUMENT  # not a texel multiple
+    assert pack(set_("viewZ", rowPitchBytes=64 * 4 - 4)) == RC.INVALID_ARGUMENT  # below the row
+    assert pack(set_("viewZ", rowPitchBytes=1 << 24)) == RC.UNSUPPORTED  # the 32-bit limits of nrdHipBindResource
+
+    def whole(d):  # pitch x height beyond 4 GiB
+        for p in (d.normalRoughness, d.viewZ, d.outNormalRoughness, d.outViewZ, d.specular.radianceHitDist, d.specular.out0):
+            p.height = 4096
+        d.normalRoughness.rowPitchBytes = 1 << 20
+    assert pack(whole) == RC.UNSUPPORTED
+
+    def sh_without_direction(d):
+        d.specular.mode = int(S.REBLUR_SH)
+        d.specular.out1 = d.specular.out0
+    assert pack(sh_without_direction) == RC.INVALID_ARGUMENT  # a mode that needs a direction plane
+
+    def sh_without_out1(d):
+        d.specular.mode = int(S.RELAX_SH)
+        d.specular.direction = d.specular.radianceHitDist
+    assert pack(sh_without_out1) == RC.INVALID_ARGUMENT
+
+    def albedo_alone(d):
+        d.albedo = d.specular.radianceHitDist
+    assert pack(albedo_alone) == RC.INVALID_ARGUMENT  # demodulation needs both planes ...
+
+    def no_camera(d):
+        d.albedo = d.rf0 = d.specular.radianceHitDist
+    assert pack(no_camera) == RC.INVALID_ARGUMENT  # ... and the camera
+
+    ortho = _ortho_settings(64, 32)
+
+    def ortho_camera(d):
+        no_camera(d)
+        d.commonSettings = C.cast(C.byref(ortho), C.c_void_p)
+    assert pack(ortho_camera) == RC.UNSUPPORTED  # orthographic, as everywhere else
+    assert pack(set_("specular", mode=99)) == RC.INVALID_ARGUMENT
+    assert pack(lambda d: setattr(d, "outMv", d.specular.out0)) == RC.INVALID_ARGUMENT  # outMv without motion
+    assert pack(lambda d: setattr(d, "outPenumbra", _plane(np.zeros((32, 64), np.float16), F.R16_SFLOAT))) == RC.INVALID_ARGUMENT  # no distanceToOccluder
+
+    # ---- back end
+    sh0, sh1, out, word, z = np.zeros((32, 64, 4), f32), np.zeros((32, 64, 4), f32), np.zeros((32, 64, 4), f32), np.zeros((32, 64), np.int32), np.ones((32, 64), f32)
+    persp = parity.common_settings(synth.Camera(64, 32, 0), synth.Camera(64, 32, 0), 64, 32, 0)
+
+    def resolve(mutate):
+        d = api.HipBackEndDesc()
+        d.hitDistParams[:] = HDP
+        d.specular.mode, d.specular.resolve = int(S.REBLUR_SH), int(RES.SG)
+        d.specular.in0, d.specular.in1, d.specular.out = _plane(sh0, F.RGBA32_SFLOAT), _plane(sh1, F.RGBA32_SFLOAT), _plane(out, F.RGBA32_SFLOAT)
+        d.normalRoughness, d.viewZ = _plane(word, F[api.NORMAL_ROUGHNESS_FORMAT_NAME]), _plane(z, F.R32_SFLOAT)
+        d.commonSettings = C.cast(C.byref(persp), C.c_void_p)
+        mutate(d)
+        code = RC(lib.nrdHipResolveOutputs(C.byref(d), None))
+        assert lib.nrdHipGetLastFrontEndError().decode(), "no error text for %s" % code.name
+        return code
+
+    assert RC(lib.nrdHipResolveOutputs(None, None)) == RC.INVALID_ARGUMENT
+    assert resolve(set_("specular.in1", data=None)) == RC.INVALID_ARGUMENT
+    assert resolve(set_("specular.out", data=None)) == RC.INVALID_ARGUMENT
+    assert resolve(set_("normalRoughness", data=None)) == RC.INVALID_ARGUMENT  # the SG resolve needs N
+    assert resolve(set_("viewZ", data=None)) == RC.INVALID_ARGUMENT  # ... and V
+    assert resolve(lambda d: setattr(d, "commonSettings", None)) == RC.INVALID_ARGUMENT
+    assert resolve(lambda d: setattr(d, "commonSettings", C.cast(C.byref(ortho), C.c_void_p))) == RC.UNSUPPORTED
+    assert resolve(set_("specular.in0", format=int(F.RGBA16_SNORM))) == RC.UNSUPPORTED
+    assert resolve(set_("specular.in1", format=int(F.RGBA16_SFLOAT))) == RC.INVALID_ARGUMENT  # SH0 fp32, SH1 fp16 (8-byte texels at a 16-byte pitch are fine; the pair must agree)
+    assert resolve(set_("specular.out", format=int(F.RGBA16_SFLOAT))) == RC.UNSUPPORTED
+    assert resolve(set_("viewZ", width=32)) == RC.INVALID_ARGUMENT
+    assert resolve(set_("specular.out", rowPitchBytes=64 * 16 + 4)) == RC.INVALID_ARGUMENT
+    assert resolve(set_("specular.out", rowPitchBytes=1 << 24)) == RC.UNSUPPORTED
+    assert resolve(lambda d: setattr(d, "remodulate", 1)) == RC.INVALID_ARGUMENT  # no albedo / rf0
+    assert resolve(lambda d: setattr(d, "outComposed", d.specular.out)) == RC.INVALID_ARGUMENT  # no diffuse signal to add
+    assert resolve(lambda d: setattr(d, "outShadow", d.viewZ)) == RC.INVALID_ARGUMENT  # no shadow plane
+    assert resolve(set_("specular", resolve=7)) == RC.INVALID_ARGUMENT
+    persp.rectSize[0] = 32
+    assert resolve(lambda d: None) == RC.INVALID_ARGUMENT  # the camera's rect is not the planes'
+
+
+def test_symbols_structs_and_python_surface():
+    lib = api.load_library()
+    for name in ("nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError"):
+        assert name in api.NRD_HIP_SYMBOLS and getattr(lib, name)
+    hdr = open(os.path.join(ROOT, "include", "NRDHip.h")).read()
+    for mode in S:
+        assert "#define NRD_HIP_SIGNAL_%s %du" % (mode.name, int(mode)) in hdr
+    for mode in RES:
+        assert "#define NRD_HIP_RESOLVE_%s %du" % (mode.name, int(mode)) in hdr
+    from raytracingdenoiser_amd.executor import HipExecutor
+
+    assert callable(HipExecutor.bind_packed) and callable(HipExecutor.resolve)
+    assert "PackInputs" in open(os.path.join(ROOT, "include", "NRDIntegrationHip.hpp")).read()
+
+
+def test_compiled_kernels_spill_nothing_and_load_whole_texels():
+    """what the compiler made of the two kernels for gfx950 (tools/frontend_bench.py isa(), the `isa` object of profiles/frontend_bench.json): no scratch, no LDS, 16-byte loads for the
+    RGBA32_SFLOAT texels that are consumed whole (normal + roughness, the two radiance + hit distance planes, motion), at least 8 waves per SIMD"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import frontend_bench
+
+    facts = frontend_bench.isa()
+    for name, k in facts.items():
+        print(name, k)
+        assert k["scratch_bytes"] == 0 and k["lds_bytes"] == 0 and k["waves_per_simd"] >= 8 and 0 < k["vgprs"] <= 64, (name, k)
+    assert facts["pack"]["global_load_dwordx4"] >= 3 and facts["resolve"]["global_load_dwordx4"] >= 4 and facts["resolve"]["global_store_dwordx4"] >= 4
+
+
+def test_synth_raw_is_additive():
+    """want=("raw",) adds out["raw"] and changes no other byte"""
+    a = synth.render_frame(48, 32, 1, want=("reblur", "relax", "sigma"))
+    b = synth.render_frame(48, 32, 1, want=("reblur", "relax", "sigma", "raw"))
+    assert set(b) - set(a) == {"raw"}
+    for k, v in a.items():
+        if torch.is_tensor(v):
+            assert torch.equal(v.view(torch.uint8) if v.dtype != torch.bool else v, b[k].view(torch.uint8) if v.dtype != torch.bool else b[k]), k
+    assert {"normal", "roughness", "material_id", "diff_radiance", "diff_hit_dist", "diff_direction", "spec_radiance", "spec_hit_dist", "spec_direction", "distance_to_occluder"} <= set(b["raw"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------- 2 / 3. pack
+TAN_LIGHT = 0.02  # the dump's SIGMA_FrontEnd_PackPenumbra( occluder, 0.02 )
+
+
+def pack_inputs_of(d, w, h):
+    i = np.arange(COUNT)
+    occluder = np.where(i % 5 == 0, f32(M.NRD_FP16_MAX), d["hitDist"][:, 0]).astype(f32)
+    motion = np.stack([d["radiance"][:, 0] * f32(40000.0) - f32(70000.0), d["direction"][:, 1] * f32(3.0), d["viewZ"][:, 0], d["roughness"][:, 0] * f32(1e5)], -1).astype(f32)
+    return dict(nr=img(d, "N", "roughness", w=w, h=h), viewz=img(d, "viewZ", w=w, h=h), material=img(d, "materialID_in", w=w, h=h), rad=img(d, "radiance", "hitDist", w=w, h=h),
+                direction=img(d, "direction", np.zeros((COUNT, 1), f32), w=w, h=h), albedo=img(d, "albedo", np.zeros((COUNT, 1), f32), w=w, h=h), occluder=img(d, occluder, w=w, h=h),
+                motion=img(d, motion, w=w, h=h))
+
+
+PACK_CALLS = [  # (diffuse mode, specular mode, with the G-buffer / SIGMA planes)
+    (S.REBLUR_RADIANCE, S.REBLUR_RADIANCE, True), (S.REBLUR_SH, S.REBLUR_SH, False), (S.REBLUR_OCCLUSION, S.REBLUR_OCCLUSION, False),
+    (S.REBLUR_DIRECTIONAL_OCCLUSION, S.RELAX_RADIANCE, False), (S.RELAX_SH, S.RELAX_SH, False), (S.RELAX_RADIANCE, None, False)]
+
+
+def run_pack(be, ins, pad=0):
+    """every mode of the pack kernel: {(call, ResourceType): host array}; pad: the outputs live in wider, stamped allocations -> also {key: whole allocation}"""
+    h, w = ins["viewz"].shape
+    dev = {k: (be.up_pitched(v, pad + 3) if pad else be.up(v)) for k, v in ins.items()}  # pad: every INPUT plane has a row pitch larger than its row, too
+    got, whole = {}, {}
+    for call, (dm, sm, full) in enumerate(PACK_CALLS):
+        kw = dict(diffuse=dict(mode=dm, radiance_hitdist=dev["rad"], direction=dev["direction"]), hit_dist_params=HDP, lib=be.lib)
+        if sm is not None:
+            kw["specular"] = dict(mode=sm, radiance_hitdist=dev["rad"], direction=dev["direction"])
+        if full:
+            kw.update(material_id=dev["material"], motion=dev["motion"], distance_to_occluder=dev["occluder"], translucency=dev["albedo"], tan_of_light_angular_radius=TAN_LIGHT)
+        out = None
+        if pad:
+            probe = frontend.pack_inputs(dev["nr"], dev["viewz"], **kw)  # (shapes and dtypes of this call's outputs)
+            out, bigs = {}, {}
+            for rt, (t, fmt) in probe.items():
+                view, big = be.padded(tuple(t.shape), str(t.dtype).replace("torch.", ""), pad, 0x5A if "uint8" in str(t.dtype) else 23130)
+                out[rt], bigs[rt] = (view, fmt), big
+        res = frontend.pack_inputs(dev["nr"], dev["viewz"], out=out, **kw)
+        for rt, (t, fmt) in res.items():
+            got[(call, rt)] = be.down(t)
+            if pad:
+                whole[(call, rt)] = be.down(bigs[rt])
+    return got, whole
+
+
+def check_pack(be, got, d, w, h):
+    """the packed planes of run_pack against B (the specular side, the G-buffer, SIGMA) and C (the diffuse side: roughness 1)"""
+    exact = be.name == "emu"  # same libm, same unfused arithmetic as B
+    i = np.arange(COUNT)
+    hit, z = d["hitDist"][:, 0].astype(np.float64), d["viewZ"][:, 0].astype(np.float64)
+    rad, dirn = d["radiance"].astype(np.float64), d["direction"].astype(np.float64)
+    g = lambda call, rt: got[(call, rt)]
+    crop = lambda a: img(d, a, w=w, h=h)
+
+    # G-buffer and SIGMA (call 0): codecs and + - * / only -> bit for bit on both backends
+    assert_bits(g(0, R.IN_NORMAL_ROUGHNESS).view(np.uint32), crop(d["word"].view(f32)).view(np.uint32), "IN_NORMAL_ROUGHNESS vs B")
+    assert_bits(g(0, R.IN_VIEWZ), crop(d["viewZ"]), "IN_VIEWZ")
+    motion = pack_inputs_of(d, w, h)["motion"]
+    assert_bits(g(0, R.IN_MV), f16(np.clip(motion, -M.NRD_FP16_MAX, M.NRD_FP16_MAX)), "IN_MV (clamped to +-FP16_MAX)")
+    assert np.isfinite(g(0, R.IN_MV).astype(f32)).all() and (np.abs(motion) > M.NRD_FP16_MAX).any()
+    assert_bits(g(0, R.IN_PENUMBRA), f16(crop(d["penumbra"])), "IN_PENUMBRA vs B")
+    assert_bits(g(0, R.IN_TRANSLUCENCY), unorm8(crop(d["translucency"])), "IN_TRANSLUCENCY vs B")
+
+    # specular side vs B: YCoCg / RELAX parts bit for bit, the normalised hit distance (exp2 of the platform) within one code on the GPU
+    def vs_b(call, rt, name, nhd_in_w):
+        a, want = g(call, rt), f16(crop(d[name]))
+        if exact or not nhd_in_w:
+            assert_bits(a, want, "%s (call %d) vs B %s" % (rt.name, call, name))
+        else:
+            assert_bits(a[..., :3], want[..., :3], "%s (call %d) vs B %s .xyz" % (rt.name, call, name))
+            assert_codes(a[..., 3], want[..., 3], "%s (call %d) vs B %s .w" % (rt.name, call, name))
+
+    vs_b(0, R.IN_SPEC_RADIANCE_HITDIST, "reblurPacked", True)
+    vs_b(1, R.IN_SPEC_SH0, "sh0", True)
+    vs_b(1, R.IN_SPEC_SH1, "sh1", False)
+    vs_b(3, R.IN_SPEC_RADIANCE_HITDIST, "relaxPacked", False)
+    vs_b(4, R.IN_SPEC_SH0, "relaxPacked", False)
+    vs_b(4, R.IN_SPEC_SH1, "relaxSh1", False)
+    want = unorm16(crop(d["normHitDist"]))
+    (assert_bits if exact else lambda a, b, t: assert_codes(a, b, t, unorm=True))(g(2, R.IN_SPEC_HITDIST), want, "IN_SPEC_HITDIST vs B normHitDist")
+
+    # diffuse side vs C: the hit distance is normalised with roughness 1
+    nhd = M.reblur_get_norm_hit_dist(hit, z, HDP, 1.0)
+    assert_codes(g(0, R.IN_DIFF_RADIANCE_HITDIST), f16(crop(M.reblur_pack_radiance_and_norm_hit_dist(rad, nhd))), "IN_DIFF_RADIANCE_HITDIST vs C")
+    sh0, sh1 = M.reblur_pack_sh(rad, nhd, dirn)
+    assert_codes(g(1, R.IN_DIFF_SH0), f16(crop(sh0)), "IN_DIFF_SH0 (REBLUR) vs C")
+    assert_codes(g(1, R.IN_DIFF_SH1), f16(crop(sh1)), "IN_DIFF_SH1 (REBLUR) vs C")
+    assert_codes(g(2, R.IN_DIFF_HITDIST), unorm16(crop(nhd)), "IN_DIFF_HITDIST vs C", unorm=True)
+    assert_codes(g(3, R.IN_DIFF_DIRECTION_HITDIST), snorm16(crop(M.reblur_pack_directional_occlusion(dirn, nhd))), "IN_DIFF_DIRECTION_HITDIST vs C")
+    r0, r1 = M.relax_pack_sh(rad, hit, dirn)
+    assert_codes(g(4, R.IN_DIFF_SH0), f16(crop(r0)), "IN_DIFF_SH0 (RELAX) vs C")
+    assert_codes(g(4, R.IN_DIFF_SH1), f16(crop(r1)), "IN_DIFF_SH1 (RELAX) vs C")
+    assert_codes(g(5, R.IN_DIFF_RADIANCE_HITDIST), f16(crop(r0)), "IN_DIFF_RADIANCE_HITDIST (RELAX) vs C")
+    # RELAX packs no normalised hit distance: the diffuse and the specular plane of the same input are the same bytes
+    assert_bits(g(4, R.IN_DIFF_SH0), g(4, R.IN_SPEC_SH0), "RELAX diffuse == specular pack")
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_pack_every_mode_512x256(backend, dump):
+    be = Backend(backend)
+    got, _ = run_pack(be, pack_inputs_of(dump, W, H))
+    check_pack(be, got, dump, W, H)
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_pack_197x61_with_a_row_pitch_larger_than_the_row(backend, dump):
+    """ragged size (the last workgroup of a row covers 5 of 64 pixels, the last row of groups 1 of 4 rows), every input plane inside a wider allocation, outputs in wider allocations
+    stamped with a pattern: same values, and no byte beyond the rect or between the rows is touched"""
+    be = Backend(backend)
+    w, h, pad = 197, 61, 19
+    got, whole = run_pack(be, pack_inputs_of(dump, w, h), pad=pad)
+    check_pack(be, got, dump, w, h)
+    for key, big in whole.items():
+        stamp = 0x5A if big.dtype == np.uint8 else 23130
+        want = np.full(big.shape, stamp, dtype=big.dtype)
+        want[:h, :w] = got[key]
+        assert np.array_equal(big.view(np.uint8), want.view(np.uint8)), "bytes outside the rect were written: call %d %s" % (key[0], key[1].name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------- view vector
+def camera_constants(cs):
+    """(gFrustum [4], the 3 x 3 rotation of gViewToWorld) as float32, from the constants of a REBLUR dispatch for the same CommonSettings (host only: no device)"""
+    inst = api.Instance([(0, api.Denoiser.REBLUR_DIFFUSE)])
+    assert inst.set_common_settings(cs) == api.Result.SUCCESS
+    r, ds = inst.get_compute_dispatches()
+    assert r == api.Result.SUCCESS
+    blob = [x.constants for x in ds if len(x.constants) == 832][0]
+    c, _ = THC.parse_block(blob, THC.REBLUR_LAYOUT)
+    m = c["gViewToWorld"].astype(f32).reshape(4, 4).T  # (stored column-major)
+    return c["gFrustum"].astype(f32), np.ascontiguousarray(m[:3, :3])
+
+
+def view_vector_numpy(frustum, rot, viewz):
+    """the V contract of include/NRDHip.h restated in float32 numpy, operation by operation"""
+    h, w = viewz.shape
+    u = ((np.arange(w, dtype=f32) + f32(0.5)) / f32(w))[None, :]
+    v = ((np.arange(h, dtype=f32) + f32(0.5)) / f32(h))[:, None]
+    xv = (u * frustum[2] + frustum[0]) * viewz
+    yv = (v * frustum[3] + frustum[1]) * viewz
+    xw = [(rot[i, 0] * xv + rot[i, 1] * yv) + rot[i, 2] * viewz for i in range(3)]
+    inv = f32(1.0) / np.sqrt((xw[0] * xw[0] + xw[1] * xw[1]) + xw[2] * xw[2])
+    out = np.stack([-(x * inv) for x in xw], -1)
+    assert out.dtype == f32
+    return out
+
+
+def frame_settings(w, h, frame=3):
+    cam = synth.Camera(w, h, frame)
+    return parity.common_settings(cam, cam, w, h, frame)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------- 4. resolve
+def probe_reference(d, nr_unpacked, v, word):
+    """source A: NRD_FrontEndProbe.cs of oracle/_ref with N / roughness = the unpacked texel and V = the numpy view vector; returns its output planes by name, [COUNT, 4]"""
+    zeros = np.zeros((COUNT, 1), f32)
+    tex = lambda *cols: np.ascontiguousarray(np.concatenate([np.asarray(c, f32).reshape(COUNT, -1) for c in cols], axis=1).reshape(H, W, 4))
+    i = np.arange(COUNT)
+    ins = [tex(nr_unpacked), tex(v.reshape(COUNT, 3), d["materialID_in"]), tex(d["radiance"], d["hitDist"]), tex(d["direction"], d["viewZ"]), tex(d["albedo"], (i % 5 == 0).astype(f32)),
+           tex(d["Rf0"], zeros), tex(d["Nw"], zeros)]
+    word_in = np.ascontiguousarray(word.reshape(H, W).astype(np.uint32))
+    word_out = np.zeros((H, W), np.uint32)
+    outs = [np.zeros((H, W, 4), f32) for _ in range(20)]
+    P = oracle_driver.OraclePlane
+    planes = [P(a.ctypes.data, a.strides[0], int(F.RGBA32_SFLOAT), W, H) for a in ins]
+    planes += [P(word_in.ctypes.data, word_in.strides[0], int(F.R10_G10_B10_A2_UNORM), W, H), P(word_out.ctypes.data, word_out.strides[0], int(F.R10_G10_B10_A2_UNORM), W, H)]
+    planes += [P(a.ctypes.data, a.strides[0], int(F.RGBA32_SFLOAT), W, H) for a in outs]
+    arr = (P * len(planes))(*planes)
+    consts = np.array(HDP, f32).tobytes() + np.array([W], np.uint32).tobytes() + bytes(12)
+    buf = C.create_string_buffer(consts, len(consts))
+    assert oracle_driver.load_ref().nrdref_dispatch(b"NRD_FrontEndProbe.cs", buf, len(consts), arr, len(planes), W // 8, H // 8) == 0
+    names = ["unpackedNR", "scalars", "reblurPacked", "reblurUnpacked", "sh0", "sh1", "relaxPacked", "relaxSh1", "dirOcc", "translucency", "diffFactor", "specFactor", "sgDiffuse", "sgSpecular",
+             "shDiffuse", "shSpecular", "sgColor", "sgDir", "rejitter", "misc"]
+    return {n: o.reshape(COUNT, 4) for n, o in zip(names, outs)}
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_resolve_every_mode(backend, dump):
+    """expected values of the SG / SH resolves and the material factors: A where oracle/_ref is built, else C"""
+    _resolve_every_mode(backend, dump, oracle_driver.ref_available())
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_resolve_every_mode_against_the_float64_model(backend, dump):
+    """the same with C as the expectation, wherever it runs (a checkout without oracle/_ref only ever takes this branch).
+    The G-buffer faces the viewer: a sample's normal is mirrored where N.V < 0 for the pixel's view vector before it is packed (by the model), as visible surfaces do and as the
+    samples of tests/cpp/frontend_check.hip:45-46 do, on which the bounds of NRD_SG_ResolveSpecular were taken. Measured on the header's own fp32 arithmetic with the unmirrored,
+    half back-facing set: 1.9e-3 (allowed 1e-3) for roughness >= 0.2 on the back-facing half, 5.1e-4 on the front-facing one -- the cancellation of NRD.hlsli:1003-1050, not the kernel."""
+    _resolve_every_mode(backend, dump, False)
+
+
+def _resolve_every_mode(backend, dump, use_ref):
+    d = dump
+    be = Backend(backend)
+    exact = backend == "emu"
+    default_encoding = (api.NORMAL_ENCODING, api.ROUGHNESS_ENCODING) == (2, 1)
+    assert default_encoding, "the dump's texels are R10G10B10A2 words"
+    cs = frame_settings(W, H)
+    frustum, rot = camera_constants(cs)
+    viewz = img(d, "viewZ")
+    V = view_vector_numpy(frustum, rot, viewz)
+    # IN_NORMAL_ROUGHNESS: the dump's normals turned towards the viewer, packed by the model (an input like any other: what N the kernel resolves with is what A / C unpack from it)
+    n_raw, v_flat = d["N"].astype(np.float64), V.reshape(COUNT, 3).astype(np.float64)
+    n_raw = np.where(((n_raw * v_flat).sum(-1) < 0.0)[:, None], -n_raw, n_raw)
+    word_np = M.store_r10g10b10a2(M.pack_normal_and_roughness(n_raw, d["roughness"][:, 0].astype(np.float64), d["materialID_in"][:, 0].astype(np.float64)))
+    word = be.up(np.ascontiguousarray(word_np.reshape(H, W)).view(np.int32))
+    dz = be.up(viewz)
+    common = dict(normal_roughness=word, viewz=dz, common_settings=cs, hit_dist_params=HDP, lib=be.lib)
+    # the SH pair the resolves are fed, as RGBA32_SFLOAT planes: the probe's own (A: it resolves exactly that pair, packed with the unpacked roughness) or the dump's
+    if use_ref:  # the probe twice: once for the unpacked texels, then with N / roughness set to them
+        unp = probe_reference(d, np.zeros((COUNT, 4), f32), V, word_np)["unpackedNR"].copy()
+        a = probe_reference(d, unp, V, word_np)
+    else:
+        un, _ = M.unpack_normal_and_roughness(M.load_r10g10b10a2(word_np))
+        unp, a = un.astype(f32), None
+    fed0, fed1 = (a["sh0"], a["sh1"]) if a is not None else (d["sh0"], d["sh1"])
+    sh0, sh1 = be.up(img(d, fed0)), be.up(img(d, fed1))
+    albedo, rf0 = be.up(img(d, "albedo", np.zeros((COUNT, 1), f32))), be.up(img(d, "Rf0", np.zeros((COUNT, 1), f32)))
+    flat = lambda t, n=3: be.down(t).reshape(COUNT, -1)[:, :n]
+
+    def run(mode_d, mode_s, resolve, **kw):
+        args = dict(common)
+        args.update(kw)
+        return frontend.resolve_outputs(diffuse=dict(mode=mode_d, resolve=resolve, in0=sh0, in1=sh1), specular=dict(mode=mode_s, resolve=resolve, in0=sh0, in1=sh1), **args)
+
+    # ---- the view vector: bit for bit on both backends
+    res = run(S.REBLUR_SH, S.RELAX_SH, RES.SG, want=("view_vector", "factors"), albedo=albedo, rf0=rf0)
+    assert_bits(be.down(res["view_vector"])[..., :3], V, "V vs the float32 numpy restatement")
+    sg_d, sg_s, dfac, sfac = flat(res["diffuse"]), flat(res["specular"]), flat(res["diff_factor"]), flat(res["spec_factor"])
+    assert_bits(flat(res["diffuse"], 4)[:, 3], fed0[:, 3], "SH resolve .w = the pair's hit distance")
+    res = run(S.RELAX_SH, S.REBLUR_SH, RES.SH)
+    sh_d, sh_s = flat(res["diffuse"]), flat(res["specular"])
+    res = run(S.REBLUR_SH, S.REBLUR_SH, RES.SG_EXTRACT_COLOR, normal_roughness=None, viewz=None, common_settings=None)  # needs neither N nor V
+    col_d, col_s = flat(res["diffuse"]), flat(res["specular"])
+
+    rough = unp[:, 3]
+    if a is not None:
+        assert_bits(a["sh0"][:, :3], d["sh0"][:, :3], "probe sh0.xyz == B")  # (the same radiance; .w is normalised with the unpacked roughness)
+        well = rough >= 0.05
+        assert well.sum() > 0.9 * COUNT
+        if exact:  # the rules of tests/test_frontend_header.py::test_frontend_header_equals_the_reference_nrd_hlsli_text
+            for got, name in ((sg_d, "sgDiffuse"), (sh_d, "shDiffuse"), (col_d, "sgColor"), (col_s, "sgColor"), (dfac, "diffFactor"), (sfac, "specFactor")):
+                assert_bits(got, a[name][:, :3], "%s vs A" % name)
+            assert_bits(sg_s[well], a["sgSpecular"][well][:, :3], "sgSpecular vs A (roughness >= 0.05)")
+            # NRD_SH_ResolveSpecular: >= 98 % of the values bit for bit, as tests/test_frontend_header.py:260-264 asks of the host header against A, and the bound of the resolves
+            # for the rest: its pow( 1 - NoV, 10.8649 ) is libm's powf on this side and exp2( y * log2( x ) ) in fp32 on A's (oracle/hlsl.h:117) -- two math libraries also on
+            # the CPU. That test's 4e-6 (of the texel's largest component) is a figure of its 16 384 samples, not of the functions: the header on the host, on the dump's own N
+            # and V, is 2.9e-6 from A over those samples and 2.1e-5 over all 131 072 (99.6 % bit for bit both times); with this test's view vectors 8.2e-6 and 2.5e-5.
+            share = float((sh_s[well] == a["shSpecular"][well][:, :3]).mean())
+            print("%-60s %.2f %% bit for bit (at least 98)" % ("shSpecular vs A", 100.0 * share))
+            assert share >= 0.98, share
+            assert_platform(sh_s, a["shSpecular"][:, :3], "shSpecular vs A")
+        else:
+            for got, name in ((col_d, "sgColor"), (col_s, "sgColor")):
+                assert_bits(got, a[name][:, :3], "%s vs A" % name)
+            for got, name in ((sg_d, "sgDiffuse"), (sh_d, "shDiffuse"), (sh_s, "shSpecular"), (dfac, "diffFactor"), (sfac, "specFactor")):
+                assert_platform(got, a[name][:, :3], "%s vs A" % name)
+            assert_platform(sg_s[well], a["sgSpecular"][well][:, :3], "sgSpecular vs A (roughness >= 0.05)")
+    else:
+        N64, V64, r64 = unp[:, :3].astype(np.float64), V.reshape(COUNT, 3).astype(np.float64), rough.astype(np.float64)
+        sg = M.unpack_sh(fed0.astype(np.float64), fed1.astype(np.float64))
+        assert_model(col_d, M.sg_extract_color(sg), 2e-6, "sgColor vs C")
+        assert_model(sg_d, M.sg_resolve_diffuse(sg, N64), 1e-4, "sgDiffuse vs C")
+        assert_model(sh_d, M.sh_resolve_diffuse(sg, N64), 1e-5, "shDiffuse vs C")
+        assert_model(sh_s, M.sh_resolve_specular(sg, N64, V64, r64), 1e-4, "shSpecular vs C")
+        want = M.sg_resolve_specular(sg, N64, V64, r64)
+        assert (r64 >= 0.05).sum() > 0.9 * COUNT  # (the share tests/test_frontend_header.py:257-258 asserts of this input set; roughness >= 0.1 is 1 - 102.5 / 1023 of a uniform 10-bit roughness)
+        assert_model(sg_s[r64 >= 0.2], want[r64 >= 0.2], 1e-3, "sgSpecular vs C (roughness >= 0.2)")
+        assert_model(sg_s[(r64 >= 0.1) & (r64 < 0.2)], want[(r64 >= 0.1) & (r64 < 0.2)], 5e-2, "sgSpecular vs C (0.1 <= roughness < 0.2)")
+        df, sf = M.material_factors(N64, V64, d["albedo"].astype(np.float64), d["Rf0"].astype(np.float64), r64)
+        assert_model(dfac, df, 2e-5, "diffFactor vs C")
+        assert_model(sfac, sf, 2e-5, "specFactor vs C")
+    assert np.all(np.isfinite(sg_s)) and sg_s.min() >= 0.0
+    n64, v64 = unp[:, :3].astype(np.float64), V.reshape(COUNT, 3).astype(np.float64)
+    assert_model(sh_s, M.sh_resolve_specular(M.unpack_sh(fed0.astype(np.float64), fed1.astype(np.float64)), n64, v64, rough.astype(np.float64)), 1e-4, "shSpecular vs C")
+
+    # ---- remodulation and composition: float32 products / sums of the planes above, bit for bit
+    res = run(S.REBLUR_SH, S.RELAX_SH, RES.SG, remodulate=True, want=("composed",), albedo=albedo, rf0=rf0)
+    assert_bits(flat(res["diffuse"]), sg_d * dfac, "remodulated diffuse == resolved * factor")
+    assert_bits(flat(res["specular"]), sg_s * sfac, "remodulated specular == resolved * factor")
+    assert_bits(flat(res["composed"]), sg_d * dfac + sg_s * sfac, "composed == diffuse + specular")
+
+    # ---- REBLUR radiance: fp32 planes vs B (bit for bit), fp16 planes vs C; the hit distance back in world units vs C
+    packed = img(d, "reblurPacked")
+    res = frontend.resolve_outputs(diffuse=dict(mode=S.REBLUR_RADIANCE, in0=be.up(packed)), specular=dict(mode=S.REBLUR_RADIANCE, in0=be.up(f16(packed))), lib=be.lib)
+    assert_bits(flat(res["diffuse"], 4), np.concatenate([d["reblurUnpacked"][:, :3], d["reblurPacked"][:, 3:]], 1), "REBLUR radiance (fp32 plane) vs B reblurUnpacked")
+    assert_model(flat(res["specular"], 4), M.reblur_unpack_radiance_and_norm_hit_dist(f16(packed).reshape(COUNT, 4).astype(np.float64)), 2e-6, "REBLUR radiance (fp16 plane) vs C")
+    res = frontend.resolve_outputs(diffuse=dict(mode=S.REBLUR_RADIANCE, in0=be.up(packed)), specular=dict(mode=S.REBLUR_RADIANCE, in0=be.up(packed)), denormalize_hit_dist=True, **common)
+    nhd, z64 = d["reblurPacked"][:, 3].astype(np.float64), d["viewZ"][:, 0].astype(np.float64)
+    assert_model(flat(res["diffuse"], 4)[:, 3], nhd * M.hit_distance_normalization(z64, HDP, 1.0), 5e-6, "REBLUR_GetHitDist (diffuse: roughness 1) vs C", floor=1.0)
+    assert_model(flat(res["specular"], 4)[:, 3], nhd * M.hit_distance_normalization(z64, HDP, rough.astype(np.float64)), 5e-6, "REBLUR_GetHitDist (specular) vs C", floor=1.0)
+
+    # ---- RELAX radiance and REBLUR occlusion: widened as they are; directional occlusion through the SH resolve vs C
+    relax = f16(img(d, "relaxPacked"))
+    occ = unorm16(img(d, "normHitDist"))
+    res = frontend.resolve_outputs(diffuse=dict(mode=S.REBLUR_OCCLUSION, in0=be.up(occ)), specular=dict(mode=S.RELAX_RADIANCE, in0=be.up(relax)), lib=be.lib)
+    assert_bits(be.down(res["specular"]), relax.astype(f32), "RELAX radiance widened")
+    assert_bits(be.down(res["diffuse"]), occ.view(np.uint16).astype(f32) / f32(65535.0), "REBLUR occlusion widened")
+    dirocc = snorm16(img(d, "dirOcc"))
+    res = frontend.resolve_outputs(diffuse=dict(mode=S.REBLUR_DIRECTIONAL_OCCLUSION, resolve=RES.SH, in0=be.up(dirocc)), **common)
+    t32 = np.maximum(dirocc.reshape(COUNT, 4).astype(f32) / f32(32767.0), f32(-1.0))
+    t = t32.astype(np.float64)
+    sg = {"c0": t[:, 3], "chroma": np.zeros((COUNT, 2)), "normHitDist": t[:, 3], "c1": t[:, :3], "sharpness": np.zeros(COUNT)}
+    assert_model(flat(res["diffuse"]), M.sh_resolve_diffuse(sg, unp[:, :3].astype(np.float64)), 1e-5, "directional occlusion, NRD_SH_ResolveDiffuse vs C")
+    assert_bits(flat(res["diffuse"], 4)[:, 3], t32[:, 3], "directional occlusion .w")
+
+    # ---- SIGMA: x * x exactly
+    for shadow in (unorm8(img(d, "roughness")), unorm8(img(d, "translucency"))):
+        res = frontend.resolve_outputs(shadow=be.up(shadow), lib=be.lib)
+        x = shadow.astype(f32) / f32(255.0)
+        assert_bits(be.down(res["shadow"]), x * x, "SIGMA_BackEnd_UnpackShadow (%d channel)" % (1 if shadow.ndim == 2 else 4))
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_resolve_197x61_with_row_pitches_larger_than_the_rows(backend, dump):
+    """the resolve kernel at a ragged size, every input plane inside a wider allocation, every output inside a wider stamped one: REBLUR radiance (fp32 plane) == B, RELAX radiance
+    and the SIGMA shadow as in the 512 x 256 test, V == the numpy restatement for this size; nothing outside the rects is written"""
+    d, be = dump, Backend(backend)
+    w, h, pad = 197, 61, 11
+    cs = frame_settings(w, h)
+    frustum, rot = camera_constants(cs)
+    viewz = img(d, "viewZ", w=w, h=h)
+    relax, shadow = f16(img(d, "relaxPacked", w=w, h=h)), unorm8(img(d, "roughness", w=w, h=h))
+    ins = dict(diffuse=dict(mode=S.REBLUR_RADIANCE, in0=be.up_pitched(img(d, "reblurPacked", w=w, h=h), pad)), specular=dict(mode=S.RELAX_RADIANCE, in0=be.up_pitched(relax, pad)),
+               shadow=be.up_pitched(shadow, pad), viewz=be.up_pitched(viewz, pad), normal_roughness=be.up_pitched(img(d, d["word"].view(f32), w=w, h=h).view(np.int32), pad))
+    out, bigs = {}, {}
+    for name, shape in (("diffuse", (h, w, 4)), ("specular", (h, w, 4)), ("shadow", (h, w)), ("view_vector", (h, w, 4))):
+        out[name], bigs[name] = be.padded(shape, "float32", pad, 23130)
+    res = frontend.resolve_outputs(common_settings=cs, want=("view_vector",), out=out, lib=be.lib, **ins)
+    want = {"diffuse": img(d, "reblurUnpacked", w=w, h=h), "specular": relax.astype(f32), "shadow": (shadow.astype(f32) / f32(255.0)) * (shadow.astype(f32) / f32(255.0)),
+            "view_vector": np.concatenate([view_vector_numpy(frustum, rot, viewz), np.zeros((h, w, 1), f32)], -1)}
+    for name, t in res.items():
+        assert_bits(be.down(t), want[name], "ragged, pitched resolve: %s" % name)
+        big = be.down(bigs[name])
+        whole = np.full(big.shape, 23130, dtype=f32)
+        whole[:h, :w] = want[name]
+        assert np.array_equal(big.view(np.uint8), whole.view(np.uint8)), "bytes outside the rect were written: %s" % name
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_pack_invalid_values(backend):
+    """what `sanitize = true` of the packers (NRD.hlsli:732-787) and the motion clamp do with NaN and infinities: invalid radiance -> 0, an invalid normalised hit distance -> 0
+    (also in the occlusion mode, which stores that channel alone), infinite motion -> +-65504, NaN motion stays NaN as under the clamp of raytracingdenoiser_amd/synth.py"""
+    be = Backend(backend)
+    h, w = 4, 64
+    nan, inf = f32(np.nan), f32(np.inf)
+    nr = np.zeros((h, w, 4), f32)
+    nr[..., 2], nr[..., 3] = 1.0, 0.5
+    rad = np.ones((h, w, 4), f32)
+    rad[0, 0] = (nan, 1, 1, 1)
+    rad[0, 1] = (1, inf, 1, 1)
+    rad[0, 2] = (1, 1, 1, nan)
+    rad[0, 3] = (1, 1, 1, inf)
+    rad[0, 4] = (-2, 70000, 1, -1)
+    motion = np.zeros((h, w, 4), f32)
+    motion[0, 0] = (nan, inf, -inf, 1e9)
+    dev = dict(nr=be.up(nr), z=be.up(np.full((h, w), 10.0, f32)), rad=be.up(rad), motion=be.up(motion))
+    res = frontend.pack_inputs(dev["nr"], dev["z"], motion=dev["motion"], diffuse=dict(mode=S.REBLUR_OCCLUSION, radiance_hitdist=dev["rad"]),
+                               specular=dict(mode=S.REBLUR_RADIANCE, radiance_hitdist=dev["rad"]), lib=be.lib)
+    occ, spec, mv = (be.down(res[rt][0]) for rt in (R.IN_DIFF_HITDIST, R.IN_SPEC_RADIANCE_HITDIST, R.IN_MV))
+    assert np.array_equal(spec[0, 0, :3], np.zeros(3, np.float16)) and np.array_equal(spec[0, 1, :3], np.zeros(3, np.float16))  # invalid radiance -> black
+    assert spec[0, 2, 3] == 0 and occ[0, 2] == 0  # NaN hit distance -> 0, in both modes
+    assert spec[0, 3, 3] == 1 and occ.view(np.uint16)[0, 3] == 65535  # an infinite hit distance normalises to 1 before the sanitiser sees it
+    assert np.array_equal(spec[0, 4], f16(M.reblur_pack_radiance_and_norm_hit_dist(np.array([0.0, M.NRD_FP16_MAX, 1.0]), np.array(0.0))))  # clamped to [0, FP16_MAX] / [0, 1]
+    assert np.isfinite(spec.astype(f32)).all()
+    assert np.isnan(mv[0, 0, 0]) and mv[0, 0, 1] == np.float16(65504) and mv[0, 0, 2] == np.float16(-65504) and mv[0, 0, 3] == np.float16(65504)
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_pack_demodulates_with_the_material_factors(backend, dump):
+    """albedo + Rf0 + camera: the radiance is divided by NRD_MaterialFactors' factors (raw N and roughness, V of the contract) before it is packed; vs C within one fp16 code"""
+    d, be = dump, Backend(backend)
+    cs = frame_settings(W, H)
+    frustum, rot = camera_constants(cs)
+    ins = pack_inputs_of(d, W, H)
+    V = view_vector_numpy(frustum, rot, ins["viewz"]).reshape(COUNT, 3).astype(np.float64)
+    df, sf = M.material_factors(d["N"].astype(np.float64), V, d["albedo"].astype(np.float64), d["Rf0"].astype(np.float64), d["roughness"][:, 0].astype(np.float64))
+    sig = dict(mode=S.RELAX_RADIANCE, radiance_hitdist=be.up(ins["rad"]))
+    res = frontend.pack_inputs(be.up(ins["nr"]), be.up(ins["viewz"]), diffuse=sig, specular=sig, albedo=be.up(ins["albedo"]), rf0=be.up(img(d, "Rf0", np.zeros((COUNT, 1), f32))),
+                               common_settings=cs, lib=be.lib)
+    hit = d["hitDist"].astype(np.float64)
+    for rt, fac in ((R.IN_DIFF_RADIANCE_HITDIST, df), (R.IN_SPEC_RADIANCE_HITDIST, sf)):
+        want = np.concatenate([np.clip(d["radiance"].astype(np.float64) / fac, 0.0, M.NRD_FP16_MAX), hit], 1)
+        assert_codes(be.down(res[rt][0]).reshape(COUNT, 4), f16(want), "%s demodulated vs C" % rt.name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------- 5. end to end (GPU)
+def _raw_inputs(frame, cuda=True):
+    raw = frame["raw"]
+    t = (lambda x: x.cuda().contiguous()) if cuda else (lambda x: x.contiguous())
+    return dict(nr=t(torch.cat([raw["normal"], raw["roughness"].unsqueeze(-1)], -1)), viewz=t(frame["viewz"]), material=t(raw["material_id"]), motion=t(frame["mv"].float()),
+                diff=t(torch.cat([raw["diff_radiance"], raw["diff_hit_dist"].unsqueeze(-1)], -1)), diff_dir=t(torch.cat([raw["diff_direction"], torch.zeros_like(raw["roughness"]).unsqueeze(-1)], -1)),
+                spec=t(torch.cat([raw["spec_radiance"], raw["spec_hit_dist"].unsqueeze(-1)], -1)), spec_dir=t(torch.cat([raw["spec_direction"], torch.zeros_like(raw["roughness"]).unsqueeze(-1)], -1)))
+
+
+def _pack_frame(ins, mode, out=None):
+    return frontend.pack_inputs(ins["nr"], ins["viewz"], material_id=ins["material"], motion=ins["motion"], diffuse=dict(mode=mode, radiance_hitdist=ins["diff"], direction=ins["diff_dir"]),
+                                specular=dict(mode=mode, radiance_hitdist=ins["spec"], direction=ins["spec_dir"]), hit_dist_params=HDP, out=out)
+
+
+E2E = {"REBLUR_DIFFUSE_SPECULAR": (S.REBLUR_RADIANCE, {R.IN_DIFF_RADIANCE_HITDIST: "diff", R.IN_SPEC_RADIANCE_HITDIST: "spec"}),
+       "RELAX_DIFFUSE_SPECULAR_SH": (S.RELAX_SH, {R.IN_DIFF_SH0: "diff_relax", R.IN_DIFF_SH1: "diff_relax_sh1", R.IN_SPEC_SH0: "spec_relax", R.IN_SPEC_SH1: "spec_relax_sh1"})}
+
+
+def _expected_packed(name, frame):
+    """expectation C of the packed signal planes of a synth frame, from its raw values (float64)"""
+    raw = {k: v.numpy().astype(np.float64) for k, v in frame["raw"].items()}
+    z = frame["viewz"].numpy().astype(np.float64)
+    out = {}
+    for which, rough in (("diff", np.ones_like(z)), ("spec", raw["roughness"])):
+        rad, hit, dirn = raw[which + "_radiance"], raw[which + "_hit_dist"], raw[which + "_direction"]
+        if name.startswith("REBLUR"):
+            out[which] = M.reblur_pack_radiance_and_norm_hit_dist(rad, M.reblur_get_norm_hit_dist(hit, z, HDP, rough))
+        else:
+            out[which + "_relax"], out[which + "_relax_sh1"] = M.relax_pack_sh(rad, hit, dirn)
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(E2E))
+def test_end_to_end_kernel_packed_planes_denoise_like_any_others(name):
+    """4 frames of the synthetic sequence from their RAW fp32 values: pack kernel -> executor -> resolve kernel. The packed planes meet expectation C; downloaded and fed to the CPU
+    oracle they give outputs the executor's are bit-identical to; the resolved outputs are what the model gives for the executor's OUT_* planes; and the same sequence with the
+    executor in graph mode and the pack / resolve launches captured by torch.cuda.graph gives identical bytes."""
+    from raytracingdenoiser_amd.executor import HipExecutor
+
+    w, h, frames = 192, 128, 4
+    mode, keys = E2E[name]
+    seq = [synth.render_frame(w, h, f, want=tuple(parity.DENOISERS[name][1]) + ("raw",)) for f in range(frames)]
+    prev = oracle_driver.set_ieee_mode(False)
+    try:
+        ora = parity.OracleRun(name, w, h)
+        inst = api.Instance([(0, parity.DENOISERS[name][0])])
+        ex = HipExecutor(inst, w, h)
+        outs = {rt: (torch.zeros((h, w, ch), dtype=dtype, device="cuda"), fmt) for rt, dtype, ch, fmt in parity.output_planes(name, w, h)}
+        for rt, (t, fmt) in outs.items():
+            ex.bind(rt, t, fmt)
+        eager = []
+        for f, frame in enumerate(seq):
+            cs = lambda: parity.common_settings(frame["camera"], seq[max(f - 1, 0)]["camera"], w, h, f)
+            packed = _pack_frame(_raw_inputs(frame), mode)
+            host = {rt: t.cpu().numpy() for rt, (t, fmt) in packed.items()}
+            # the G-buffer: what the scene generator packs itself (written without NRD.hip.h)
+            assert_bits(host[R.IN_NORMAL_ROUGHNESS], frame["normal_roughness"].numpy(), "frame %d IN_NORMAL_ROUGHNESS == synth" % f)
+            assert_bits(host[R.IN_VIEWZ], frame["viewz"].numpy(), "frame %d IN_VIEWZ" % f)
+            assert_bits(host[R.IN_MV], frame["mv"].numpy(), "frame %d IN_MV" % f)
+            want = _expected_packed(name, frame)
+            for rt, key in keys.items():
+                assert_codes(host[rt], f16(want[key]), "frame %d %s vs C" % (f, rt.name))
+            # the very planes the kernel packed, through the oracle and through the executor
+            fed = dict(frame, normal_roughness=packed[R.IN_NORMAL_ROUGHNESS][0].cpu(), viewz=packed[R.IN_VIEWZ][0].cpu(), mv=packed[R.IN_MV][0].cpu(), **{key: packed[rt][0].cpu() for rt, key in keys.items()})
+            ora.step(fed, cs(), parity.denoiser_settings(name, frame))
+            ex.bind_packed(packed)
+            assert inst.set_denoiser_settings(0, parity.denoiser_settings(name, frame)) == api.Result.SUCCESS
+            assert inst.set_common_settings(cs()) == api.Result.SUCCESS
+            ex.denoise()
+            resolved = ex.resolve(diffuse_mode=mode, specular_mode=mode, resolve=RES.SG_EXTRACT_COLOR)
+            torch.cuda.synchronize()
+            for rt, (t, fmt) in outs.items():
+                assert_bits(t.cpu().numpy(), ora.outs[rt][0], "frame %d %s: executor on kernel-packed planes == oracle" % (f, rt.name))
+            slots = {which: frontend.signal_slots(which, mode, "OUT") for which in ("diffuse", "specular")}
+            for which, (s0, s1) in slots.items():
+                o0 = outs[s0][0].cpu().numpy().reshape(-1, 4).astype(np.float64)
+                got = resolved[which].cpu().numpy().reshape(-1, 4)
+                if name.startswith("REBLUR"):
+                    assert_model(got, M.reblur_unpack_radiance_and_norm_hit_dist(o0), 2e-6, "frame %d resolved %s vs C" % (f, which))
+                else:
+                    sg = M.unpack_sh(o0, outs[s1][0].cpu().numpy().reshape(-1, 4).astype(np.float64))
+                    assert_model(got[:, :3], M.sg_extract_color(sg), 2e-6, "frame %d resolved %s (NRD_SG_ExtractColor) vs C" % (f, which))
+                    assert_bits(got[:, 3], o0[:, 3].astype(f32), "frame %d resolved %s hit distance" % (f, which))
+            eager.append(({rt: t.cpu().numpy().copy() for rt, (t, fmt) in outs.items()}, {k: v.cpu().numpy().copy() for k, v in resolved.items()}, host))
+        ex.destroy()
+
+        # ---- once more: executor in graph mode, pack and resolve captured by torch.cuda.graph (default queues, nothing else set)
+        inst = api.Instance([(0, parity.DENOISERS[name][0])])
+        ex = HipExecutor(inst, w, h)
+        ex.set_graph_mode(True)
+        for rt, (t, fmt) in outs.items():
+            t.zero_()
+            ex.bind(rt, t, fmt)
+        static = _raw_inputs(seq[0])
+        packed = _pack_frame(static, mode)  # allocates the packed planes (and warms the launch path up) outside the capture
+        ex.bind_packed(packed)
+        resolved = ex.resolve(diffuse_mode=mode, specular_mode=mode, resolve=RES.SG_EXTRACT_COLOR)
+        torch.cuda.synchronize()
+        g_pack, g_resolve = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g_pack):
+            _pack_frame(static, mode, out=packed)
+        with torch.cuda.graph(g_resolve):
+            ex.resolve(diffuse_mode=mode, specular_mode=mode, resolve=RES.SG_EXTRACT_COLOR, out=resolved, stream=torch.cuda.current_stream())
+        for f, frame in enumerate(seq):
+            for k, v in _raw_inputs(frame).items():
+                static[k].copy_(v)
+            g_pack.replay()
+            assert inst.set_denoiser_settings(0, parity.denoiser_settings(name, frame)) == api.Result.SUCCESS
+            assert inst.set_common_settings(parity.common_settings(frame["camera"], seq[max(f - 1, 0)]["camera"], w, h, f)) == api.Result.SUCCESS
+            ex.denoise()
+            g_resolve.replay()
+            torch.cuda.synchronize()
+            want_outs, want_resolved, want_packed = eager[f]
+            for rt, (t, fmt) in packed.items():
+                assert_bits(t.cpu().numpy(), want_packed[rt], "graph frame %d %s == eager" % (f, rt.name))
+            for rt, (t, fmt) in outs.items():
+                assert_bits(t.cpu().numpy(), want_outs[rt], "graph frame %d %s == eager" % (f, rt.name))
+            for k, v in resolved.items():
+                assert_bits(v.cpu().numpy(), want_resolved[k], "graph frame %d resolved %s == eager" % (f, k))
+        assert ex.graph_stats()[0] >= frames
+        ex.destroy()
+    finally:
+        oracle_driver.set_ieee_mode(prev)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------- 6. another encoding (GPU, child process)
+ENCODING = (4, 2)  # RGBA16_SNORM normals (64-bit texels), square-root roughness: built by build() (raytracingdenoiser_amd/build.py TESTED_ENCODINGS)
+
+
+def encoding_case():
+    """runs in a child process whose environment selects the encoding (as tests/test_encodings.py does): the IN_NORMAL_ROUGHNESS texels of the pack kernel, all 64 bits, bit for bit
+    against include/NRD.hip.h evaluated on the host for this encoding (tests/cpp/pack_texels.hip; the low words also against tests/cpp/frontend_check's dump), and within one code
+    of the scene generator's packer, which does not include the header. (The issue names the NRD_FrontEndProbe.cs of this encoding's oracle/_ref as the expectation: the
+    per-encoding build of oracle/ref holds one denoiser per family and no probe, so that comparison does not exist; the header on the host is what the probe test of the default
+    encoding, tests/test_frontend_header.py, holds bit for bit against the reference text.)"""
+    assert (api.NORMAL_ENCODING, api.ROUGHNESS_ENCODING) == ENCODING
+    TFH._build()
+    path = os.path.join(os.path.dirname(TFH.EXE), "pack_resolve_dump%s.bin" % api.ENCODING_SUFFIX)
+    r = subprocess.run([TFH.EXE, "--dump-host", path, str(COUNT)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    d = TFH._load_dump(path, COUNT)
+    os.remove(path)
+    nr, z = torch.from_numpy(img(d, "N", "roughness")).cuda(), torch.from_numpy(img(d, "viewZ")).cuda()
+    packed = frontend.pack_inputs(nr, z, material_id=torch.from_numpy(img(d, "materialID_in")).cuda())
+    t, fmt = packed[R.IN_NORMAL_ROUGHNESS]
+    assert fmt == F[api.NORMAL_ROUGHNESS_FORMAT_NAME] == F.RGBA16_SNORM and t.dtype == torch.int16 and tuple(t.shape) == (H, W, 4)
+    got = t.cpu().numpy()
+    # the whole texel, bit for bit: include/NRD.hip.h on the host, compiled with this encoding's defines (tests/cpp/pack_texels.hip), over the same inputs
+    exe = os.path.join(os.path.dirname(TFH.EXE), "pack_texels" + api.ENCODING_SUFFIX)
+    subprocess.run([TFH.HIPCC, "-std=c++17", "-O2", "-ffp-contract=off", "--offload-arch=gfx950", "-DNRD_NORMAL_ENCODING=%d" % api.NORMAL_ENCODING, "-DNRD_ROUGHNESS_ENCODING=%d" % api.ROUGHNESS_ENCODING,
+                    "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "pack_texels.hip"), "-o", exe], check=True, capture_output=True, text=True)
+    rows, texels = exe + ".in", exe + ".out"
+    np.concatenate([d["N"], d["roughness"], d["materialID_in"]], 1).astype(f32).tofile(rows)
+    r = subprocess.run([exe, rows, texels], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "packed %d texels of 64 bits" % COUNT in r.stdout, r.stdout + r.stderr
+    want = np.fromfile(texels, dtype=np.uint64).view(np.int16).reshape(H, W, 4)
+    os.remove(rows), os.remove(texels)
+    assert_bits(got, want, "IN_NORMAL_ROUGHNESS (RGBA16_SNORM, sqrt roughness) vs NRD.hip.h on the host, all 64 bits")
+    assert_bits(np.ascontiguousarray(got[..., :2]).view(np.uint32)[..., 0], img(d, d["word"].view(f32)).view(np.uint32), "IN_NORMAL_ROUGHNESS low words vs B of the encoding")
+    # the scene generator's packer (torch, written without NRD.hip.h; its CPU square root is not always correctly rounded): one code of the format at most
+    synth_texels = synth.pack_normal_roughness(torch.from_numpy(img(d, "N")), torch.from_numpy(img(d, "roughness")), torch.from_numpy(img(d, "materialID_in"))).numpy()
+    assert_codes(got, synth_texels, "IN_NORMAL_ROUGHNESS vs the scene generator's packer")
+    assert np.mean(got == synth_texels) > 0.999
+    print("encoding_case OK")
+
+
+@pytest.mark.gpu
+def test_pack_in_another_g_buffer_encoding():
+    env = dict(os.environ, NRD_NORMAL_ENCODING=str(ENCODING[0]), NRD_ROUGHNESS_ENCODING=str(ENCODING[1]))
+    env.pop("NRD_HIP_LIBRARY", None)
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_pack_resolve as T; T.encoding_case()" % (ROOT, os.path.join(ROOT, "tests"))
+    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "encoding_case OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

@@ -1,0 +1,157 @@
+"""Times the front-end pack and back-end resolve kernels (include/NRDHip.h nrdHipPackInputs / nrdHipResolveOutputs) for the REBLUR_DIFFUSE_SPECULAR plane set and holds them
+against (c) the same packing done with the torch packers of raytracingdenoiser_amd/synth.py -- the only path there was before the kernels -- and (d) the copy bandwidth the
+same device delivers (nrdHipMeasureCopyBandwidth). Device events around `--reps` back-to-back launches after `--warmup` launches; the bytes are counted from the plane formats.
+Also records what the compiler made of the kernels (VGPRs, waves per SIMD, scratch, 16-byte loads) from a gfx950 assembly listing (tools/isa_stats.py).
+usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only]"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+
+import isa_stats  # noqa: E402
+from raytracingdenoiser_amd import build as B  # noqa: E402
+
+SRC = os.path.join(B.CSRC, "hip", "kernels_frontend.hip")
+# bytes per pixel of the timed plane sets, from the formats
+PACK_READ = {"normal_roughness RGBA32_SFLOAT": 16, "viewZ R32_SFLOAT": 4, "motion RGBA32_SFLOAT": 16, "diffuse radiance_hitdist RGBA32_SFLOAT": 16, "specular radiance_hitdist RGBA32_SFLOAT": 16}
+PACK_WRITE = {"IN_NORMAL_ROUGHNESS": 4, "IN_VIEWZ R32_SFLOAT": 4, "IN_MV RGBA16_SFLOAT": 8, "IN_DIFF_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "IN_SPEC_RADIANCE_HITDIST RGBA16_SFLOAT": 8}
+RESOLVE_READ = {"OUT_DIFF_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "OUT_SPEC_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "IN_NORMAL_ROUGHNESS": 4, "IN_VIEWZ R32_SFLOAT": 4}
+RESOLVE_WRITE = {"diffuse RGBA32_SFLOAT": 16, "specular RGBA32_SFLOAT": 16}
+
+
+def isa():
+    """static facts about the two kernels from a gfx950 listing of the translation unit, compiled with the product's flags"""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_frontend.s")
+        flags = [f for f in B._flags(SRC) if f not in ("-x", "hip")]
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+    out = {}
+    for mangled, s in stats.items():
+        name = "pack" if "PackInputsKernel" in mangled else "resolve" if "ResolveOutputsKernel" in mangled else None
+        if name:
+            c = s["counter"]
+            out[name] = {"vgprs": s["vgpr"], "waves_per_simd": s["occ"], "scratch_bytes": s["scratch"], "lds_bytes": s["ldsb"], "valu": s["valu"], "salu": s["salu"], "vmem": s["vmem"],
+                         "global_load_dwordx4": c.get("global_load_dwordx4", 0), "global_load_dwordx2": c.get("global_load_dwordx2", 0), "global_store_dwordx4": c.get("global_store_dwordx4", 0),
+                         "global_store_dwordx2": c.get("global_store_dwordx2", 0), "v_div_scale_f32": c.get("v_div_scale_f32", 0), "transcendental": s["trans"]}
+    assert set(out) == {"pack", "resolve"}, list(stats)
+    return out
+
+
+def synth_pack(raw, synth, torch):
+    """the packing of synth.render_frame for REBLUR_DIFFUSE_SPECULAR on the raw values: its packers, elementwise torch operations with fp32 intermediates"""
+    out = {"normal_roughness": synth.pack_normal_roughness(raw["normal"], raw["roughness"], raw["material"]).contiguous(), "viewz": raw["viewz"].clone(),
+           "mv": raw["motion"].clamp(-synth.FP16_MAX, synth.FP16_MAX).to(torch.float16).contiguous()}
+    for which, rough in (("diff", torch.ones_like(raw["roughness"])), ("spec", raw["roughness"])):
+        rad = raw[which][..., :3].clamp(0.0, synth.FP16_MAX)
+        nhd = synth._norm_hit_dist(raw[which][..., 3], raw["viewz"], rough)
+        out[which] = torch.cat([synth._ycocg(rad), nhd.unsqueeze(-1)], -1).clamp(-synth.FP16_MAX, synth.FP16_MAX).to(torch.float16).contiguous()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=2560)
+    ap.add_argument("--height", type=int, default=1440)
+    ap.add_argument("--reps", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.json"))
+    ap.add_argument("--isa-only", action="store_true", help="no GPU needed: print the static facts and leave")
+    args = ap.parse_args()
+    result = {"isa": isa()}
+    if args.isa_only:  # the static half of the record: nothing here is a time
+        print(json.dumps(result))
+        return
+    import torch
+
+    from raytracingdenoiser_amd import api, frontend, synth
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    w, h = args.width, args.height
+    px = w * h
+    g = torch.Generator(device="cuda").manual_seed(7)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    n = rand(h, w, 3) * 2.0 - 1.0
+    n = n / n.norm(dim=-1, keepdim=True).clamp_min(1e-6)
+    raw = {"normal": n, "roughness": rand(h, w), "material": torch.floor(rand(h, w) * 4.0), "viewz": 0.5 + rand(h, w) * 100.0, "motion": rand(h, w, 4) - 0.5,
+           "diff": rand(h, w, 4) * torch.tensor([4.0, 3.0, 5.0, 30.0], device="cuda"), "spec": rand(h, w, 4) * torch.tensor([4.0, 3.0, 5.0, 30.0], device="cuda")}
+    nr = torch.cat([raw["normal"], raw["roughness"].unsqueeze(-1)], -1).contiguous()
+    sig = lambda t: dict(mode=frontend.SignalMode.REBLUR_RADIANCE, radiance_hitdist=t)
+
+    lib = api.load_library()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    # the descriptors are built once; the timed loops call the C-ABI itself (ctypes, a few microseconds), not the Python wrappers that assemble a descriptor per call
+    packed, pack_desc, keep_pack = frontend.describe_pack(nr, raw["viewz"], material_id=raw["material"], motion=raw["motion"], diffuse=sig(raw["diff"]), specular=sig(raw["spec"]))
+
+    def pack():
+        assert lib.nrdHipPackInputs(C.byref(pack_desc), stream) == 0
+
+    pack()
+    R = api.ResourceType
+    resolve_args = dict(diffuse=dict(mode=frontend.SignalMode.REBLUR_RADIANCE, in0=packed[R.IN_DIFF_RADIANCE_HITDIST][0]),
+                        specular=dict(mode=frontend.SignalMode.REBLUR_RADIANCE, in0=packed[R.IN_SPEC_RADIANCE_HITDIST][0]), normal_roughness=packed[R.IN_NORMAL_ROUGHNESS][0],
+                        viewz=packed[R.IN_VIEWZ][0], denormalize_hit_dist=True)
+    resolved, resolve_desc, keep_resolve = frontend.describe_resolve(**resolve_args)
+
+    def resolve():
+        assert lib.nrdHipResolveOutputs(C.byref(resolve_desc), stream) == 0
+
+    resolve()
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(args.reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / args.reps
+
+    # alternate the measurements twice: the spread between the rounds says how much a difference means
+    rounds = []
+    for _ in range(2):
+        rounds.append({"pack_ms": timed(pack), "resolve_ms": timed(resolve), "synth_pack_ms": timed(lambda: synth_pack(raw, synth, torch)),
+                       "pack_through_python_wrapper_ms": timed(lambda: frontend.pack_inputs(nr, raw["viewz"], material_id=raw["material"], motion=raw["motion"], diffuse=sig(raw["diff"]),
+                                                                                           specular=sig(raw["spec"]), out=packed))})
+    best = {k: min(r[k] for r in rounds) for k in rounds[0]}
+    # how fast the host can enqueue: the same call on a 64 x 4 frame, where the kernel is one workgroup -- a window bounded by this rate would measure the host, not the kernel
+    tiny = torch.zeros(4, 64, 4, device="cuda")
+    _, tiny_desc, keep_tiny = frontend.describe_pack(tiny, tiny[..., 0].contiguous(), diffuse=sig(tiny), specular=sig(tiny))
+    enqueue_ms = timed(lambda: lib.nrdHipPackInputs(C.byref(tiny_desc), stream))
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(gbps)) == 0
+    pack_bytes, resolve_bytes = sum(PACK_READ.values()) + sum(PACK_WRITE.values()), sum(RESOLVE_READ.values()) + sum(RESOLVE_WRITE.values())
+    rate = lambda bytes_per_px, ms: bytes_per_px * px / (ms * 1e-3) / 1e9
+    result.update({
+        "device": torch.cuda.get_device_name(0), "width": w, "height": h, "reps": args.reps, "warmup": args.warmup, "rounds": rounds,
+        "pack": {"ms": best["pack_ms"], "read_bytes_per_pixel": PACK_READ, "write_bytes_per_pixel": PACK_WRITE, "bytes_per_pixel": pack_bytes, "gigabytes_per_second": rate(pack_bytes, best["pack_ms"])},
+        "resolve": {"ms": best["resolve_ms"], "read_bytes_per_pixel": RESOLVE_READ, "write_bytes_per_pixel": RESOLVE_WRITE, "bytes_per_pixel": resolve_bytes,
+                    "gigabytes_per_second": rate(resolve_bytes, best["resolve_ms"])},
+        "synth_pack": {"ms": best["synth_pack_ms"], "what": "raytracingdenoiser_amd/synth.py packers (pack_normal_roughness, _ycocg, _norm_hit_dist, fp16 casts) on CUDA tensors, same planes"},
+        "copy_gigabytes_per_second": gbps.value,
+        "times_are": "device events around --reps back-to-back launches through the C-ABI, per launch; enqueue_floor_ms is the same loop on a 64 x 4 frame",
+        "enqueue_floor_ms": enqueue_ms, "pack_through_python_wrapper_ms": best["pack_through_python_wrapper_ms"],
+        "pack_over_synth_pack": best["pack_ms"] / best["synth_pack_ms"],
+        "pack_fraction_of_copy_rate": rate(pack_bytes, best["pack_ms"]) / gbps.value,
+        "resolve_fraction_of_copy_rate": rate(resolve_bytes, best["resolve_ms"]) / gbps.value,
+    })
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fp:
+        json.dump(result, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps({k: v for k, v in result.items() if k not in ("rounds", "isa")}))
+    assert best["pack_ms"] < best["synth_pack_ms"], "the pack kernel must beat the torch packers it replaces"
+
+
+if __name__ == "__main__":
+    main()
