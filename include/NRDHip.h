@@ -283,6 +283,37 @@ uint32_t nrdHipPackInputs(const NrdHipFrontEndDesc* desc, void* hipStream);
 uint32_t nrdHipResolveOutputs(const NrdHipBackEndDesc* desc, void* hipStream);
 const char* nrdHipGetLastFrontEndError(void);
 
+// The same two calls with an options struct next to the descriptor. options == NULL or an all-zero struct is exactly the call above: the same kernel, the same bytes.
+// The contract is the one above: validated before the first HIP call, nothing enqueued on an error, no allocation, no synchronisation, capturable into a graph,
+// errors through nrdHipGetLastFrontEndError. (In all four calls the camera of commonSettings is read when the call is made: a captured call replays with the camera it was captured with.)
+//
+// Checkerboarded noisy inputs (reference NRDSettings.h:35-44 "checkerboardMode"; every REBLUR / RELAX pass here implements it). All planes keep the full size. With
+// BLACK the diffuse signal lives in cell 0 and the specular one in cell 1, with WHITE the opposite; pixel (x, y) carries a signal's data when
+// ( ( x ^ y ) ^ frameIndex ) & 1 == cell (nrdmath.h CheckerBoard). Only those pixels of the signal's fp32 planes (radianceHitDist, direction) are read -- the others may
+// hold anything, NaN included -- and the texel the plain call would write for that pixel (its own viewZ, roughness and material factor) goes to column x >> 1 of the same
+// row of out0 / out1. No other byte of out0 / out1 is written: not the right half, and not the last column of the left half in the rows where, at an odd width, it has no
+// source pixel. The G-buffer outputs are unaffected. checkerboardMode > 2, or a mode other than OFF without a diffuse or specular signal -> INVALID_ARGUMENT.
+typedef struct NrdHipFrontEndOptions {
+    uint32_t checkerboardMode; // nrd::CheckerboardMode: 0 OFF, 1 BLACK, 2 WHITE -- the orientation of the DIFFUSE signal, the specular one is the opposite (Reblur.cpp:318-330, Relax.cpp:88-97)
+    uint32_t frameIndex;       // CommonSettings::frameIndex of the frame the planes are for
+} NrdHipFrontEndOptions;
+uint32_t nrdHipPackInputsEx(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, void* hipStream);
+
+// Re-jittering: step two of the high-quality resolve of an SH denoiser (reference README "IMPROVING OUTPUT QUALITY": SG resolve, re-jitter, remodulation). With
+// reJitter != 0 pixel (x, y) computes
+//   scale = NRD_SG_ReJitter( diffSg, specSg, Rf0, V, roughness, Z, Ze, Zw, Zn, Zs, N, Ne, Nw, Nn, Ns )
+// from the two unpacked SH pairs, Rf0 of the rf0 plane, V of the contract above, Z of IN_VIEWZ, N and the roughness of the IN_NORMAL_ROUGHNESS texel, and the Z and N of the
+// neighbours e = ( x + 1, y ), w = ( x - 1, y ), n = ( x, y + 1 ), s = ( x, y - 1 ); a neighbour outside the plane has N = 0 and Z = 0, with which the function
+// returns ( 1, 1 ): border pixels are exactly unscaled. The colour written is ( resolved.rgb * scale.x or .y ) * factor, in that order, the factor only with remodulate; .w and
+// outComposed (the sum of the two colours as written) are as without it. Needs both signals in an SH mode with resolve SH or SG (else INVALID_ARGUMENT), and
+// normalRoughness, viewZ, rf0 and commonSettings (INVALID_ARGUMENT naming the one that is missing); albedo only with remodulation or the factor outputs.
+// outReJitterScale in another format -> UNSUPPORTED; outReJitterScale without reJitter -> INVALID_ARGUMENT.
+typedef struct NrdHipBackEndOptions {
+    uint32_t reJitter;                // != 0: multiply both resolved colours by NRD_SG_ReJitter
+    NrdHipPlaneDesc outReJitterScale; // out, RG32_SFLOAT, optional: the two factors (x diffuse, y specular)
+} NrdHipBackEndOptions;
+uint32_t nrdHipResolveOutputsEx(const NrdHipBackEndDesc* desc, const NrdHipBackEndOptions* options, void* hipStream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,9 @@ public:
     // into the planes "Denoise" consumes, resolve its outputs into linear radiance. Asynchronous; false + GetLastFrontEndError() on an invalid descriptor.
     inline bool PackInputs(const NrdHipFrontEndDesc& desc) { return nrdHipPackInputs(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
     inline bool ResolveOutputs(const NrdHipBackEndDesc& desc) { return nrdHipResolveOutputs(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
+    // with options (nrdHipPackInputsEx / nrdHipResolveOutputsEx): checkerboarded noisy inputs, NRD_SG_ReJitter between the resolve and the remodulation
+    inline bool PackInputs(const NrdHipFrontEndDesc& desc, const NrdHipFrontEndOptions& options) { return nrdHipPackInputsEx(&desc, &options, m_Stream) == (uint32_t)Result::SUCCESS; }
+    inline bool ResolveOutputs(const NrdHipBackEndDesc& desc, const NrdHipBackEndOptions& options) { return nrdHipResolveOutputsEx(&desc, &options, m_Stream) == (uint32_t)Result::SUCCESS; }
     inline const char* GetLastFrontEndError() const { return nrdHipGetLastFrontEndError(); }
 
     // Assumes that no work of this integration is in flight on the stream

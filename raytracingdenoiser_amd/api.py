@@ -298,7 +298,16 @@ class HipBackEndDesc(C.Structure):  # include/NRDHip.h NrdHipBackEndDesc
                 ("outSpecFactor", HipPlaneDesc)]
 
 
+class HipFrontEndOptions(C.Structure):  # include/NRDHip.h NrdHipFrontEndOptions
+    _fields_ = [("checkerboardMode", C.c_uint32), ("frameIndex", C.c_uint32)]
+
+
+class HipBackEndOptions(C.Structure):  # include/NRDHip.h NrdHipBackEndOptions
+    _fields_ = [("reJitter", C.c_uint32), ("outReJitterScale", HipPlaneDesc)]
+
+
 assert C.sizeof(HipPlaneDesc) == 24 and C.sizeof(HipFrontEndSignal) == 104 and C.sizeof(HipFrontEndDesc) == 552 and C.sizeof(HipBackEndSignal) == 80 and C.sizeof(HipBackEndDesc) == 432
+assert C.sizeof(HipFrontEndOptions) == 8 and C.sizeof(HipBackEndOptions) == 32
 
 
 # ----------------------------------------------------------------------------------------------- library
@@ -321,7 +330,8 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipDenoise", "nrdHipGetPoolMemoryUsage", "nrdHipGetLastError", "nrdHipEvalNumerics", "nrdHipGetArenaSize",
                    "nrdHipCreateExecutorWithArena", "nrdHipSetProfiling", "nrdHipCollectPassTimings", "nrdHipSetOwnedRows", "nrdHipGetDispatchReach",
                    "nrdHipExecuteDispatchRange", "nrdHipPlanHaloExchange", "nrdHipSetGraphMode", "nrdHipGetGraphStats", "nrdHipGetTileFallbackStats", "nrdHipGetNumericsMode", "nrdHipMeasureCopyBandwidth",
-                   "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError"]
+                   "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError",
+                   "nrdHipPackInputsEx", "nrdHipResolveOutputsEx"]
 
 _libs = {}
 
@@ -391,6 +401,8 @@ def load_library(path=None):
     lib.nrdHipPackInputs.argtypes, lib.nrdHipPackInputs.restype = [P(HipFrontEndDesc), C.c_void_p], C.c_uint32
     lib.nrdHipResolveOutputs.argtypes, lib.nrdHipResolveOutputs.restype = [P(HipBackEndDesc), C.c_void_p], C.c_uint32
     lib.nrdHipGetLastFrontEndError.argtypes, lib.nrdHipGetLastFrontEndError.restype = [], C.c_char_p
+    lib.nrdHipPackInputsEx.argtypes, lib.nrdHipPackInputsEx.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), C.c_void_p], C.c_uint32
+    lib.nrdHipResolveOutputsEx.argtypes, lib.nrdHipResolveOutputsEx.restype = [P(HipBackEndDesc), P(HipBackEndOptions), C.c_void_p], C.c_uint32
     _libs[path] = lib
     return lib
 

@@ -1,7 +1,8 @@
 // Front end / back end on the device (include/NRDHip.h nrdHipPackInputs / nrdHipResolveOutputs): the application side of the reference's NRD.hlsli as two
 // fused streaming kernels -- one launch packs a frame's fp32 G-buffer and noisy signals into the planes nrdHipBindResource accepts, one launch turns the
 // denoised OUT_* planes into linear fp32 radiance. One thread per pixel, 64 x 4 workgroups: a wave covers 64 consecutive pixels of one row, so every load
-// and store of a wave is one contiguous segment (16 B per lane for the RGBA32_SFLOAT inputs: global_load_dwordx4).
+// and store of a wave is one contiguous segment (16 B per lane for the RGBA32_SFLOAT inputs: global_load_dwordx4). The calls with options (nrdHipPackInputsEx /
+// nrdHipResolveOutputsEx) launch these very kernels when the options are absent or zero, else one of two more: the checkerboard twin of the pack kernel and the re-jitter kernel.
 //
 // Arithmetic: include/NRD.hip.h and nothing else -- its contract, and the reference text it is pinned to, is unfused IEEE fp32 with correctly rounded
 // division and square root. The product builds its device sources with -ffp-contract=on, hence the pragma below, in front of every include: no statement
@@ -71,8 +72,9 @@ __device__ __forceinline__ float3 ViewVector(const FeCamera& c, int x, int y, in
     return make_float3(-n.x, -n.y, -n.z);
 }
 
+// (x, y): the pixel whose data is packed; the texels go to column xo of its row (xo = x, or x >> 1 of a checkerboarded frame)
 template <bool SPEC>
-__device__ __forceinline__ void PackSignal(uint32_t mode, const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, int x, int y, int w, int h, float viewZ,
+__device__ __forceinline__ void PackSignal(uint32_t mode, const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, int x, int xo, int y, int w, int h, float viewZ,
     float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
     const float4 s = LoadRGBA32F(AsPlane(in, w, h), x, y);
     float3 radiance = Xyz(s);
@@ -88,24 +90,24 @@ __device__ __forceinline__ void PackSignal(uint32_t mode, const FePlane& in, con
     float4 p1;
     switch (mode) { // wave-uniform: a kernel argument
         case NRD_HIP_SIGNAL_REBLUR_RADIANCE:
-            StoreRGBA16F(o0, x, y, REBLUR_FrontEnd_PackRadianceAndNormHitDist(radiance, REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r), true));
+            StoreRGBA16F(o0, xo, y, REBLUR_FrontEnd_PackRadianceAndNormHitDist(radiance, REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r), true));
             break;
         case NRD_HIP_SIGNAL_REBLUR_SH:
-            StoreRGBA16F(o0, x, y, REBLUR_FrontEnd_PackSh(radiance, REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r), direction, p1, true));
-            StoreRGBA16F(o1, x, y, p1);
+            StoreRGBA16F(o0, xo, y, REBLUR_FrontEnd_PackSh(radiance, REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r), direction, p1, true));
+            StoreRGBA16F(o1, xo, y, p1);
             break;
         case NRD_HIP_SIGNAL_REBLUR_OCCLUSION: // the hit distance channel of the radiance packer, sanitised by it (NaN / inf -> 0)
-            StoreR16Unorm(o0, x, y, REBLUR_FrontEnd_PackRadianceAndNormHitDist(make_float3(0.0f, 0.0f, 0.0f), REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r), true).w);
+            StoreR16Unorm(o0, xo, y, REBLUR_FrontEnd_PackRadianceAndNormHitDist(make_float3(0.0f, 0.0f, 0.0f), REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r), true).w);
             break;
         case NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION:
-            StoreRGBA16Snorm(o0, x, y, REBLUR_FrontEnd_PackDirectionalOcclusion(direction, REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r), true));
+            StoreRGBA16Snorm(o0, xo, y, REBLUR_FrontEnd_PackDirectionalOcclusion(direction, REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r), true));
             break;
         case NRD_HIP_SIGNAL_RELAX_RADIANCE:
-            StoreRGBA16F(o0, x, y, RELAX_FrontEnd_PackRadianceAndHitDist(radiance, hitDist, true));
+            StoreRGBA16F(o0, xo, y, RELAX_FrontEnd_PackRadianceAndHitDist(radiance, hitDist, true));
             break;
         case NRD_HIP_SIGNAL_RELAX_SH:
-            StoreRGBA16F(o0, x, y, RELAX_FrontEnd_PackSh(radiance, hitDist, direction, p1, true));
-            StoreRGBA16F(o1, x, y, p1);
+            StoreRGBA16F(o0, xo, y, RELAX_FrontEnd_PackSh(radiance, hitDist, direction, p1, true));
+            StoreRGBA16F(o1, xo, y, p1);
             break;
         default:
             break;
@@ -115,7 +117,11 @@ __device__ __forceinline__ void PackSignal(uint32_t mode, const FePlane& in, con
 // motion is clamped to +-FP16_MAX as raytracingdenoiser_amd/synth.py clamps it: infinities land on the bounds, a NaN stays a NaN (fminf / fmaxf alone would turn it into a bound)
 __device__ __forceinline__ float ClampToHalf(float v) { return isnan(v) ? v : fminf(fmaxf(v, -NRD_FP16_MAX), NRD_FP16_MAX); }
 
-__global__ void __launch_bounds__(256) PackInputsKernel(const PackArgs a) {
+// One pixel of the front end. CHECKERBOARD (nrdHipPackInputsEx, NRDSettings.h:35-44): a pixel carries the data of ONE signal -- the diffuse one where
+// ( ( x ^ y ) ^ frameIndex ) & 1 == diffCell (nrdmath.h CheckerBoard), the specular one elsewhere -- and its texel goes to column x >> 1: the left half of the plane.
+// Only those pixels of a signal's fp32 planes are read and no other texel of its packed planes is written.
+template <bool CHECKERBOARD>
+__device__ __forceinline__ void PackPixel(const PackArgs& a, uint32_t diffCell, uint32_t frameIndex) {
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
     const int w = a.w, h = a.h;
     if (x >= w || y >= h)
@@ -146,10 +152,12 @@ __global__ void __launch_bounds__(256) PackInputsKernel(const PackArgs a) {
         const float3 V = ViewVector(a.camera, x, y, w, h, viewZ);
         NRD_MaterialFactors(N, V, Xyz(LoadRGBA32F(AsPlane(a.albedo, w, h), x, y)), Xyz(LoadRGBA32F(AsPlane(a.rf0, w, h), x, y)), roughness, diffFactor, specFactor);
     }
-    if (a.diffMode)
-        PackSignal<false>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, x, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, diffFactor);
-    if (a.specMode)
-        PackSignal<true>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, x, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, specFactor);
+    const bool diffHere = !CHECKERBOARD || ((((uint32_t)x ^ (uint32_t)y) ^ frameIndex) & 1u) == diffCell;
+    const int xo = CHECKERBOARD ? x >> 1 : x;
+    if (a.diffMode && diffHere)
+        PackSignal<false>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, diffFactor);
+    if (a.specMode && (!CHECKERBOARD || !diffHere))
+        PackSignal<true>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, specFactor);
 
     if (a.outPenumbra.ptr || a.outTranslucency.ptr) {
         const float distanceToOccluder = LoadR32F(AsPlane(a.occluder, w, h), x, y);
@@ -159,6 +167,10 @@ __global__ void __launch_bounds__(256) PackInputsKernel(const PackArgs a) {
             StoreRGBA8Unorm(AsPlane(a.outTranslucency, w, h), x, y, SIGMA_FrontEnd_PackTranslucency(distanceToOccluder, Xyz(LoadRGBA32F(AsPlane(a.translucency, w, h), x, y))));
     }
 }
+
+__global__ void __launch_bounds__(256) PackInputsKernel(const PackArgs a) { PackPixel<false>(a, 0u, 0u); }
+
+__global__ void __launch_bounds__(256) PackCheckerboardKernel(const PackArgs a, const uint32_t diffCell, const uint32_t frameIndex) { PackPixel<true>(a, diffCell, frameIndex); }
 
 __device__ __forceinline__ float4 LoadSignalTexel(const FePlane& p, bool wide, int x, int y, int w, int h) {
     return wide ? LoadRGBA32F(AsPlane(p, w, h), x, y) : LoadRGBA16F(AsPlane(p, w, h), x, y);
@@ -242,6 +254,115 @@ __global__ void __launch_bounds__(256) ResolveOutputsKernel(const ResolveArgs a)
     if (a.specMode)
         spec = ResolveSignal<true>(a.specMode, a.specResolve, a.specWide != 0u, a.specIn0, a.specIn1, a.specOut, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
             a.remodulate != 0u, specFactor);
+    if (a.outComposed.ptr)
+        StoreRGBA32F(AsPlane(a.outComposed, w, h), x, y, make_float4(diff.x + spec.x, diff.y + spec.y, diff.z + spec.z, 0.0f));
+    if (a.outShadow.ptr) {
+        if (a.shadowIsRGBA)
+            StoreRGBA32F(AsPlane(a.outShadow, w, h), x, y, SIGMA_BackEnd_UnpackShadow(LoadRGBA8Unorm(AsPlane(a.shadow, w, h), x, y)));
+        else
+            StoreR32F(AsPlane(a.outShadow, w, h), x, y, SIGMA_BackEnd_UnpackShadow(LoadR8Unorm(AsPlane(a.shadow, w, h), x, y)));
+    }
+}
+
+// ---- the high-quality resolve of an SH denoiser (nrdHipResolveOutputsEx with reJitter): SG / SH resolve, NRD_SG_ReJitter, remodulation ---------------
+// NRD_SG_ReJitter is the one stencil of the back end: it wants viewZ and the decoded normal of the four edge neighbours. NRD_REJITTER_TILE = 1 (shipped; DESIGN.md
+// section 3.4 has the A/B): a workgroup stages the decoded N.xyz and Z of its 64 x 4 pixels plus a one-texel halo in LDS -- every lane decodes its own texel, the
+// first 140 lanes one halo texel more: 396 / 256 = 1.55 decodes per pixel -- and reads its neighbours from there. Rows of 66 float4: the 64 lanes of a wave (one row of
+// the tile) read 64 consecutive 16-byte texels, at any of the three column offsets and three rows -- a conflict-free ds_read_b128. NRD_REJITTER_TILE = 0 (A/B builds): every lane loads
+// and decodes its four neighbour texels itself, 5 decodes per pixel. Same decoded values, same function: the two forms give the same bits.
+// Texels outside the plane read as zeros (N = 0, Z = 0), with which NRD_SG_ReJitter returns (1, 1): border pixels are exactly unscaled.
+#ifndef NRD_REJITTER_TILE
+#define NRD_REJITTER_TILE 1
+#endif
+constexpr int kReJitterTileW = 64, kReJitterTileH = 4; // = the workgroup
+
+struct ReJitterArgs {
+    ResolveArgs r;
+    FePlane outScale;
+};
+
+// decoded N.xyz and Z (.w) of texel (x, y), zeros outside the plane; roughness: that of the texel
+__device__ __forceinline__ float4 LoadNormalAndViewZ(const ResolveArgs& a, int x, int y, float& roughness) {
+    roughness = 0.0f;
+    if ((unsigned)x >= (unsigned)a.w || (unsigned)y >= (unsigned)a.h)
+        return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 nr = NRD_FrontEnd_UnpackNormalAndRoughness(NRD_LoadNormalRoughnessTexel(*TexelPtr<const NRD_NormalRoughnessTexel>(AsPlane(a.normalRoughness, a.w, a.h), x, y)));
+    roughness = nr.w;
+    return make_float4(nr.x, nr.y, nr.z, LoadR32F(AsPlane(a.viewZ, a.w, a.h), x, y));
+}
+
+template <bool SPEC>
+__device__ __forceinline__ NRD_SG LoadSg(uint32_t mode, bool wide, const FePlane& in0, const FePlane& in1, int x, int y, int w, int h) {
+    const float4 sh0 = LoadSignalTexel(in0, wide, x, y, w, h), sh1 = LoadSignalTexel(in1, wide, x, y, w, h);
+    return mode == NRD_HIP_SIGNAL_REBLUR_SH ? REBLUR_BackEnd_UnpackSh(sh0, sh1) : RELAX_BackEnd_UnpackSh(sh0, sh1);
+}
+
+// ( resolved.rgb * scale ) * factor, in that order; .w as ResolveSignal writes it
+template <bool SPEC>
+__device__ __forceinline__ float3 StoreReJittered(const ResolveArgs& a, uint32_t mode, uint32_t resolve, const FePlane& out, NRD_SG sg, int x, int y, float viewZ, float3 N, float3 V, float roughness,
+    float scale, float3 factor) {
+    float3 rgb;
+    if (resolve == NRD_HIP_RESOLVE_SH)
+        rgb = SPEC ? NRD_SH_ResolveSpecular(sg, N, V, roughness) : NRD_SH_ResolveDiffuse(sg, N);
+    else
+        rgb = SPEC ? NRD_SG_ResolveSpecular(sg, N, V, roughness) : NRD_SG_ResolveDiffuse(sg, N);
+    float4 c = make_float4(rgb.x * scale, rgb.y * scale, rgb.z * scale, sg.normHitDist);
+    if (a.denormalize && mode == NRD_HIP_SIGNAL_REBLUR_SH)
+        c.w = REBLUR_GetHitDist(c.w, viewZ, a.hitDistParams, SPEC ? roughness : 1.0f);
+    if (a.remodulate)
+        c = make_float4(c.x * factor.x, c.y * factor.y, c.z * factor.z, c.w);
+    StoreRGBA32F(AsPlane(out, a.w, a.h), x, y, c);
+    return Xyz(c);
+}
+
+__global__ void __launch_bounds__(256) ReJitterKernel(const ReJitterArgs args) {
+    const ResolveArgs& a = args.r;
+    const int x = (int)(blockIdx.x * (uint32_t)kReJitterTileW + threadIdx.x), y = (int)(blockIdx.y * (uint32_t)kReJitterTileH + threadIdx.y);
+    const int w = a.w, h = a.h;
+    float roughness, unused;
+    const float4 c = LoadNormalAndViewZ(a, x, y, roughness);
+#if NRD_REJITTER_TILE
+    __shared__ float4 s_Tile[kReJitterTileH + 2][kReJitterTileW + 2];
+    const int tx = (int)threadIdx.x + 1, ty = (int)threadIdx.y + 1;
+    s_Tile[ty][tx] = c;
+    // the halo: the row above, the row below (66 texels each), then the columns left and right (4 each)
+    constexpr int kRow = kReJitterTileW + 2, kHalo = 2 * kRow + 2 * kReJitterTileH;
+    const int j = (int)(threadIdx.y * (uint32_t)kReJitterTileW + threadIdx.x);
+    if (j < kHalo) {
+        const int k = j - 2 * kRow;
+        const int hx = j < kRow ? j : j < 2 * kRow ? j - kRow : k < kReJitterTileH ? 0 : kRow - 1;
+        const int hy = j < kRow ? 0 : j < 2 * kRow ? kReJitterTileH + 1 : (k < kReJitterTileH ? k : k - kReJitterTileH) + 1;
+        s_Tile[hy][hx] = LoadNormalAndViewZ(a, (int)(blockIdx.x * (uint32_t)kReJitterTileW) + hx - 1, (int)(blockIdx.y * (uint32_t)kReJitterTileH) + hy - 1, unused);
+    }
+    __syncthreads();
+    if (x >= w || y >= h)
+        return;
+    const float4 e = LdsFloat4(&s_Tile[ty][tx + 1]), wn = LdsFloat4(&s_Tile[ty][tx - 1]), n = LdsFloat4(&s_Tile[ty + 1][tx]), s = LdsFloat4(&s_Tile[ty - 1][tx]);
+#else
+    if (x >= w || y >= h)
+        return;
+    const float4 e = LoadNormalAndViewZ(a, x + 1, y, unused), wn = LoadNormalAndViewZ(a, x - 1, y, unused), n = LoadNormalAndViewZ(a, x, y + 1, unused), s = LoadNormalAndViewZ(a, x, y - 1, unused);
+#endif
+    const float viewZ = c.w;
+    const float3 N = Xyz(c);
+    const float3 V = ViewVector(a.camera, x, y, w, h, viewZ);
+    if (a.outViewVector.ptr)
+        StoreRGBA32F(AsPlane(a.outViewVector, w, h), x, y, make_float4(V.x, V.y, V.z, 0.0f));
+    const float3 Rf0 = Xyz(LoadRGBA32F(AsPlane(a.rf0, w, h), x, y));
+    float3 diffFactor = make_float3(1.0f, 1.0f, 1.0f), specFactor = diffFactor;
+    if (a.needFactors) {
+        NRD_MaterialFactors(N, V, Xyz(LoadRGBA32F(AsPlane(a.albedo, w, h), x, y)), Rf0, roughness, diffFactor, specFactor);
+        if (a.outDiffFactor.ptr)
+            StoreRGBA32F(AsPlane(a.outDiffFactor, w, h), x, y, make_float4(diffFactor.x, diffFactor.y, diffFactor.z, 0.0f));
+        if (a.outSpecFactor.ptr)
+            StoreRGBA32F(AsPlane(a.outSpecFactor, w, h), x, y, make_float4(specFactor.x, specFactor.y, specFactor.z, 0.0f));
+    }
+    const NRD_SG diffSg = LoadSg<false>(a.diffMode, a.diffWide != 0u, a.diffIn0, a.diffIn1, x, y, w, h), specSg = LoadSg<true>(a.specMode, a.specWide != 0u, a.specIn0, a.specIn1, x, y, w, h);
+    const float2 scale = NRD_SG_ReJitter(diffSg, specSg, Rf0, V, roughness, viewZ, e.w, wn.w, n.w, s.w, N, Xyz(e), Xyz(wn), Xyz(n), Xyz(s));
+    if (args.outScale.ptr)
+        *TexelPtr<float2>(AsPlane(args.outScale, w, h), x, y) = scale;
+    const float3 diff = StoreReJittered<false>(a, a.diffMode, a.diffResolve, a.diffOut, diffSg, x, y, viewZ, N, V, roughness, scale.x, diffFactor);
+    const float3 spec = StoreReJittered<true>(a, a.specMode, a.specResolve, a.specOut, specSg, x, y, viewZ, N, V, roughness, scale.y, specFactor);
     if (a.outComposed.ptr)
         StoreRGBA32F(AsPlane(a.outComposed, w, h), x, y, make_float4(diff.x + spec.x, diff.y + spec.y, diff.z + spec.z, 0.0f));
     if (a.outShadow.ptr) {
@@ -396,12 +517,17 @@ void BackEndSignal(Checker& c, const NrdHipBackEndSignal& s, const char* name, F
 
 extern "C" __attribute__((visibility("default"))) const char* nrdHipGetLastFrontEndError(void) { return t_LastError.c_str(); }
 
-extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputs(const NrdHipFrontEndDesc* d, void* hipStream) {
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsEx(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, void* hipStream) {
     using F = nrd::Format;
     if (!d)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputs: null descriptor");
     if (d->diffuse.mode > NRD_HIP_SIGNAL_RELAX_SH || d->specular.mode > NRD_HIP_SIGNAL_RELAX_SH || d->specular.mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputs: unknown signal mode (directional occlusion is a diffuse mode)");
+    const uint32_t checkerboardMode = options ? options->checkerboardMode : 0u;
+    if (checkerboardMode > (uint32_t)nrd::CheckerboardMode::WHITE)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsEx: options: unknown checkerboardMode");
+    if (checkerboardMode && d->diffuse.mode == NRD_HIP_SIGNAL_NONE && d->specular.mode == NRD_HIP_SIGNAL_NONE)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsEx: options: checkerboardMode without a diffuse or a specular signal to checkerboard");
     Checker c{"nrdHipPackInputs"};
     PackArgs a = {};
     a.normalRoughness = c.Check(d->normalRoughness, "normalRoughness", "required", F::RGBA32_SFLOAT);
@@ -434,20 +560,34 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputs(cons
     a.w = c.w;
     a.h = c.h;
     t_LastError.clear();
-    hipLaunchKernelGGL(PackInputsKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a);
+    if (checkerboardMode) // BLACK: the diffuse signal lives in cell 0, the specular one in cell 1 (reference Reblur.cpp:318-330, Relax.cpp:88-97); WHITE: the opposite
+        hipLaunchKernelGGL(PackCheckerboardKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a,
+            checkerboardMode == (uint32_t)nrd::CheckerboardMode::BLACK ? 0u : 1u, options->frameIndex & 1u);
+    else
+        hipLaunchKernelGGL(PackInputsKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a);
     return hipGetLastError() == hipSuccess ? (uint32_t)nrd::Result::SUCCESS : Fail(nrd::Result::FAILURE, "nrdHipPackInputs: the kernel launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputs(const NrdHipBackEndDesc* d, void* hipStream) {
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputs(const NrdHipFrontEndDesc* d, void* hipStream) { return nrdHipPackInputsEx(d, nullptr, hipStream); }
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsEx(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* options, void* hipStream) {
     using F = nrd::Format;
     if (!d)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputs: null descriptor");
+    const bool reJitter = options && options->reJitter;
     const NrdHipBackEndSignal &ds = d->diffuse, &ss = d->specular;
     if (ds.mode > NRD_HIP_SIGNAL_RELAX_SH || ss.mode > NRD_HIP_SIGNAL_RELAX_SH || ss.mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION || ds.resolve > NRD_HIP_RESOLVE_SG ||
         ss.resolve > NRD_HIP_RESOLVE_SG)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputs: unknown signal mode or resolve (directional occlusion is a diffuse mode)");
+    if (reJitter && !(IsSh(ds.mode) && IsSh(ss.mode)))
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsEx: options: reJitter needs a diffuse and a specular signal in an SH mode (NRD_SG_ReJitter takes both SGs)");
+    if (reJitter && (ds.resolve == NRD_HIP_RESOLVE_SG_EXTRACT_COLOR || ss.resolve == NRD_HIP_RESOLVE_SG_EXTRACT_COLOR))
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsEx: options: reJitter scales a resolved colour: the resolve of both signals must be SH or SG, not SG_EXTRACT_COLOR");
+    if (!reJitter && options && options->outReJitterScale.data)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsEx: options: outReJitterScale: given without reJitter");
     Checker c{"nrdHipResolveOutputs"};
-    ResolveArgs a = {};
+    ReJitterArgs ra = {};
+    ResolveArgs& a = ra.r;
     BackEndSignal(c, ds, "diffuse", a.diffIn0, a.diffIn1, a.diffOut, a.diffWide);
     BackEndSignal(c, ss, "specular", a.specIn0, a.specIn1, a.specOut, a.specWide);
     a.shadow = c.Check(d->shadow, "shadow", d->outShadow.data ? "outShadow needs it" : nullptr, F::R8_UNORM, F::RGBA8_UNORM);
@@ -462,15 +602,17 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputs(
     const bool reblurSpec = ss.mode >= NRD_HIP_SIGNAL_REBLUR_RADIANCE && ss.mode <= NRD_HIP_SIGNAL_REBLUR_OCCLUSION;
     const bool anyReblur = reblurSpec || (ds.mode >= NRD_HIP_SIGNAL_REBLUR_RADIANCE && ds.mode <= NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION);
     const bool needFactors = d->remodulate || a.outDiffFactor.ptr || a.outSpecFactor.ptr;
-    const bool needV = needFactors || a.outViewVector.ptr || (resolved(ss) && ss.resolve != NRD_HIP_RESOLVE_SG_EXTRACT_COLOR);
-    const bool needN = needFactors || (resolved(ds) && ds.resolve != NRD_HIP_RESOLVE_SG_EXTRACT_COLOR) || (resolved(ss) && ss.resolve != NRD_HIP_RESOLVE_SG_EXTRACT_COLOR) ||
+    const bool needV = reJitter || needFactors || a.outViewVector.ptr || (resolved(ss) && ss.resolve != NRD_HIP_RESOLVE_SG_EXTRACT_COLOR);
+    const bool needN = reJitter || needFactors || (resolved(ds) && ds.resolve != NRD_HIP_RESOLVE_SG_EXTRACT_COLOR) || (resolved(ss) && ss.resolve != NRD_HIP_RESOLVE_SG_EXTRACT_COLOR) ||
         (d->denormalizeHitDist && reblurSpec);
     if (a.outComposed.ptr && !(carriesColour(ds) && carriesColour(ss)) && !c.Failed())
         c.Error(nrd::Result::INVALID_ARGUMENT, "outComposed", "needs a diffuse and a specular signal that carry a colour");
     a.normalRoughness = c.Check(d->normalRoughness, "normalRoughness", needN ? "the chosen resolves / remodulation / specular hit distance need N and the roughness" : nullptr, kNormalRoughnessFormat);
     a.viewZ = c.Check(d->viewZ, "viewZ", needV || (d->denormalizeHitDist && anyReblur) ? "the view vector / denormalizeHitDist need it" : nullptr, F::R32_SFLOAT);
     a.albedo = c.Check(d->albedo, "albedo", needFactors ? "remodulation needs albedo and rf0" : nullptr, F::RGBA32_SFLOAT);
-    a.rf0 = c.Check(d->rf0, "rf0", needFactors ? "remodulation needs albedo and rf0" : nullptr, F::RGBA32_SFLOAT);
+    a.rf0 = c.Check(d->rf0, "rf0", needFactors ? "remodulation needs albedo and rf0" : reJitter ? "reJitter needs Rf0" : nullptr, F::RGBA32_SFLOAT);
+    if (reJitter)
+        ra.outScale = c.Check(options->outReJitterScale, "outReJitterScale", nullptr, F::RG32_SFLOAT);
     if (!c.Failed() && !c.w)
         c.Error(nrd::Result::INVALID_ARGUMENT, "descriptor", "nothing to do: no signal, no shadow, no output plane");
     if (needV)
@@ -489,6 +631,12 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputs(
     a.w = c.w;
     a.h = c.h;
     t_LastError.clear();
-    hipLaunchKernelGGL(ResolveOutputsKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a);
+    if (reJitter)
+        hipLaunchKernelGGL(ReJitterKernel, dim3((c.w + (uint32_t)kReJitterTileW - 1u) / (uint32_t)kReJitterTileW, (c.h + (uint32_t)kReJitterTileH - 1u) / (uint32_t)kReJitterTileH),
+            dim3(kReJitterTileW, kReJitterTileH), 0, (hipStream_t)hipStream, ra);
+    else
+        hipLaunchKernelGGL(ResolveOutputsKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a);
     return hipGetLastError() == hipSuccess ? (uint32_t)nrd::Result::SUCCESS : Fail(nrd::Result::FAILURE, "nrdHipResolveOutputs: the kernel launch failed");
 }
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputs(const NrdHipBackEndDesc* d, void* hipStream) { return nrdHipResolveOutputsEx(d, nullptr, hipStream); }

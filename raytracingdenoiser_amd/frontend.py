@@ -1,4 +1,4 @@
-"""Front end / back end on the device: plumbing over nrdHipPackInputs / nrdHipResolveOutputs (include/NRDHip.h).
+"""Front end / back end on the device: plumbing over nrdHipPackInputs(Ex) / nrdHipResolveOutputs(Ex) (include/NRDHip.h).
 
 pack_inputs() turns an application's fp32 buffers into the packed planes HipExecutor.bind accepts, resolve_outputs() turns the denoised OUT_* planes into
 linear fp32 radiance -- one kernel launch each, asynchronous on the current stream, usable inside torch.cuda.graph. This module allocates and calls the
@@ -142,13 +142,24 @@ def _reuse(out, key, like, shape, dtype):
 
 
 # ---- front end -------------------------------------------------------------------------------------------------------------------------------------------
-def pack_inputs(normal_roughness, viewz, *args, **kw):
-    """see describe_pack; launches on `stream` (a torch.cuda.Stream, or a raw handle with four-channel inputs only; default: the current stream) and returns the packed planes"""
+def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0, **kw):
+    """see describe_pack; launches on `stream` (a torch.cuda.Stream, or a raw handle with four-channel inputs only; default: the current stream) and returns the packed planes.
+    checkerboard_mode (api.CheckerboardMode) other than OFF: the noisy signals are traced for every other pixel of frame `frame_index` (CommonSettings::frameIndex) and their
+    texels go to the left half of the signal planes, whose other texels are left as they are (NRDHip.h nrdHipPackInputsEx)."""
     with _stream_scope(viewz, kw.get("stream")):
         res, d, keep = describe_pack(normal_roughness, viewz, *args, **kw)
         lib = kw.get("lib") or api.load_library()
-        _check(lib, lib.nrdHipPackInputs(C.byref(d), _stream(viewz, kw.get("stream"))), "nrdHipPackInputs")
+        if int(checkerboard_mode) == 0:
+            _check(lib, lib.nrdHipPackInputs(C.byref(d), _stream(viewz, kw.get("stream"))), "nrdHipPackInputs")
+        else:
+            options = pack_options(checkerboard_mode, frame_index)
+            _check(lib, lib.nrdHipPackInputsEx(C.byref(d), C.byref(options), _stream(viewz, kw.get("stream"))), "nrdHipPackInputsEx")
     return res
+
+
+def pack_options(checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0):
+    """api.HipFrontEndOptions for nrdHipPackInputsEx, next to the descriptor of describe_pack"""
+    return api.HipFrontEndOptions(int(checkerboard_mode), int(frame_index) & 0xFFFFFFFF)
 
 
 def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffuse=None, specular=None, albedo=None, rf0=None, distance_to_occluder=None, translucency=None,
@@ -224,14 +235,32 @@ def _packed_plane(t, what):
     return _plane(t, _IN_FORMAT[key])
 
 
-def resolve_outputs(**kw):
-    """see describe_resolve; launches on `stream` (as pack_inputs) and returns the fp32 planes"""
+def resolve_outputs(rejitter=False, **kw):
+    """see describe_resolve; launches on `stream` (as pack_inputs) and returns the fp32 planes. rejitter=True (both signals in an SH mode, resolve SH or SG; needs rf0): the
+    resolved colours are multiplied by NRD_SG_ReJitter before the remodulation (NRDHip.h nrdHipResolveOutputsEx); "rejitter_scale" in `want` adds the two factors, fp32 [H, W, 2]."""
     like = next(t for t in (kw.get("shadow"), kw.get("viewz"), kw.get("normal_roughness"), (kw.get("diffuse") or {}).get("in0"), (kw.get("specular") or {}).get("in0")) if t is not None)
     with _stream_scope(like, kw.get("stream")):
-        res, d, keep = describe_resolve(**kw)
+        want = tuple(kw.get("want", ()))
+        res, d, keep = describe_resolve(**dict(kw, want=tuple(n for n in want if n != "rejitter_scale")))
         lib = kw.get("lib") or api.load_library()
-        _check(lib, lib.nrdHipResolveOutputs(C.byref(d), _stream(like, kw.get("stream"))), "nrdHipResolveOutputs")
+        if not rejitter and "rejitter_scale" not in want:
+            _check(lib, lib.nrdHipResolveOutputs(C.byref(d), _stream(like, kw.get("stream"))), "nrdHipResolveOutputs")
+        else:
+            options = resolve_options(res, like, rejitter=rejitter, want_scale="rejitter_scale" in want, out=kw.get("out"))
+            _check(lib, lib.nrdHipResolveOutputsEx(C.byref(d), C.byref(options), _stream(like, kw.get("stream"))), "nrdHipResolveOutputsEx")
     return res
+
+
+def resolve_options(res, like, rejitter=True, want_scale=False, out=None):
+    """api.HipBackEndOptions for nrdHipResolveOutputsEx, next to the descriptor of describe_resolve: `res` is the dict describe_resolve returned, which gains
+    "rejitter_scale" (fp32 [H, W, 2], allocated like `like` or taken from `out`) with want_scale"""
+    options = api.HipBackEndOptions()
+    options.reJitter = int(bool(rejitter))
+    if want_scale:
+        h, w = like.shape[:2]
+        res["rejitter_scale"] = _reuse(out, "rejitter_scale", like, (h, w, 2), "float32")
+        options.outReJitterScale = _plane(res["rejitter_scale"], F.RG32_SFLOAT)
+    return options
 
 
 def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=None, viewz=None, albedo=None, rf0=None, common_settings=None, hit_dist_params=HIT_DIST_PARAMS,

@@ -2,11 +2,15 @@
 against (c) the same packing done with the torch packers of raytracingdenoiser_amd/synth.py -- the only path there was before the kernels -- and (d) the copy bandwidth the
 same device delivers (nrdHipMeasureCopyBandwidth). Device events around `--reps` back-to-back launches after `--warmup` launches; the bytes are counted from the plane formats.
 Also records what the compiler made of the kernels (VGPRs, waves per SIMD, scratch, 16-byte loads) from a gfx950 assembly listing (tools/isa_stats.py).
-usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only]"""
+--rejitter adds, in the same run, an SH plane set (REBLUR_SH for both signals in fp16 planes): (a) nrdHipResolveOutputs with resolve = SG, (b) nrdHipResolveOutputsEx with
+reJitter = 1 on the same planes, both against the copy rate, (b) once more from --ab-library (a build of the re-jitter form that did not ship:
+python tools/build_variant.py rejitter_plain -DNRD_REJITTER_TILE=0), and nrdHipPackInputsEx with checkerboardMode = BLACK on the plane set of `pack`.
+usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]]"""
 import argparse
 import ctypes as C
 import json
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -23,6 +27,8 @@ PACK_READ = {"normal_roughness RGBA32_SFLOAT": 16, "viewZ R32_SFLOAT": 4, "motio
 PACK_WRITE = {"IN_NORMAL_ROUGHNESS": 4, "IN_VIEWZ R32_SFLOAT": 4, "IN_MV RGBA16_SFLOAT": 8, "IN_DIFF_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "IN_SPEC_RADIANCE_HITDIST RGBA16_SFLOAT": 8}
 RESOLVE_READ = {"OUT_DIFF_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "OUT_SPEC_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "IN_NORMAL_ROUGHNESS": 4, "IN_VIEWZ R32_SFLOAT": 4}
 RESOLVE_WRITE = {"diffuse RGBA32_SFLOAT": 16, "specular RGBA32_SFLOAT": 16}
+SH_RESOLVE_READ = {"OUT_DIFF_SH0 RGBA16_SFLOAT": 8, "OUT_DIFF_SH1 RGBA16_SFLOAT": 8, "OUT_SPEC_SH0 RGBA16_SFLOAT": 8, "OUT_SPEC_SH1 RGBA16_SFLOAT": 8, "IN_NORMAL_ROUGHNESS": 4, "IN_VIEWZ R32_SFLOAT": 4}
+REJITTER_READ = dict(SH_RESOLVE_READ, **{"rf0 RGBA32_SFLOAT": 16})  # (the four neighbour texels of IN_NORMAL_ROUGHNESS / IN_VIEWZ are other lanes' own texels: counted once)
 
 
 def isa():
@@ -44,6 +50,31 @@ def isa():
     return out
 
 
+def _facts(s):
+    c = s["counter"]
+    return {"vgprs": s["vgpr"], "waves_per_simd": s["occ"], "scratch_bytes": s["scratch"], "lds_bytes": s["ldsb"], "valu": s["valu"], "salu": s["salu"], "vmem": s["vmem"],
+            "ds_read_b128": c.get("ds_read_b128", 0), "ds_write_b128": c.get("ds_write_b128", 0), "v_div_scale_f32": c.get("v_div_scale_f32", 0), "transcendental": s["trans"]}
+
+
+def options_isa(extra=()):
+    """static facts about the kernels behind nrdHipResolveOutputsEx / nrdHipPackInputsEx (the `isa_options` object of profiles/frontend_bench.json), as isa(): "rejitter"
+    and "pack_checkerboard"; extra: further compiler flags (-DNRD_REJITTER_TILE=0: the form without the LDS tile). rejitter also holds the tile its source declares."""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_frontend.s")
+        flags = [f for f in B._flags(SRC) if f not in ("-x", "hip")] + list(extra)
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+    out = {}
+    for mangled, s in stats.items():
+        name = "rejitter" if "ReJitterKernel" in mangled else "pack_checkerboard" if "PackCheckerboardKernel" in mangled else None
+        if name:
+            out[name] = _facts(s)
+    assert set(out) == {"rejitter", "pack_checkerboard"}, list(stats)
+    tile = re.search(r"constexpr int kReJitterTileW = (\d+), kReJitterTileH = (\d+);", open(SRC).read())
+    out["rejitter"]["declared_tile_bytes"] = (int(tile.group(1)) + 2) * (int(tile.group(2)) + 2) * 16
+    return out
+
+
 def synth_pack(raw, synth, torch):
     """the packing of synth.render_frame for REBLUR_DIFFUSE_SPECULAR on the raw values: its packers, elementwise torch operations with fp32 intermediates"""
     out = {"normal_roughness": synth.pack_normal_roughness(raw["normal"], raw["roughness"], raw["material"]).contiguous(), "viewz": raw["viewz"].clone(),
@@ -55,6 +86,59 @@ def synth_pack(raw, synth, torch):
     return out
 
 
+def rejitter_calls(args, lib, stream, pack_desc, torch, api, frontend):
+    """{name: callable} of the --rejitter section: the SH plane set is packed by the pack kernel from smooth raw values, the descriptors are built once"""
+    from raytracingdenoiser_amd import scene, synth
+
+    w, h = args.width, args.height
+    g = torch.Generator(device="cuda").manual_seed(11)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    cam = synth.Camera(w, h, 0)
+    cs = scene.common_settings(cam, cam, w, h, 0)
+    # normals facing the viewer with per-pixel detail, depth without steps: NRD_SG_ReJitter accepts its four neighbours at almost every pixel
+    n_view = torch.cat([0.6 * (rand(h, w, 2) - 0.5), -torch.ones(h, w, 1, device="cuda")], -1)
+    n_view = n_view / n_view.norm(dim=-1, keepdim=True)
+    rot = torch.tensor([cam.right, cam.up, cam.fwd], device="cuda", dtype=torch.float32)  # rows: the view axes in world space
+    normal = n_view @ rot
+    nr = torch.cat([normal, 0.05 + 0.95 * rand(h, w, 1)], -1).contiguous()
+    xs = torch.arange(w, device="cuda", dtype=torch.float32)
+    viewz = (5.0 + 0.002 * xs).expand(h, w).contiguous()
+
+    def signal():
+        direction = normal + 0.8 * (rand(h, w, 3) - 0.5)
+        direction = torch.cat([direction / direction.norm(dim=-1, keepdim=True), torch.zeros(h, w, 1, device="cuda")], -1).contiguous()
+        return dict(mode=frontend.SignalMode.REBLUR_SH, radiance_hitdist=(rand(h, w, 4) * torch.tensor([4.0, 3.0, 5.0, 30.0], device="cuda")).contiguous(), direction=direction)
+
+    packed = frontend.pack_inputs(nr, viewz, diffuse=signal(), specular=signal())
+    R, S, RES = api.ResourceType, frontend.SignalMode, frontend.ResolveMode
+    rf0 = torch.cat([(0.04 + 0.8 * rand(h, w, 1)).expand(h, w, 3), torch.zeros(h, w, 1, device="cuda")], -1).contiguous()
+    planes = dict(diffuse=dict(mode=S.REBLUR_SH, resolve=RES.SG, in0=packed[R.IN_DIFF_SH0][0], in1=packed[R.IN_DIFF_SH1][0]),
+                  specular=dict(mode=S.REBLUR_SH, resolve=RES.SG, in0=packed[R.IN_SPEC_SH0][0], in1=packed[R.IN_SPEC_SH1][0]), normal_roughness=packed[R.IN_NORMAL_ROUGHNESS][0],
+                  viewz=packed[R.IN_VIEWZ][0], common_settings=cs)
+    res_a, desc_a, keep_a = frontend.describe_resolve(**planes)
+    res_b, desc_b, keep_b = frontend.describe_resolve(rf0=rf0, **planes)
+    options = frontend.resolve_options(res_b, viewz, rejitter=True)
+    front_options = frontend.pack_options(api.CheckerboardMode.BLACK, 0)
+    keep = [packed, res_a, keep_a, res_b, keep_b, rf0, cs]
+
+    def call(fn, *a):
+        def f(keep=keep):
+            assert fn(*a) == 0
+        return f
+
+    calls = {"sg_resolve": call(lib.nrdHipResolveOutputs, C.byref(desc_a), stream), "rejitter": call(lib.nrdHipResolveOutputsEx, C.byref(desc_b), C.byref(options), stream),
+             "pack_checkerboard": call(lib.nrdHipPackInputsEx, C.byref(pack_desc), C.byref(front_options), stream)}
+    if args.ab_library:
+        other = api.load_library(args.ab_library)
+        calls["rejitter_other_form"] = call(other.nrdHipResolveOutputsEx, C.byref(desc_b), C.byref(options), stream)
+    for f in calls.values():
+        f()
+    torch.cuda.synchronize()
+    scale = frontend.resolve_outputs(rejitter=True, rf0=rf0, want=("rejitter_scale",), **planes)["rejitter_scale"]
+    print("re-jitter planes: %.1f %% of the pixels scaled" % (100.0 * float((scale != 1.0).any(-1).float().mean())))
+    return calls
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=2560)
@@ -63,8 +147,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.json"))
     ap.add_argument("--isa-only", action="store_true", help="no GPU needed: print the static facts and leave")
+    ap.add_argument("--rejitter", action="store_true", help="also time the SH plane set: SG resolve, SG resolve + re-jitter (nrdHipResolveOutputsEx), and the checkerboard pack")
+    ap.add_argument("--ab-library", help="with --rejitter: a build of the other re-jitter form (-DNRD_REJITTER_TILE=0), timed on the same planes in the same rounds")
     args = ap.parse_args()
-    result = {"isa": isa()}
+    result = {"isa": isa(), "isa_options": options_isa()}
     if args.isa_only:  # the static half of the record: nothing here is a time
         print(json.dumps(result))
         return
@@ -117,12 +203,17 @@ def main():
         torch.cuda.synchronize()
         return t0.elapsed_time(t1) / args.reps
 
+    extra = {}
+    if args.rejitter:
+        extra = rejitter_calls(args, lib, stream, pack_desc, torch, api, frontend)
+
     # alternate the measurements twice: the spread between the rounds says how much a difference means
     rounds = []
     for _ in range(2):
         rounds.append({"pack_ms": timed(pack), "resolve_ms": timed(resolve), "synth_pack_ms": timed(lambda: synth_pack(raw, synth, torch)),
                        "pack_through_python_wrapper_ms": timed(lambda: frontend.pack_inputs(nr, raw["viewz"], material_id=raw["material"], motion=raw["motion"], diffuse=sig(raw["diff"]),
                                                                                            specular=sig(raw["spec"]), out=packed))})
+        rounds[-1].update({name + "_ms": timed(fn) for name, fn in extra.items()})
     best = {k: min(r[k] for r in rounds) for k in rounds[0]}
     # how fast the host can enqueue: the same call on a 64 x 4 frame, where the kernel is one workgroup -- a window bounded by this rate would measure the host, not the kernel
     tiny = torch.zeros(4, 64, 4, device="cuda")
@@ -145,6 +236,22 @@ def main():
         "pack_fraction_of_copy_rate": rate(pack_bytes, best["pack_ms"]) / gbps.value,
         "resolve_fraction_of_copy_rate": rate(resolve_bytes, best["resolve_ms"]) / gbps.value,
     })
+    if args.rejitter:
+        sg_bytes, rj_bytes = sum(SH_RESOLVE_READ.values()) + sum(RESOLVE_WRITE.values()), sum(REJITTER_READ.values()) + sum(RESOLVE_WRITE.values())
+        result["rejitter"] = {
+            "planes": "REBLUR_SH for both signals in RGBA16_SFLOAT planes, IN_NORMAL_ROUGHNESS, IN_VIEWZ, rf0; smooth normals and depth, so that most pixels are scaled",
+            "sg_resolve_ms": best["sg_resolve_ms"], "sg_resolve_read_bytes_per_pixel": SH_RESOLVE_READ, "sg_resolve_bytes_per_pixel": sg_bytes,
+            "sg_resolve_fraction_of_copy_rate": rate(sg_bytes, best["sg_resolve_ms"]) / gbps.value,
+            "ms": best["rejitter_ms"], "read_bytes_per_pixel": REJITTER_READ, "write_bytes_per_pixel": RESOLVE_WRITE, "bytes_per_pixel": rj_bytes,
+            "gigabytes_per_second": rate(rj_bytes, best["rejitter_ms"]), "fraction_of_copy_rate": rate(rj_bytes, best["rejitter_ms"]) / gbps.value,
+            "rejitter_over_sg_resolve": best["rejitter_ms"] / best["sg_resolve_ms"],
+            "shipped_form": "a 64 x 4 workgroup stages decoded N.xyz and viewZ of its tile plus a one-texel halo in LDS (NRD_REJITTER_TILE = 1)",
+            "fraction_is_not": "a share of HBM bandwidth: the working set partly fits the memory-side cache, as for resolve (DESIGN.md section 3.4)"}
+        if "rejitter_other_form" in extra:
+            result["rejitter"]["other_form"] = {"what": "every lane loads and decodes its four neighbour texels itself (NRD_REJITTER_TILE = 0), same planes, same rounds",
+                                                "ms": best["rejitter_other_form_ms"], "over_shipped_form": best["rejitter_other_form_ms"] / best["rejitter_ms"]}
+        result["pack_checkerboard"] = {"ms": best["pack_checkerboard_ms"], "over_pack": best["pack_checkerboard_ms"] / best["pack_ms"],
+                                       "what": "nrdHipPackInputsEx, checkerboardMode = BLACK, on the planes of `pack`: reads every other texel of the two signal planes, writes half of the two packed ones"}
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as fp:
         json.dump(result, fp, indent=1)
