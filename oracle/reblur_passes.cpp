@@ -682,6 +682,12 @@ void TemporalAccumulation(const PassIO& io) {
                 y = clamp(y, 0, rh);
                 const int shift = (OCC && c.gSpecCheckerboard != 2) ? 1 : 0; // REBLUR_TemporalAccumulation.hlsli:21-27
                 float hitDist = (OCC || c.gSpecPrepassBlurRadius == 0.0f) ? ExtractHitDist(Sig::From(gIn_Spec->Load(x >> shift, y))) : gIn_SpecHitDistForTracking->Load(x, y).x;
+                // the host's noisy input beyond the denoising range is no sample (a deliberate departure from REBLUR_TemporalAccumulation.hlsli:29-35, which takes whatever
+                // a host left there into the minimum; identical where that is 0 or NaN -- DESIGN.md "Input rules")
+                // (checkerboarded: the packed texel holds the data of the pixel of this pair whose parity matches -- that pixel's viewZ decides)
+                const int sx = shift ? min((x & ~1) | int((c.gSpecCheckerboard ^ uint32_t(y) ^ c.gFrameIndex) & 1u), rw) : x;
+                if ((OCC || c.gSpecPrepassBlurRadius == 0.0f) && UnpackViewZ(c, gIn_ViewZ.Load(sx, y).x) > c.gDenoisingRange)
+                    hitDist = 0.0f;
                 return hitDist == 0.0f ? NRD_INF : hitDist;
             };
 

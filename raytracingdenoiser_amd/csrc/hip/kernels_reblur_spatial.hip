@@ -96,8 +96,9 @@ struct TapGuides {
 };
 
 // the "full rect" tap: k = the snapped pixel (integer-valued floats, not yet clamped)
-template <int FR, bool NEED_ROUGHNESS>
-NRD_D TapGuides FetchTapGuidesFullRect(const ReblurCB& c, const SpatialCtx& s, float2 k, const NormalRoughnessGuide& gIn_Normal_Roughness, const Plane& gIn_ViewPos, bool compareMaterials) {
+template <SpatialMode MODE, int FR, bool NEED_ROUGHNESS>
+NRD_D TapGuides FetchTapGuidesFullRect(const ReblurCB& c, const SpatialCtx& s, float2 k, const Plane& gIn_ViewZ, const NormalRoughnessGuide& gIn_Normal_Roughness, const Plane& gIn_ViewPos,
+    bool compareMaterials) {
     TapGuides t;
     const float2 rectSize = ToF2(c.gRectSize), rectSizeInv = ToF2(c.gRectSizeInv);
     // clamp in the float domain (one v_med3_f32 per axis; the snapped coordinate is an integer-valued float): inside <=> the clamp changed nothing
@@ -123,6 +124,12 @@ NRD_D TapGuides FetchTapGuidesFullRect(const ReblurCB& c, const SpatialCtx& s, f
         if (NEED_ROUGHNESS || FR == 1)
             bits = *(const uint32_t*)(gIn_Normal_Roughness.word.ptr + (offset >> 2)); // (a quarter of the guide planes' pitch: reblur_device.h NormalRoughnessGuide)
     }
+    // PostBlur: the tap's viewZ comes from the pass's OWN viewZ plane, as in the generic tap -- not from the frame's guide texel. That plane is the copy the Blur pass wrote, and
+    // Blur's workgroups over all-sky tiles leave before writing it (as the reference's do): under sky tiles it keeps viewZ of EARLIER frames, and that stale value is what the
+    // reference weighs the tap by. Within the range the two planes agree (Blur wrote the texel this frame). 4 bytes more per tap; re-reading only where the guide says "beyond
+    // the range" is the same value for fewer bytes but a divergent branch per tap: 78 -> 95 VGPRs in the benchmarked kernel against 78 -> 79 (profiles/HISTORY.md).
+    if (MODE == POST_BLUR)
+        t.zs = UnpackViewZ(c, LoadR32F(gIn_ViewZ, t.ts.x, t.ts.y));
     const float2 uvc = (k + 0.5f) * rectSizeInv; // centre of the snapped pixel; equals the clamped texel's centre whenever the tap counts (t.w != 0)
     t.Xvs = ReconstructViewPosition(uvc, ToF4(c.gFrustum), t.zs, 0.0f); // perspective only (CheckSupported); dead code unless the caller needs the position
     t.NvXvs = t.zs * (k.x * s.geo.x + (k.y * s.geo.y + s.geo.z));
@@ -140,7 +147,7 @@ NRD_D TapGuides FetchTapGuides(const ReblurCB& c, const SpatialCtx& s, float2 uv
     const float2 rectSize = ToF2(c.gRectSize), rectSizeInv = ToF2(c.gRectSizeInv);
     uv = Floor(uv * rectSize);
     if (FR)
-        return FetchTapGuidesFullRect<FR, NEED_ROUGHNESS>(c, s, uv, gIn_Normal_Roughness, gIn_ViewPos, compareMaterials);
+        return FetchTapGuidesFullRect<MODE, FR, NEED_ROUGHNESS>(c, s, uv, gIn_ViewZ, gIn_Normal_Roughness, gIn_ViewPos, compareMaterials);
     TapGuides t;
     uv = uv + 0.5f;
     if (MODE == PRE_BLUR && CB)
@@ -596,7 +603,7 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_SPATIAL) void Rebl
     }
 }
 
-// NRD_HIP_GENERIC_TAPS=1: never take the "full rect" variant (A/B runs and the test that holds the two variants against each other)
+// NRD_HIP_GENERIC_TAPS=1: never take the "full rect" variant (A/B runs; tests/test_input_rules.py holds the two variants against each other byte for byte in child processes)
 static bool ForceGenericTaps() {
     const char* v = getenv("NRD_HIP_GENERIC_TAPS");
     return v && atoi(v) != 0;

@@ -147,10 +147,21 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
         for (int i = threadIdx.x; i < BUF_X * BUF_Y; i += TILE_X * TILE_Y) {
             int lx = i % BUF_X, ly = i / BUF_X;
             int gx = ClampI(baseX + lx, 0, rw), gy = ClampI(baseY + ly, 0, rh);
-            s_Normal_Roughness[ly * BUF_STRIDE + lx] = LoadDecodedNormalRoughness(P.decodedNR, gx, gy);
+            float unusedMaterialID, texelViewZ; // (the viewZ rides in the guide texel: no extra load)
+            s_Normal_Roughness[ly * BUF_STRIDE + lx] = LoadDecodedNormalRoughness(P.decodedNR, gx, gy, unusedMaterialID, texelViewZ);
             if (SPEC) {
                 const int shift = (OCC && cArg.gSpecCheckerboard != 2) ? 1 : 0; // checkerboarded occlusion input: left half (reference REBLUR_TemporalAccumulation.hlsli:21-27)
                 float hitDist = (OCC || cArg.gSpecPrepassBlurRadius == 0.0f) ? ExtractHitDist(Sig::Load(P.inSpec, gx >> shift, gy)) : LoadR16F(P.inSpecHitDistForTracking, gx, gy);
+                // Without a pre-pass this is the host's NOISY input, which may hold anything beyond the denoising range: such a texel is no sample (0 = "none"). The reference
+                // takes it into the 3x3 minimum unasked (REBLUR_TemporalAccumulation.hlsli:29-35) -- identical on a sky whose hit distance is 0 or NaN, and a departure where a
+                // host leaves a finite value there (DESIGN.md "Input rules").
+                // (checkerboarded: the packed texel holds the data of the pixel of this pair whose parity matches -- that pixel's viewZ decides)
+                if (shift) {
+                    const int sx = min((gx & ~1) | (int)((cArg.gSpecCheckerboard ^ (uint32_t)gy ^ cArg.gFrameIndex) & 1u), rw);
+                    LoadDecodedNormalRoughness(P.decodedNR, sx, gy, unusedMaterialID, texelViewZ);
+                }
+                if ((OCC || cArg.gSpecPrepassBlurRadius == 0.0f) && texelViewZ > cArg.gDenoisingRange)
+                    hitDist = 0.0f;
                 s_HitDistForTracking[ly * BUF_STRIDE + lx] = hitDist == 0.0f ? NRD_INF : hitDist;
             }
         }

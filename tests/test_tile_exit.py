@@ -25,8 +25,8 @@ SKY_FRAME = 2  # "flash": the frame on which everything is sky
 def _shape_sky(frame, mode, f):
     """lays the sky of a rendered frame out for the case, in place. Sky = viewZ beyond the denoising range (all the tile classification looks at). A pixel that BECOMES sky takes
     the values of a rendered sky pixel in every other plane too (zero signal and motion, the renderer's sky normal, ...), and rendered sky that becomes geometry is what
-    "no_sky" is for: a far wall that keeps the rendered sky's planes. (Sky pixels that carry a signal are another matter than the tile test: next to such pixels REBLUR's device
-    code and the oracle disagree on two specular history planes -- also with the sources before this change, on the GPU and in the emulation; see the change's description.)"""
+    "no_sky" is for: a far wall that keeps the rendered sky's planes. (Sky pixels that carry a signal, a geometry normal or garbage are another matter than the tile test: tests/test_input_rules.py
+    holds the library on them -- a sky painted by viewZ alone, NaN / INF in the noisy inputs beyond the range, arbitrary finite guides.)"""
     viewz = frame["viewz"]
     h, w = viewz.shape
     if mode == "default" or (mode == "flash" and f != SKY_FRAME):
