@@ -314,6 +314,48 @@ typedef struct NrdHipBackEndOptions {
 } NrdHipBackEndOptions;
 uint32_t nrdHipResolveOutputsEx(const NrdHipBackEndDesc* desc, const NrdHipBackEndOptions* options, void* hipStream);
 
+// Many paths per pixel (reference README "NOISY INPUTS": "In case of many paths per pixel hitT for specular must be 'averaged' by
+// NRD_FrontEnd_SpecHitDistAveraging_* functions from NRD.hlsli"): the pack call over N sample layers per signal, reduced by the reference's rules and packed in the
+// same launch. Sample layer s of a signal plane is the plane of the descriptor with its `data` advanced by s x layerBytes -- a [ N, H, W, 4 ] tensor; layer bases are
+// 64-bit pointers, each layer obeys the per-plane limits above, the whole stack may exceed 4 GiB. samples == NULL, or a struct whose counts are 0 or 1 and whose
+// threshold is 0, is exactly nrdHipPackInputsEx( desc, options, stream ): the same kernel, the same bytes, no extra loads. The contract is the one above: validated
+// before the first HIP call, nothing enqueued on an error, no allocation, no synchronisation, capturable into a graph, errors through nrdHipGetLastFrontEndError.
+// INVALID_ARGUMENT, naming the field: samplesNum > 64; a non-zero `reserved`; a negative or NaN hitDistTrimThreshold; and with samplesNum > 1: a layer stride
+// (of a plane the mode reads) that is not a multiple of 16 or is below rowPitchBytes x height of that plane, or a signal whose mode is NONE.
+//
+// Per pixel and signal, in unfused fp32 with correctly rounded division, with r = 1 for the diffuse signal and the pixel's roughness for the specular one, and
+// `factor` the signal's NRD_MaterialFactors factor when demodulating -- for s = 0 .. N - 1, in this order:
+//   1. ( rad_s, h_s ) and, where the mode needs it, dir_s are read from layer s
+//   2. if hitDistTrimThreshold > 0: h_s = NRD_FrontEnd_TrimHitDistance( h_s, hitDistTrimThreshold )
+//   3. if demodulating: rad_s = rad_s / factor, component-wise, as the plain call does
+//   4. P_s = what the mode's packer of NRD.hip.h returns for that one sample with sanitize = true: the fp32 out0 (and out1 for the SH modes), before any store codec.
+//      Sanitising, clamping to NRD_FP16_MAX and the hit-distance normalisation ( REBLUR_FrontEnd_GetNormHitDist( h_s, viewZ, hitDistParams, r ) ) are per sample,
+//      exactly as the plain call would do for a pixel holding that sample.
+// Then
+//   diffuse signal, every mode:            texel = ( ( ( P_0 + P_1 ) + P_2 ) + ... ) / float( N ), component-wise over all channels of out0 and out1
+//   specular signal, colour channels:      the same mean over every channel except the one that carries the hit distance
+//   specular signal, hit-distance channel: ( out0.w, or the only channel in the occlusion mode ) the packer's hit-distance output for the single value H, where
+//                                          a = NRD_FrontEnd_SpecHitDistAveraging_Begin(); _Add( a, h_s ) for each s in order; _End( a ); H = a
+//                                          -- normalised once for the REBLUR modes, clamped by RELAX's packer for the RELAX modes
+// and the texel goes through the store codec of the plain call. This is the only place where the two signals differ: the reference prescribes the minimum of the
+// non-zero samples (0 when all are 0) for the specular hitT only and nothing for the diffuse one, for which the mean of the normalised (RELAX: clamped) hit
+// distances is used. Every packer is linear in ( radiance, direction x luminance ) once its per-sample clamp is applied, so the mean of the packed samples is the
+// packed estimate of the mean signal for radiance, SH and directional occlusion alike; N = 1 degenerates to the plain call bit for bit ( P_0 / 1.0f ).
+// Checkerboarding: pixel selection and the x >> 1 column are those of nrdHipPackInputsEx; only the selected pixels of any layer are read. The G-buffer and SIGMA
+// outputs are unaffected.
+typedef struct NrdHipSignalSamples {
+    uint32_t samplesNum;                // 0 is read as 1; at most 64
+    uint32_t reserved;                  // must be 0
+    uint64_t radianceHitDistLayerBytes; // distance from sample layer s to layer s + 1 of NrdHipFrontEndSignal::radianceHitDist
+    uint64_t directionLayerBytes;       // the same for ::direction (modes that read it)
+} NrdHipSignalSamples;
+typedef struct NrdHipFrontEndSamples {
+    NrdHipSignalSamples diffuse, specular;
+    float hitDistTrimThreshold;         // > 0: every sample's hit distance goes through NRD_FrontEnd_TrimHitDistance first; 0: off
+    uint32_t reserved;                  // must be 0
+} NrdHipFrontEndSamples;
+uint32_t nrdHipPackInputsSamples(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, void* hipStream);
+
 #ifdef __cplusplus
 }
 #endif

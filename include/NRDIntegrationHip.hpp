@@ -104,6 +104,10 @@ public:
     inline bool ResolveOutputs(const NrdHipBackEndDesc& desc) { return nrdHipResolveOutputs(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
     // with options (nrdHipPackInputsEx / nrdHipResolveOutputsEx): checkerboarded noisy inputs, NRD_SG_ReJitter between the resolve and the remodulation
     inline bool PackInputs(const NrdHipFrontEndDesc& desc, const NrdHipFrontEndOptions& options) { return nrdHipPackInputsEx(&desc, &options, m_Stream) == (uint32_t)Result::SUCCESS; }
+    // many paths per pixel (nrdHipPackInputsSamples): N sample layers per signal, reduced by the reference's rules (specular hitT: NRD_FrontEnd_SpecHitDistAveraging_*) and packed in one launch
+    inline bool PackInputs(const NrdHipFrontEndDesc& desc, const NrdHipFrontEndOptions& options, const NrdHipFrontEndSamples& samples) {
+        return nrdHipPackInputsSamples(&desc, &options, &samples, m_Stream) == (uint32_t)Result::SUCCESS;
+    }
     inline bool ResolveOutputs(const NrdHipBackEndDesc& desc, const NrdHipBackEndOptions& options) { return nrdHipResolveOutputsEx(&desc, &options, m_Stream) == (uint32_t)Result::SUCCESS; }
     inline const char* GetLastFrontEndError() const { return nrdHipGetLastFrontEndError(); }
 

@@ -306,8 +306,16 @@ class HipBackEndOptions(C.Structure):  # include/NRDHip.h NrdHipBackEndOptions
     _fields_ = [("reJitter", C.c_uint32), ("outReJitterScale", HipPlaneDesc)]
 
 
+class HipSignalSamples(C.Structure):  # include/NRDHip.h NrdHipSignalSamples
+    _fields_ = [("samplesNum", C.c_uint32), ("reserved", C.c_uint32), ("radianceHitDistLayerBytes", C.c_uint64), ("directionLayerBytes", C.c_uint64)]
+
+
+class HipFrontEndSamples(C.Structure):  # include/NRDHip.h NrdHipFrontEndSamples
+    _fields_ = [("diffuse", HipSignalSamples), ("specular", HipSignalSamples), ("hitDistTrimThreshold", C.c_float), ("reserved", C.c_uint32)]
+
+
 assert C.sizeof(HipPlaneDesc) == 24 and C.sizeof(HipFrontEndSignal) == 104 and C.sizeof(HipFrontEndDesc) == 552 and C.sizeof(HipBackEndSignal) == 80 and C.sizeof(HipBackEndDesc) == 432
-assert C.sizeof(HipFrontEndOptions) == 8 and C.sizeof(HipBackEndOptions) == 32
+assert C.sizeof(HipFrontEndOptions) == 8 and C.sizeof(HipBackEndOptions) == 32 and C.sizeof(HipSignalSamples) == 24 and C.sizeof(HipFrontEndSamples) == 56
 
 
 # ----------------------------------------------------------------------------------------------- library
@@ -331,7 +339,7 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipCreateExecutorWithArena", "nrdHipSetProfiling", "nrdHipCollectPassTimings", "nrdHipSetOwnedRows", "nrdHipGetDispatchReach",
                    "nrdHipExecuteDispatchRange", "nrdHipPlanHaloExchange", "nrdHipSetGraphMode", "nrdHipGetGraphStats", "nrdHipGetTileFallbackStats", "nrdHipGetNumericsMode", "nrdHipMeasureCopyBandwidth",
                    "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError",
-                   "nrdHipPackInputsEx", "nrdHipResolveOutputsEx"]
+                   "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples"]
 
 _libs = {}
 
@@ -402,6 +410,7 @@ def load_library(path=None):
     lib.nrdHipResolveOutputs.argtypes, lib.nrdHipResolveOutputs.restype = [P(HipBackEndDesc), C.c_void_p], C.c_uint32
     lib.nrdHipGetLastFrontEndError.argtypes, lib.nrdHipGetLastFrontEndError.restype = [], C.c_char_p
     lib.nrdHipPackInputsEx.argtypes, lib.nrdHipPackInputsEx.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), C.c_void_p], C.c_uint32
+    lib.nrdHipPackInputsSamples.argtypes, lib.nrdHipPackInputsSamples.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSamples), C.c_void_p], C.c_uint32
     lib.nrdHipResolveOutputsEx.argtypes, lib.nrdHipResolveOutputsEx.restype = [P(HipBackEndDesc), P(HipBackEndOptions), C.c_void_p], C.c_uint32
     _libs[path] = lib
     return lib

@@ -47,6 +47,13 @@ struct PackArgs {
     uint32_t diffMode, specMode, motionIsRG, demodulate;
 };
 
+// nrdHipPackInputsSamples: sample layer s of a signal's fp32 planes starts s x layer bytes behind the plane of PackArgs (64-bit: a stack of layers may exceed 4 GiB)
+struct SampleArgs {
+    uint64_t diffInLayer, diffDirLayer, specInLayer, specDirLayer;
+    uint32_t diffNum, specNum; // >= 1
+    float trim;                // > 0: NRD_FrontEnd_TrimHitDistance on every sample's hit distance
+};
+
 struct ResolveArgs {
     FePlane normalRoughness, viewZ, albedo, rf0;
     FePlane diffIn0, diffIn1, diffOut, specIn0, specIn1, specOut;
@@ -114,14 +121,151 @@ __device__ __forceinline__ void PackSignal(uint32_t mode, const FePlane& in, con
     }
 }
 
+// ---- many paths per pixel (nrdHipPackInputsSamples; the per-pixel rules are spelled out in NRDHip.h) ---------------------------------------------------
+// P_s of one sample: the fp32 texels the mode's packer returns, before the store codec. The specular signal takes its hit-distance channel from PackedHitDist
+// of the reduced value instead, so its samples are packed with a hit distance of 0 and that channel of the sum is never read.
+template <bool SPEC, uint32_t MODE>
+__device__ __forceinline__ float4 PackSample(float3 radiance, float hitDist, float3 direction, float viewZ, float r, float4 hitDistParams, float4& p1) {
+    constexpr bool kReblur = MODE != NRD_HIP_SIGNAL_RELAX_RADIANCE && MODE != NRD_HIP_SIGNAL_RELAX_SH;
+    const float hd = SPEC ? 0.0f : kReblur ? REBLUR_FrontEnd_GetNormHitDist(hitDist, viewZ, hitDistParams, r) : hitDist;
+    if (MODE == NRD_HIP_SIGNAL_REBLUR_RADIANCE)
+        return REBLUR_FrontEnd_PackRadianceAndNormHitDist(radiance, hd, true);
+    if (MODE == NRD_HIP_SIGNAL_REBLUR_SH)
+        return REBLUR_FrontEnd_PackSh(radiance, hd, direction, p1, true);
+    if (MODE == NRD_HIP_SIGNAL_REBLUR_OCCLUSION)
+        return REBLUR_FrontEnd_PackRadianceAndNormHitDist(make_float3(0.0f, 0.0f, 0.0f), hd, true);
+    if (MODE == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
+        return REBLUR_FrontEnd_PackDirectionalOcclusion(direction, hd, true);
+    if (MODE == NRD_HIP_SIGNAL_RELAX_RADIANCE)
+        return RELAX_FrontEnd_PackRadianceAndHitDist(radiance, hd, true);
+    return RELAX_FrontEnd_PackSh(radiance, hd, direction, p1, true);
+}
+
+// the hit-distance channel the mode's packer writes for the single hit distance H (specular signal): normalised once (REBLUR) or clamped by RELAX's packer
+template <uint32_t MODE>
+__device__ __forceinline__ float PackedHitDist(float H, float viewZ, float r, float4 hitDistParams) {
+    float4 unused;
+    const float3 zero = make_float3(0.0f, 0.0f, 0.0f);
+    if (MODE == NRD_HIP_SIGNAL_RELAX_RADIANCE)
+        return RELAX_FrontEnd_PackRadianceAndHitDist(zero, H, true).w;
+    if (MODE == NRD_HIP_SIGNAL_RELAX_SH)
+        return RELAX_FrontEnd_PackSh(zero, H, zero, unused, true).w;
+    const float normHitDist = REBLUR_FrontEnd_GetNormHitDist(H, viewZ, hitDistParams, r);
+    if (MODE == NRD_HIP_SIGNAL_REBLUR_SH)
+        return REBLUR_FrontEnd_PackSh(zero, normHitDist, zero, unused, true).w;
+    return REBLUR_FrontEnd_PackRadianceAndNormHitDist(zero, normHitDist, true).w;
+}
+
+struct SampleSums {
+    float4 p0, p1;
+    float specHitDist; // the accumulator of NRD_FrontEnd_SpecHitDistAveraging_*
+};
+
+template <bool SPEC, uint32_t MODE>
+__device__ __forceinline__ void AddSample(SampleSums& sums, float4 s, float4 d, float trim, float viewZ, float r, float4 hitDistParams, bool demodulate, float3 factor) {
+    float3 radiance = Xyz(s);
+    float hitDist = s.w;
+    if (trim > 0.0f)
+        hitDist = NRD_FrontEnd_TrimHitDistance(hitDist, trim);
+    if (demodulate)
+        radiance = make_float3(radiance.x / factor.x, radiance.y / factor.y, radiance.z / factor.z);
+    if (SPEC)
+        NRD_FrontEnd_SpecHitDistAveraging_Add(sums.specHitDist, hitDist);
+    float4 p1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 p0 = PackSample<SPEC, MODE>(radiance, hitDist, Xyz(d), viewZ, r, hitDistParams, p1);
+    sums.p0 = make_float4(sums.p0.x + p0.x, sums.p0.y + p0.y, sums.p0.z + p0.z, sums.p0.w + p0.w);
+    sums.p1 = make_float4(sums.p1.x + p1.x, sums.p1.y + p1.y, sums.p1.z + p1.z, sums.p1.w + p1.w);
+}
+
+// a sample texel, read whole: one global_load_dwordx4 per lane in every mode (a mode that consumes .w or .xyz alone would else get a narrower load of the same sectors,
+// and a 16-byte lane stride with it: the wave still touches the whole 1 KiB segment)
+__device__ __forceinline__ float4 LoadSampleTexel(const Plane& layer, int x, int y) {
+    float4 v = LoadRGBA32F(layer, x, y);
+    NRD_LDS_WHOLE_TEXEL(v);
+    return v;
+}
+
+// One signal of one pixel over `num` sample layers, the mode a template argument: the wave-uniform switch sits outside the sample loop (PackSignalSamples).
+// Layer bases advance by scalar 64-bit additions; a lane's byte offset inside a layer is computed once. The loads of four layers are issued before the first of
+// them is consumed (a wave reads one contiguous 1 KiB segment per layer and plane), the remaining num & 3 layers one by one.
+template <bool SPEC, uint32_t MODE>
+__device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, uint64_t inLayer, uint64_t dirLayer, uint32_t num, float trim,
+    int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
+    constexpr bool kDirection = MODE == NRD_HIP_SIGNAL_REBLUR_SH || MODE == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION || MODE == NRD_HIP_SIGNAL_RELAX_SH;
+    constexpr bool kSh = MODE == NRD_HIP_SIGNAL_REBLUR_SH || MODE == NRD_HIP_SIGNAL_RELAX_SH;
+    constexpr uint32_t kBatch = 4;
+    const float r = SPEC ? roughness : 1.0f;
+    // -0 is the identity of the addition ( -0 + p == p bit for bit, also for p = -0 and p = +0 ): the sums below are ( ( P_0 + P_1 ) + P_2 ) + ...
+    SampleSums sums = {make_float4(-0.0f, -0.0f, -0.0f, -0.0f), make_float4(-0.0f, -0.0f, -0.0f, -0.0f), NRD_FrontEnd_SpecHitDistAveraging_Begin()};
+    Plane layer = AsPlane(in, w, h), dirLayerPlane = AsPlane(kDirection ? dirPlane : in, w, h);
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uint32_t s = 0;
+    for (; s + kBatch <= num; s += kBatch) {
+        float4 t[kBatch], d[kBatch];
+#pragma unroll
+        for (uint32_t k = 0; k < kBatch; k++) {
+            t[k] = LoadSampleTexel(layer, x, y);
+            d[k] = kDirection ? LoadSampleTexel(dirLayerPlane, x, y) : zero;
+            layer.ptr += inLayer;
+            dirLayerPlane.ptr += dirLayer;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kBatch; k++)
+            AddSample<SPEC, MODE>(sums, t[k], d[k], trim, viewZ, r, hitDistParams, demodulate, factor);
+    }
+    for (; s < num; s++) {
+        const float4 t = LoadSampleTexel(layer, x, y);
+        const float4 d = kDirection ? LoadSampleTexel(dirLayerPlane, x, y) : zero;
+        layer.ptr += inLayer;
+        dirLayerPlane.ptr += dirLayer;
+        AddSample<SPEC, MODE>(sums, t, d, trim, viewZ, r, hitDistParams, demodulate, factor);
+    }
+    const float n = float(num);
+    float4 p0 = make_float4(sums.p0.x / n, sums.p0.y / n, sums.p0.z / n, sums.p0.w / n);
+    if (SPEC) {
+        NRD_FrontEnd_SpecHitDistAveraging_End(sums.specHitDist);
+        p0.w = PackedHitDist<MODE>(sums.specHitDist, viewZ, r, hitDistParams);
+    }
+    const Plane o0 = AsPlane(out0, w, h);
+    if (MODE == NRD_HIP_SIGNAL_REBLUR_OCCLUSION)
+        StoreR16Unorm(o0, xo, y, p0.w);
+    else if (MODE == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
+        StoreRGBA16Snorm(o0, xo, y, p0);
+    else
+        StoreRGBA16F(o0, xo, y, p0);
+    if (kSh)
+        StoreRGBA16F(AsPlane(out1, w, h), xo, y, make_float4(sums.p1.x / n, sums.p1.y / n, sums.p1.z / n, sums.p1.w / n));
+}
+
+#define NRD_REDUCE_SIGNAL(MODE) \
+    case MODE: \
+        ReduceSignal<SPEC, MODE>(in, dirPlane, out0, out1, inLayer, dirLayer, num, trim, x, xo, y, w, h, viewZ, roughness, hitDistParams, demodulate, factor); \
+        break;
+template <bool SPEC>
+__device__ __forceinline__ void PackSignalSamples(uint32_t mode, const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, uint64_t inLayer, uint64_t dirLayer, uint32_t num,
+    float trim, int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
+    switch (mode) { // wave-uniform: a kernel argument
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_RADIANCE)
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_SH)
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_OCCLUSION)
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_RELAX_RADIANCE)
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_RELAX_SH)
+        default:
+            break;
+    }
+}
+#undef NRD_REDUCE_SIGNAL
+
 // motion is clamped to +-FP16_MAX as raytracingdenoiser_amd/synth.py clamps it: infinities land on the bounds, a NaN stays a NaN (fminf / fmaxf alone would turn it into a bound)
 __device__ __forceinline__ float ClampToHalf(float v) { return isnan(v) ? v : fminf(fmaxf(v, -NRD_FP16_MAX), NRD_FP16_MAX); }
 
 // One pixel of the front end. CHECKERBOARD (nrdHipPackInputsEx, NRDSettings.h:35-44): a pixel carries the data of ONE signal -- the diffuse one where
 // ( ( x ^ y ) ^ frameIndex ) & 1 == diffCell (nrdmath.h CheckerBoard), the specular one elsewhere -- and its texel goes to column x >> 1: the left half of the plane.
 // Only those pixels of a signal's fp32 planes are read and no other texel of its packed planes is written.
-template <bool CHECKERBOARD>
-__device__ __forceinline__ void PackPixel(const PackArgs& a, uint32_t diffCell, uint32_t frameIndex) {
+// SAMPLES (nrdHipPackInputsSamples): each signal is reduced over its sample layers (PackSignalSamples); the other kernels never look at `sa`.
+template <bool CHECKERBOARD, bool SAMPLES>
+__device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& sa, uint32_t diffCell, uint32_t frameIndex) {
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
     const int w = a.w, h = a.h;
     if (x >= w || y >= h)
@@ -154,10 +298,19 @@ __device__ __forceinline__ void PackPixel(const PackArgs& a, uint32_t diffCell, 
     }
     const bool diffHere = !CHECKERBOARD || ((((uint32_t)x ^ (uint32_t)y) ^ frameIndex) & 1u) == diffCell;
     const int xo = CHECKERBOARD ? x >> 1 : x;
-    if (a.diffMode && diffHere)
-        PackSignal<false>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, diffFactor);
-    if (a.specMode && (!CHECKERBOARD || !diffHere))
-        PackSignal<true>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, specFactor);
+    if (SAMPLES) {
+        if (a.diffMode && diffHere)
+            PackSignalSamples<false>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sa.diffInLayer, sa.diffDirLayer, sa.diffNum, sa.trim, x, xo, y, w, h, viewZ, roughness, a.hitDistParams,
+                a.demodulate != 0u, diffFactor);
+        if (a.specMode && (!CHECKERBOARD || !diffHere))
+            PackSignalSamples<true>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, sa.specInLayer, sa.specDirLayer, sa.specNum, sa.trim, x, xo, y, w, h, viewZ, roughness, a.hitDistParams,
+                a.demodulate != 0u, specFactor);
+    } else {
+        if (a.diffMode && diffHere)
+            PackSignal<false>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, diffFactor);
+        if (a.specMode && (!CHECKERBOARD || !diffHere))
+            PackSignal<true>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, specFactor);
+    }
 
     if (a.outPenumbra.ptr || a.outTranslucency.ptr) {
         const float distanceToOccluder = LoadR32F(AsPlane(a.occluder, w, h), x, y);
@@ -168,9 +321,15 @@ __device__ __forceinline__ void PackPixel(const PackArgs& a, uint32_t diffCell, 
     }
 }
 
-__global__ void __launch_bounds__(256) PackInputsKernel(const PackArgs a) { PackPixel<false>(a, 0u, 0u); }
+__global__ void __launch_bounds__(256) PackInputsKernel(const PackArgs a) { PackPixel<false, false>(a, SampleArgs{}, 0u, 0u); }
 
-__global__ void __launch_bounds__(256) PackCheckerboardKernel(const PackArgs a, const uint32_t diffCell, const uint32_t frameIndex) { PackPixel<true>(a, diffCell, frameIndex); }
+__global__ void __launch_bounds__(256) PackCheckerboardKernel(const PackArgs a, const uint32_t diffCell, const uint32_t frameIndex) { PackPixel<true, false>(a, SampleArgs{}, diffCell, frameIndex); }
+
+// the multi-sample twin of the two (nrdHipPackInputsSamples with more than one sample layer or a trim threshold), templated on checkerboard like them
+template <bool CHECKERBOARD>
+__global__ void __launch_bounds__(256) PackSamplesKernel(const PackArgs a, const SampleArgs sa, const uint32_t diffCell, const uint32_t frameIndex) {
+    PackPixel<CHECKERBOARD, true>(a, sa, diffCell, frameIndex);
+}
 
 __device__ __forceinline__ float4 LoadSignalTexel(const FePlane& p, bool wide, int x, int y, int w, int h) {
     return wide ? LoadRGBA32F(AsPlane(p, w, h), x, y) : LoadRGBA16F(AsPlane(p, w, h), x, y);
@@ -517,7 +676,32 @@ void BackEndSignal(Checker& c, const NrdHipBackEndSignal& s, const char* name, F
 
 extern "C" __attribute__((visibility("default"))) const char* nrdHipGetLastFrontEndError(void) { return t_LastError.c_str(); }
 
-extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsEx(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, void* hipStream) {
+namespace {
+
+// the rules of NrdHipFrontEndSamples that need no plane; num: the signal's sample count, 0 read as 1
+uint32_t CheckSamples(const NrdHipSignalSamples& s, uint32_t mode, const char* name, uint32_t& num) {
+    const std::string n = std::string("nrdHipPackInputsSamples: samples: ") + name;
+    num = s.samplesNum ? s.samplesNum : 1u;
+    if (s.samplesNum > 64u)
+        return Fail(nrd::Result::INVALID_ARGUMENT, n + ".samplesNum: more than 64 sample layers");
+    if (s.reserved)
+        return Fail(nrd::Result::INVALID_ARGUMENT, n + ".reserved: must be 0");
+    if (num > 1u && mode == NRD_HIP_SIGNAL_NONE)
+        return Fail(nrd::Result::INVALID_ARGUMENT, n + ".samplesNum: sample layers given for a signal whose mode is NONE");
+    return (uint32_t)nrd::Result::SUCCESS;
+}
+
+// a layer stride of a plane the kernel reads `num` > 1 layers of
+void CheckLayerBytes(Checker& c, uint64_t layerBytes, const FePlane& plane, uint32_t num, const char* field) {
+    if (c.Failed() || num <= 1u || !plane.ptr)
+        return;
+    if (layerBytes % 16u)
+        c.Error(nrd::Result::INVALID_ARGUMENT, field, "the layer stride is not a multiple of 16 (the texel size)");
+    else if (layerBytes < (uint64_t)plane.pitch * c.h)
+        c.Error(nrd::Result::INVALID_ARGUMENT, field, "the layer stride is below rowPitchBytes x height of the plane");
+}
+
+uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, void* hipStream) {
     using F = nrd::Format;
     if (!d)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputs: null descriptor");
@@ -528,6 +712,20 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsEx(co
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsEx: options: unknown checkerboardMode");
     if (checkerboardMode && d->diffuse.mode == NRD_HIP_SIGNAL_NONE && d->specular.mode == NRD_HIP_SIGNAL_NONE)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsEx: options: checkerboardMode without a diffuse or a specular signal to checkerboard");
+    SampleArgs sa = {};
+    sa.diffNum = sa.specNum = 1u;
+    if (samples) {
+        if (uint32_t r = CheckSamples(samples->diffuse, d->diffuse.mode, "diffuse", sa.diffNum))
+            return r;
+        if (uint32_t r = CheckSamples(samples->specular, d->specular.mode, "specular", sa.specNum))
+            return r;
+        if (samples->reserved)
+            return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsSamples: samples: reserved: must be 0");
+        if (!(samples->hitDistTrimThreshold >= 0.0f)) // (a NaN fails every comparison)
+            return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsSamples: samples: hitDistTrimThreshold: negative or NaN");
+        sa.trim = samples->hitDistTrimThreshold;
+    }
+    const bool multiSample = sa.diffNum > 1u || sa.specNum > 1u || sa.trim > 0.0f; // else: the kernels of nrdHipPackInputsEx, the same bytes, no extra loads
     Checker c{"nrdHipPackInputs"};
     PackArgs a = {};
     a.normalRoughness = c.Check(d->normalRoughness, "normalRoughness", "required", F::RGBA32_SFLOAT);
@@ -547,6 +745,14 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsEx(co
     a.rf0 = c.Check(d->rf0, "rf0", demodulate ? "demodulation needs albedo and rf0" : nullptr, F::RGBA32_SFLOAT);
     FrontEndSignal(c, d->diffuse, "diffuse", a.diffIn, a.diffDir, a.diffOut0, a.diffOut1);
     FrontEndSignal(c, d->specular, "specular", a.specIn, a.specDir, a.specOut0, a.specOut1);
+    if (multiSample && samples) {
+        c.entry = "nrdHipPackInputsSamples";
+        CheckLayerBytes(c, sa.diffInLayer = samples->diffuse.radianceHitDistLayerBytes, a.diffIn, sa.diffNum, "samples: diffuse.radianceHitDistLayerBytes");
+        CheckLayerBytes(c, sa.diffDirLayer = samples->diffuse.directionLayerBytes, a.diffDir, sa.diffNum, "samples: diffuse.directionLayerBytes");
+        CheckLayerBytes(c, sa.specInLayer = samples->specular.radianceHitDistLayerBytes, a.specIn, sa.specNum, "samples: specular.radianceHitDistLayerBytes");
+        CheckLayerBytes(c, sa.specDirLayer = samples->specular.directionLayerBytes, a.specDir, sa.specNum, "samples: specular.directionLayerBytes");
+        c.entry = "nrdHipPackInputs";
+    }
     if (demodulate)
         Camera(c, d->commonSettings, "demodulation needs the frame's camera", a.camera);
     if (c.Failed())
@@ -560,12 +766,29 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsEx(co
     a.w = c.w;
     a.h = c.h;
     t_LastError.clear();
-    if (checkerboardMode) // BLACK: the diffuse signal lives in cell 0, the specular one in cell 1 (reference Reblur.cpp:318-330, Relax.cpp:88-97); WHITE: the opposite
+    const dim3 grid((c.w + 63u) / 64u, (c.h + 3u) / 4u), block(64, 4);
+    if (multiSample) {
+        const uint32_t diffCell = checkerboardMode == (uint32_t)nrd::CheckerboardMode::BLACK ? 0u : 1u, frameIndex = options ? options->frameIndex & 1u : 0u;
+        if (checkerboardMode)
+            hipLaunchKernelGGL(PackSamplesKernel<true>, grid, block, 0, (hipStream_t)hipStream, a, sa, diffCell, frameIndex);
+        else
+            hipLaunchKernelGGL(PackSamplesKernel<false>, grid, block, 0, (hipStream_t)hipStream, a, sa, 0u, 0u);
+    } else if (checkerboardMode) // BLACK: the diffuse signal lives in cell 0, the specular one in cell 1 (reference Reblur.cpp:318-330, Relax.cpp:88-97); WHITE: the opposite
         hipLaunchKernelGGL(PackCheckerboardKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a,
             checkerboardMode == (uint32_t)nrd::CheckerboardMode::BLACK ? 0u : 1u, options->frameIndex & 1u);
     else
         hipLaunchKernelGGL(PackInputsKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a);
     return hipGetLastError() == hipSuccess ? (uint32_t)nrd::Result::SUCCESS : Fail(nrd::Result::FAILURE, "nrdHipPackInputs: the kernel launch failed");
+}
+
+} // namespace
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsEx(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, void* hipStream) {
+    return PackInputs(d, options, nullptr, hipStream);
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsSamples(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, void* hipStream) {
+    return PackInputs(d, options, samples, hipStream);
 }
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputs(const NrdHipFrontEndDesc* d, void* hipStream) { return nrdHipPackInputsEx(d, nullptr, hipStream); }

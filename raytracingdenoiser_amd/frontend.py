@@ -6,6 +6,7 @@ C-ABI; it computes nothing (no arithmetic on tensors, no fallback). Planes are C
 memory" is host memory (the CPU emulation of the device sources that the test-suite builds).
 """
 import ctypes as C
+import inspect
 
 import numpy as np
 
@@ -74,8 +75,8 @@ def _fp32_plane(t, channels, what):
 
 
 def rgba(xyz, w=None):
-    """[H, W, 3] (+ [H, W]) -> a new [H, W, 4] array: copies only (the planes of the C-ABI are RGBA32_SFLOAT)"""
-    out = _empty(xyz, tuple(xyz.shape[:2]) + (4,), "float32")
+    """[H, W, 3] (+ [H, W]) -> a new [H, W, 4] array, [N, H, W, 3] (+ [N, H, W]) -> a new [N, H, W, 4] one: copies only (the planes of the C-ABI are RGBA32_SFLOAT)"""
+    out = _empty(xyz, tuple(xyz.shape[:-1]) + (4,), "float32")
     out[..., :3] = xyz
     if w is None:
         out[..., 3] = 0.0
@@ -90,6 +91,28 @@ def _rgba_arg(t, what):
     elif t.ndim == 3 and t.shape[2] == 3:
         t = rgba(t)
     return t, _fp32_plane(t, 4, what)
+
+
+def _layers(t):
+    """(is it a stack of sample layers, N, bytes from one layer to the next) of a signal argument: [N, H, W, 4], [N, H, W, 3] or an ([N, H, W, 3], [N, H, W]) pair are stacks --
+    a three-channel stack is widened into a dense copy -- anything else is one layer"""
+    first = t[0] if isinstance(t, (tuple, list)) else t
+    if first.ndim != 4:
+        return False, 1, 0
+    if isinstance(t, (tuple, list)) or first.shape[3] == 3:
+        return True, first.shape[0], first.shape[1] * first.shape[2] * 16
+    return True, first.shape[0], (first.strides[0] if _is_numpy(first) else first.stride(0) * first.element_size())
+
+
+def _signal_arg(t, what):
+    """_rgba_arg for a signal plane that may be a stack of sample layers: the plane is that of layer 0"""
+    if not _layers(t)[0]:
+        return _rgba_arg(t, what)
+    if isinstance(t, (tuple, list)):
+        t = rgba(*t)
+    elif t.shape[3] == 3:
+        t = rgba(t)
+    return t, _fp32_plane(t[0], 4, what)
 
 
 def _stream(like, stream):
@@ -145,11 +168,19 @@ def _reuse(out, key, like, shape, dtype):
 def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0, **kw):
     """see describe_pack; launches on `stream` (a torch.cuda.Stream, or a raw handle with four-channel inputs only; default: the current stream) and returns the packed planes.
     checkerboard_mode (api.CheckerboardMode) other than OFF: the noisy signals are traced for every other pixel of frame `frame_index` (CommonSettings::frameIndex) and their
-    texels go to the left half of the signal planes, whose other texels are left as they are (NRDHip.h nrdHipPackInputsEx)."""
+    texels go to the left half of the signal planes, whose other texels are left as they are (NRDHip.h nrdHipPackInputsEx). A signal given as a stack of sample layers
+    ([N, H, W, 4]: many paths per pixel) or hit_dist_trim != 0 goes through nrdHipPackInputsSamples, which reduces the layers by the reference's rules in the same launch;
+    every other call is the call it was."""
     with _stream_scope(viewz, kw.get("stream")):
         res, d, keep = describe_pack(normal_roughness, viewz, *args, **kw)
         lib = kw.get("lib") or api.load_library()
-        if int(checkerboard_mode) == 0:
+        given = inspect.signature(describe_pack).bind(normal_roughness, viewz, *args, **kw).arguments
+        layered = any(_layers(sig[k])[0] for sig in (given.get("diffuse"), given.get("specular")) if sig for k in ("radiance_hitdist", "direction") if sig.get(k) is not None)
+        if layered or given.get("hit_dist_trim", 0.0) != 0.0:  # many paths per pixel (NRDHip.h nrdHipPackInputsSamples)
+            samples = pack_samples(given.get("diffuse"), given.get("specular"), given.get("hit_dist_trim", 0.0))
+            options = pack_options(checkerboard_mode, frame_index)
+            _check(lib, lib.nrdHipPackInputsSamples(C.byref(d), C.byref(options), C.byref(samples), _stream(viewz, kw.get("stream"))), "nrdHipPackInputsSamples")
+        elif int(checkerboard_mode) == 0:
             _check(lib, lib.nrdHipPackInputs(C.byref(d), _stream(viewz, kw.get("stream"))), "nrdHipPackInputs")
         else:
             options = pack_options(checkerboard_mode, frame_index)
@@ -162,13 +193,31 @@ def pack_options(checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0):
     return api.HipFrontEndOptions(int(checkerboard_mode), int(frame_index) & 0xFFFFFFFF)
 
 
+def pack_samples(diffuse=None, specular=None, hit_dist_trim=0.0):
+    """api.HipFrontEndSamples for nrdHipPackInputsSamples, next to the descriptor of describe_pack, from the same diffuse / specular dicts: the sample counts and the layer
+    strides (the arrays' stride(0); a three-channel stack or a pair is widened by describe_pack into a dense [N, H, W, 4] copy). hit_dist_trim > 0: every sample's hit
+    distance goes through NRD_FrontEnd_TrimHitDistance first."""
+    samples = api.HipFrontEndSamples()
+    samples.hitDistTrimThreshold = float(hit_dist_trim)
+    for sig, dst in ((diffuse, samples.diffuse), (specular, samples.specular)):
+        if sig is None:
+            continue
+        _, dst.samplesNum, dst.radianceHitDistLayerBytes = _layers(sig["radiance_hitdist"])
+        if sig.get("direction") is not None:
+            _, n, dst.directionLayerBytes = _layers(sig["direction"])
+            assert n == dst.samplesNum, "direction and radiance_hitdist must have the same number of sample layers"
+    return samples
+
+
 def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffuse=None, specular=None, albedo=None, rf0=None, distance_to_occluder=None, translucency=None,
-                  common_settings=None, hit_dist_params=HIT_DIST_PARAMS, viewz_scale=1.0, tan_of_light_angular_radius=0.0, out=None, stream=None, lib=None):
+                  common_settings=None, hit_dist_params=HIT_DIST_PARAMS, viewz_scale=1.0, tan_of_light_angular_radius=0.0, out=None, stream=None, lib=None, hit_dist_trim=0.0):
     """The descriptor of one nrdHipPackInputs launch, without launching: (packed planes, api.HipFrontEndDesc, arrays the descriptor points into besides its arguments) -- for a
     caller that launches the same frame layout repeatedly through the C-ABI itself. fp32 inputs: normal_roughness [H, W, 4] (or a (normal [H, W, 3], roughness [H, W]) pair), viewz [H, W], material_id [H, W],
     motion [H, W, 4] or [H, W, 2], albedo / rf0 / translucency [H, W, 4] or [H, W, 3], distance_to_occluder [H, W]; diffuse / specular: dict(mode=SignalMode,
     radiance_hitdist=[H, W, 4] or (radiance [H, W, 3], hit_dist [H, W]), direction=[H, W, 4] or [H, W, 3] for the SH / directional modes). albedo + rf0 +
-    common_settings switch demodulation on. Returns {ResourceType: (packed array, Format)}, ready for HipExecutor.bind_packed; `out` = a dict returned earlier, whose
+    common_settings switch demodulation on. Many paths per pixel: a signal's radiance_hitdist may be [N, H, W, 4] or ([N, H, W, 3], [N, H, W]) and its direction
+    [N, H, W, 4] or [N, H, W, 3] with the same N (layers may be pitched or padded: the layer stride is stride(0)); the descriptor then holds layer 0 and pack_samples
+    the rest, with hit_dist_trim, for nrdHipPackInputsSamples. Returns {ResourceType: (packed array, Format)}, ready for HipExecutor.bind_packed; `out` = a dict returned earlier, whose
     arrays are written again instead of allocating."""
     d = api.HipFrontEndDesc()
     keep = []  # widened copies must outlive the launch call
@@ -211,10 +260,10 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
             continue
         mode = SignalMode(sig["mode"])
         dst.mode = int(mode)
-        t, dst.radianceHitDist = _rgba_arg(sig["radiance_hitdist"], which + " radiance_hitdist")
+        t, dst.radianceHitDist = _signal_arg(sig["radiance_hitdist"], which + " radiance_hitdist")
         keep.append(t)
         if sig.get("direction") is not None:
-            t, dst.direction = _rgba_arg(sig["direction"], which + " direction")
+            t, dst.direction = _signal_arg(sig["direction"], which + " direction")
             keep.append(t)
         slot0, slot1 = signal_slots(which, mode, "IN")
         dtype, ch, fmt = _SIGNAL_OUT[mode]

@@ -5,7 +5,11 @@ Also records what the compiler made of the kernels (VGPRs, waves per SIMD, scrat
 --rejitter adds, in the same run, an SH plane set (REBLUR_SH for both signals in fp16 planes): (a) nrdHipResolveOutputs with resolve = SG, (b) nrdHipResolveOutputsEx with
 reJitter = 1 on the same planes, both against the copy rate, (b) once more from --ab-library (a build of the re-jitter form that did not ship:
 python tools/build_variant.py rejitter_plain -DNRD_REJITTER_TILE=0), and nrdHipPackInputsEx with checkerboardMode = BLACK on the plane set of `pack`.
-usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]]"""
+--samples [N ...] (default 4) is a run of its own with an output file of its own (profiles/frontend_samples_bench.json): many paths per pixel, REBLUR_RADIANCE on both signals, N sample
+layers each. Alternated in one process: (a) nrdHipPackInputsSamples, (b) the best composition there was before it -- torch reductions to the same two single-sample planes (mean for the
+radiance and the diffuse hit distance, masked amin for the specular one) followed by nrdHipPackInputs -- and (c) the plain single-sample pack, for scale; with the algorithmic bytes of (a),
+its GB/s and its fraction of the copy rate of the same run, and the static facts of the kernel (samples_isa()). The run fails if (a) is slower than (b).
+usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]]"""
 import argparse
 import ctypes as C
 import json
@@ -73,6 +77,136 @@ def options_isa(extra=()):
     tile = re.search(r"constexpr int kReJitterTileW = (\d+), kReJitterTileH = (\d+);", open(SRC).read())
     out["rejitter"]["declared_tile_bytes"] = (int(tile.group(1)) + 2) * (int(tile.group(2)) + 2) * 16
     return out
+
+
+def _loop_loads(body):
+    """{instruction: count} of the vector-memory loads inside the loops of one kernel of a listing: the instructions between a label and a later branch back to it"""
+    lines = body.split("\n")
+    label_at = {m.group(1): i for i, l in enumerate(lines) for m in [re.match(r"(\.LBB\d+_\d+):", l)] if m}
+    inside = set()
+    for i, l in enumerate(lines):
+        m = re.match(r"\ts_c?branch\w*\s+(\.LBB\d+_\d+)", l)
+        if m and label_at.get(m.group(1), i) < i:
+            inside.update(range(label_at[m.group(1)], i))
+    out = {}
+    for i in sorted(inside):
+        ins = lines[i].strip().split()[0] if lines[i].startswith("\t") and lines[i].strip() else ""
+        if ins.startswith(("global_load", "buffer_load", "flat_load", "scratch_load")):
+            out[ins] = out.get(ins, 0) + 1
+    return out
+
+
+def samples_isa():
+    """static facts about the two instantiations of the kernel behind nrdHipPackInputsSamples (the `isa_samples` object of profiles/frontend_samples_bench.json), as isa():
+    "pack_samples" and "pack_samples_checkerboard"; sample_loop_loads: the loads inside the kernel's loops -- the sample loops are its only ones"""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_frontend.s")
+        flags = [f for f in B._flags(SRC) if f not in ("-x", "hip")]
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+        txt = open(listing).read()
+    out = {}
+    for mangled, s in stats.items():
+        if "PackSamplesKernel" not in mangled:
+            continue
+        name = "pack_samples_checkerboard" if "ILb1E" in mangled else "pack_samples"
+        c = s["counter"]
+        body = txt[txt.index("\n" + mangled + ":"):].split(".Lfunc_end")[0]
+        out[name] = {"vgprs": s["vgpr"], "waves_per_simd": s["occ"], "scratch_bytes": s["scratch"], "lds_bytes": s["ldsb"], "valu": s["valu"], "salu": s["salu"], "vmem": s["vmem"],
+                     "global_load_dwordx4": c.get("global_load_dwordx4", 0), "v_div_scale_f32": c.get("v_div_scale_f32", 0), "transcendental": s["trans"],
+                     "sample_loop_loads": _loop_loads(body)}
+    assert set(out) == {"pack_samples", "pack_samples_checkerboard"}, list(stats)
+    return out
+
+
+def samples_main(args):
+    """--samples: see the module text"""
+    result = {"isa_samples": samples_isa()}
+    if args.isa_only:
+        print(json.dumps(result))
+        return
+    import torch
+
+    from raytracingdenoiser_amd import api, frontend
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    w, h = args.width, args.height
+    px = w * h
+    g = torch.Generator(device="cuda").manual_seed(7)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    n = rand(h, w, 3) * 2.0 - 1.0
+    n = n / n.norm(dim=-1, keepdim=True).clamp_min(1e-6)
+    nr = torch.cat([n, rand(h, w, 1)], -1).contiguous()
+    viewz, material, motion = 0.5 + rand(h, w) * 100.0, torch.floor(rand(h, w) * 4.0), rand(h, w, 4) - 0.5
+    lib = api.load_library()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    mode = frontend.SignalMode.REBLUR_RADIANCE
+    scale = torch.tensor([4.0, 3.0, 5.0, 30.0], device="cuda")
+    gbuffer_read = {"normal_roughness RGBA32_SFLOAT": 16, "viewZ R32_SFLOAT": 4, "materialID R32_SFLOAT": 4, "motion RGBA32_SFLOAT": 16}
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(args.reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / args.reps
+
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
+    result.update({"device": torch.cuda.get_device_name(0), "width": w, "height": h, "reps": args.reps, "warmup": args.warmup, "copy_gigabytes_per_second": gbps.value,
+                   "planes": "REBLUR_RADIANCE on both signals, N sample layers each ([N, H, W, 4] fp32), normal + roughness, viewZ, materialID, motion",
+                   "times_are": "device events around --reps back-to-back calls, per call, the best of two alternated rounds", "samples": {}})
+    slower = []
+    for count in args.samples:
+        diff, spec = rand(count, h, w, 4) * scale, rand(count, h, w, 4) * scale
+        spec[..., 3] *= (rand(count, h, w) > 0.25)  # a quarter of the specular paths miss: hit distance 0
+        sig = lambda t: dict(mode=mode, radiance_hitdist=t)
+        packed, desc, keep = frontend.describe_pack(nr, viewz, material_id=material, motion=motion, diffuse=sig(diff), specular=sig(spec))
+        samples = frontend.pack_samples(sig(diff), sig(spec))
+        one_diff, one_spec = torch.empty(h, w, 4, device="cuda"), torch.empty(h, w, 4, device="cuda")
+        _, desc_one, keep_one = frontend.describe_pack(nr, viewz, material_id=material, motion=motion, diffuse=sig(one_diff), specular=sig(one_spec), out=packed)
+        inf = torch.tensor(float("inf"), device="cuda")
+        zero = torch.zeros((), device="cuda")
+
+        def new_call():
+            assert lib.nrdHipPackInputsSamples(C.byref(desc), None, C.byref(samples), stream) == 0
+
+        def composition():
+            torch.mean(diff, dim=0, out=one_diff)
+            torch.mean(spec, dim=0, out=one_spec)
+            hit = spec[..., 3]
+            smallest = torch.where(hit == 0, inf, hit).amin(0)
+            one_spec[..., 3] = torch.where(smallest == inf, zero, smallest)
+            assert lib.nrdHipPackInputs(C.byref(desc_one), stream) == 0
+
+        def plain():
+            assert lib.nrdHipPackInputs(C.byref(desc_one), stream) == 0
+
+        rounds = [{"samples_ms": timed(new_call), "torch_reduce_then_pack_ms": timed(composition), "plain_pack_ms": timed(plain)} for _ in range(2)]
+        best = {k: min(r[k] for r in rounds) for k in rounds[0]}
+        read = dict(gbuffer_read, **{"diffuse radiance_hitdist RGBA32_SFLOAT x N": 16 * count, "specular radiance_hitdist RGBA32_SFLOAT x N": 16 * count})
+        write_bytes = sum(t.numel() * t.element_size() for t, fmt in packed.values()) // px  # counted from the planes the call writes
+        total = sum(read.values()) + write_bytes
+        rate = total * px / (best["samples_ms"] * 1e-3) / 1e9
+        result["samples"][str(count)] = dict(best, rounds=rounds, read_bytes_per_pixel=read, write_bytes_per_pixel=write_bytes, bytes_per_pixel=total, gigabytes_per_second=rate,
+                                             fraction_of_copy_rate=rate / gbps.value, samples_over_torch_reduce_then_pack=best["samples_ms"] / best["torch_reduce_then_pack_ms"],
+                                             samples_over_plain_pack=best["samples_ms"] / best["plain_pack_ms"])
+        if best["samples_ms"] > best["torch_reduce_then_pack_ms"]:
+            slower.append(count)
+        del diff, spec, one_diff, one_spec, packed, keep, keep_one
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.samples_out), exist_ok=True)
+    with open(args.samples_out, "w") as fp:
+        json.dump(result, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps({k: v for k, v in result.items() if k != "isa_samples"}))
+    assert not slower, "nrdHipPackInputsSamples is slower than torch reductions + nrdHipPackInputs at N = %s: the kernel is not finished" % slower
 
 
 def synth_pack(raw, synth, torch):
@@ -149,7 +283,12 @@ def main():
     ap.add_argument("--isa-only", action="store_true", help="no GPU needed: print the static facts and leave")
     ap.add_argument("--rejitter", action="store_true", help="also time the SH plane set: SG resolve, SG resolve + re-jitter (nrdHipResolveOutputsEx), and the checkerboard pack")
     ap.add_argument("--ab-library", help="with --rejitter: a build of the other re-jitter form (-DNRD_REJITTER_TILE=0), timed on the same planes in the same rounds")
+    ap.add_argument("--samples", type=int, nargs="*", help="a run of its own: nrdHipPackInputsSamples with N sample layers per signal (default 4) against torch reductions + nrdHipPackInputs")
+    ap.add_argument("--samples-out", default=os.path.join(ROOT, "profiles", "frontend_samples_bench.json"))
     args = ap.parse_args()
+    if args.samples is not None:
+        args.samples = args.samples or [4]
+        return samples_main(args)
     result = {"isa": isa(), "isa_options": options_isa()}
     if args.isa_only:  # the static half of the record: nothing here is a time
         print(json.dumps(result))
