@@ -1290,7 +1290,7 @@ void HistoryClamping(const PassIO& io) {
             if (gIn_Tiles.Load(px >> 4, py >> 4).x != 0.0f)
                 continue;
             // group-shared data, read at rect-clamped coordinates; NOTE: raw viewZ (no scale, no abs) as in the reference
-            auto IsValid = [&](int x, int y) { return Cmp(gIn_ViewZ.Load(clamp(x, 0, rectW - 1), clamp(y, 0, rectH - 1)).x < c.gDenoisingRange); };
+            auto IsValid = [&](int x, int y) { return Cmp(abs(gIn_ViewZ.Load(clamp(x, 0, rectW - 1), clamp(y, 0, rectH - 1)).x) < c.gDenoisingRange); };  // (the magnitude: DESIGN.md section 4)
             if (IsValid(px, py) == 0.0f)
                 continue;
 

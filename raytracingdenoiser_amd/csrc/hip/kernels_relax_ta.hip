@@ -1019,7 +1019,9 @@ __global__ __launch_bounds__(256, NRD_WAVES_RELAX_HC) void RelaxHistoryClampingK
     for (int idx = threadIdx.x; idx < hc::BUF_X * hc::BUF_Y; idx += 256) {
         int lx = idx % hc::BUF_X, ly = idx / hc::BUF_X;
         int gx = ClampI(BlockTileX(rows) * TILE_X - hc::BORDER + lx, 0, rectW - 1), gy = ClampI(blockY * TILE_Y - hc::BORDER + ly, 0, rectH - 1);
-        float isValid = Cmp(LoadR32F(P.viewZ, gx, gy) < c.shared.gDenoisingRange); // raw viewZ as in the reference
+        // unscaled viewZ as in the reference, but its MAGNITUDE: RELAX_HistoryClamping.hlsli:25-26 compares the signed texel, which calls every texel of a right-handed
+        // host (negative view depth), the sky included, valid -- the one place where a negated depth plane changed the result
+        float isValid = Cmp(Abs(LoadR32F(P.viewZ, gx, gy)) < c.shared.gDenoisingRange);
         int li = ly * hc::BUF_STRIDE + lx;
         if (SPEC) {
             float4 f = LoadRGBA16F(P.spec.fast, gx, gy);

@@ -166,7 +166,7 @@ def denoiser_settings(name, frame, overrides=None):
     if name.startswith("REBLUR"):
         s = api.ReblurSettings(**(overrides or {}))
     elif name.startswith("SIGMA_SHADOW"):
-        s = api.SigmaSettings(lightDirection=frame["light_dir"], **(overrides or {}))
+        s = api.SigmaSettings(**{"lightDirection": frame["light_dir"], **(overrides or {})})  # (an override may name another light direction)
     elif name.startswith("RELAX"):
         s = api.RelaxSettings(**(overrides or {}))
     else:

@@ -79,7 +79,7 @@ class PassStats:
             err = np.where(np.isnan(err), np.inf, err)
             # storage granularity: one unit in the last place of the stored format is as close as two correct implementations can be held
             if kind == "f16":
-                ulp = np.maximum(np.abs(b), 6.1e-5) * 2.0 ** -10
+                ulp = np.maximum(np.abs(b), 2.0 ** -14) * 2.0 ** -10  # (below 2^-14 the format is denormal: one unit is 2^-24 exactly -- 6.1e-5 here called such neighbours two apart)
                 one_ulp = np.abs(a - b) <= ulp * 1.0001
             else:
                 one_ulp = np.zeros(a.shape, bool)

@@ -24,13 +24,13 @@ def _expected_world_space_rows(cs, viewz, row_begin, row_end, denoising_range):
     ys, xs = np.meshgrid(np.arange(h) + 0.5, np.arange(w) + 0.5, indexing="ij")
     u, v = xs / w, ys / h
     nx, ny = u * 2.0 - 1.0, -(v * 2.0 - 1.0)
-    zv = sign * np.abs(viewz.astype(np.float64))
+    zv = sign * np.abs(viewz.astype(np.float64)) * float(cs.viewZScale)  # (view depth as the host wrote it, times CommonSettings::viewZScale; either handedness)
     cw = P[3, 2] * zv + P[3, 3]
     view = np.stack([(nx * cw - P[0, 2] * zv - P[0, 3]) / P[0, 0], (ny * cw - P[1, 2] * zv - P[1, 3]) / P[1, 1], zv, np.ones_like(zv)]).reshape(4, -1)
     clip = (Pp @ Vp @ np.linalg.inv(V)) @ view
     v_prev = (clip[1] / clip[3] * -0.5 + 0.5).reshape(h, w)
     rows = np.abs(v_prev - v) * float(cs.rectSizePrev[1])
-    rows[np.abs(viewz) > denoising_range] = 0.0
+    rows[np.abs(zv) > denoising_range] = 0.0
     return float(rows[row_begin:row_end].max()) if row_end > row_begin else 0.0
 
 
@@ -70,8 +70,29 @@ class _Harness:
         return out.value
 
 
-def _check_world_space(name, backend):
-    h = _Harness(name, backend)
+def _scaled_depth(factor):
+    def edit(frame):
+        frame["viewz"] = (frame["viewz"] * factor).contiguous()
+
+    return edit
+
+
+# view depth conventions: doubled depth with viewZScale = 0.5 (the model applies the scale itself, from CommonSettings alone), and the negative depth of a right-handed host
+DEPTH_CONVENTIONS = {"plain": (None, None), "scaled": (dict(viewZScale=0.5), _scaled_depth(2.0)), "negated": (None, _scaled_depth(-1.0))}
+
+
+def _check_world_space(name, backend, convention="plain"):
+    cs_kw, frame_edit = DEPTH_CONVENTIONS[convention]
+    plain = None
+    if convention != "plain":  # (measured and released before the run under test: one executor at a time)
+        p = _Harness(name, backend)
+        plain = (p.measure(), _expected_world_space_rows(p.cs, p.viewz, 0, H, float(p.cs.denoisingRange)), p.viewz)
+        del p
+    h = _Harness(name, backend, cs_kw=cs_kw, frame_edit=frame_edit)
+    if plain:
+        assert not np.array_equal(h.viewz, plain[2])
+        assert _expected_world_space_rows(h.cs, h.viewz, 0, H, float(h.cs.denoisingRange)) == pytest.approx(plain[1], rel=1e-12)  # the model: the same geometry
+        assert h.measure() == plain[0]  # the kernel: a power-of-two scale and a sign change are exact
     rng = float(h.cs.denoisingRange)
     for rows in ((0, H), (0, H // 2), (H // 2, H), (37, 38), (50, 50)):
         want = _expected_world_space_rows(h.cs, h.viewz, rows[0], rows[1], rng)
@@ -123,6 +144,12 @@ def test_emulated_motion_rows_world_space(name):
     _check_world_space(name, "emu")
 
 
+@pytest.mark.parametrize("convention", ["scaled", "negated"])
+@pytest.mark.parametrize("name", ["REBLUR_DIFFUSE_SPECULAR", "RELAX_DIFFUSE_SPECULAR", "SIGMA_SHADOW"])
+def test_emulated_motion_rows_view_depth_conventions(name, convention):
+    _check_world_space(name, "emu", convention)
+
+
 @pytest.mark.parametrize("name", ["REBLUR_DIFFUSE", "RELAX_DIFFUSE"])
 def test_emulated_motion_rows_screen_space(name):
     _check_screen_space(name, "emu")
@@ -136,6 +163,13 @@ def test_emulated_motion_rows_argument_errors():
 @pytest.mark.parametrize("name", ["REBLUR_DIFFUSE_SPECULAR", "RELAX_DIFFUSE_SPECULAR", "SIGMA_SHADOW"])
 def test_motion_rows_world_space(name):
     _check_world_space(name, "hip")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("convention", ["scaled", "negated"])
+@pytest.mark.parametrize("name", ["REBLUR_DIFFUSE_SPECULAR", "RELAX_DIFFUSE_SPECULAR", "SIGMA_SHADOW"])
+def test_motion_rows_view_depth_conventions(name, convention):
+    _check_world_space(name, "hip", convention)
 
 
 @pytest.mark.gpu

@@ -439,6 +439,42 @@ def test_pack_197x61_with_a_row_pitch_larger_than_the_row(backend, dump):
         assert np.array_equal(big.view(np.uint8), want.view(np.uint8)), "bytes outside the rect were written: call %d %s" % (key[0], key[1].name)
 
 
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_pack_scales_the_view_depth(backend):
+    """NrdHipFrontEndDesc::viewZScale (frontend.pack_inputs(viewz_scale=)): a host whose depth plane holds 2 * viewZ packs with a scale of 0.5. IN_VIEWZ is the scaled depth and
+    the REBLUR hit distances are normalised with it -- against C, which applies the scale itself -- on a rendered frame with sky texels (depth 1e6, no hit distance); and,
+    a power of two being exact, every packed plane is the bytes of the unscaled pack. 100 x 36: the last workgroup of a row covers 36 of 64 pixels."""
+    be = Backend(backend)
+    w, h, scale = 100, 36, 0.5
+    frame = synth.render_frame(w, h, 1, want=("reblur", "raw"))
+    sky = frame["is_sky"].numpy()
+    assert sky.any() and not sky.all()
+    ins = {k: v.numpy() for k, v in _raw_inputs(frame, cuda=False).items()}
+    doubled = (ins["viewz"] * f32(2.0)).astype(f32)
+
+    def pack(viewz, **kw):
+        res = frontend.pack_inputs(be.up(ins["nr"]), be.up(viewz), material_id=be.up(ins["material"]), motion=be.up(ins["motion"]), hit_dist_params=HDP, lib=be.lib,
+                                   diffuse=dict(mode=S.REBLUR_RADIANCE, radiance_hitdist=be.up(ins["diff"]), direction=be.up(ins["diff_dir"])),
+                                   specular=dict(mode=S.REBLUR_RADIANCE, radiance_hitdist=be.up(ins["spec"]), direction=be.up(ins["spec_dir"])), **kw)
+        return {rt: np.array(be.down(t), copy=True) for rt, (t, fmt) in res.items()}
+
+    got, plain = pack(doubled, viewz_scale=scale), pack(ins["viewz"])
+    assert_bits(got[R.IN_VIEWZ], ins["viewz"], "IN_VIEWZ = viewZ * viewZScale")
+    assert np.all(got[R.IN_VIEWZ][sky] == f32(synth.SKY_VIEWZ))
+    z = doubled.astype(np.float64) * scale  # the model's own scale
+    raw = {k: v.numpy().astype(np.float64) for k, v in frame["raw"].items()}
+    for rt, which, rough in ((R.IN_DIFF_RADIANCE_HITDIST, "diff", np.ones_like(z)), (R.IN_SPEC_RADIANCE_HITDIST, "spec", raw["roughness"])):
+        nhd = M.reblur_get_norm_hit_dist(raw[which + "_hit_dist"], z, HDP, rough)
+        assert_codes(got[rt], f16(M.reblur_pack_radiance_and_norm_hit_dist(raw[which + "_radiance"], nhd)), "%s vs C with the scaled depth" % rt.name)
+        # what the scale is for: the same hit distances normalised with the UNSCALED plane are other codes (a kernel that dropped the scale would produce these)
+        wrong = M.reblur_get_norm_hit_dist(raw[which + "_hit_dist"], doubled.astype(np.float64), HDP, rough)
+        assert np.sum(f16(wrong) != f16(nhd)) > 100
+        assert np.all(got[rt][sky][..., 3] == 0)
+    assert got.keys() == plain.keys()
+    for rt in got:
+        assert_bits(got[rt].view(np.uint8), plain[rt].view(np.uint8), "%s: scaled pack == unscaled pack" % rt.name)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------------- view vector
 def camera_constants(cs):
     """(gFrustum [4], the 3 x 3 rotation of gViewToWorld) as float32, from the constants of a REBLUR dispatch for the same CommonSettings (host only: no device)"""
