@@ -356,6 +356,42 @@ typedef struct NrdHipFrontEndSamples {
 } NrdHipFrontEndSamples;
 uint32_t nrdHipPackInputsSamples(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, void* hipStream);
 
+// Three-channel and split planes: the layout a tensor host holds -- normal [ H, W, 3 ] and roughness [ H, W ], radiance [ H, W, 3 ] and hit distance [ H, W ] -- read and
+// written in place, with no widened RGBA32_SFLOAT copy. In the two calls below a plane documented as RGBA32_SFLOAT may be RGB32_SFLOAT instead (nrd::Format, 12-byte texels):
+//   pack:     normalRoughness, motion, albedo, rf0, translucency, { diffuse, specular }.radianceHitDist and .direction
+//   resolve:  the inputs albedo and rf0; the outputs diffuse.out, specular.out, outComposed, outViewVector, outDiffFactor, outSpecFactor
+// (the fp32 in0 / in1 planes, outShadow and outReJitterScale keep their formats; the calls above still answer UNSUPPORTED to RGB32_SFLOAT). An RGB32_SFLOAT plane: pointer and
+// row pitch multiples of 4 (not of 12, not of 16), row pitch >= 12 x width, the 32-bit limits as above. Where `.w` comes from:
+//   normalRoughness RGB32_SFLOAT                       -> .w = split->roughness
+//   { diffuse, specular }.radianceHitDist RGB32_SFLOAT -> .w = split->{ diffuse, specular }HitDist
+//   a companion that is missing -> INVALID_ARGUMENT naming the field (no roughness or hit distance is ever taken as 0 silently); a companion given next to an RGBA32_SFLOAT
+//   plane, or for a signal whose mode is NONE -> INVALID_ARGUMENT (.w would have two sources). .w of every other RGB32_SFLOAT input is not read; motion.w = 0, as .zw of RG32_SFLOAT.
+//   REBLUR_OCCLUSION reads .w only: radianceHitDist.data may be NULL when the companion is given (4 bytes per pixel are read for that signal).
+// Resolve: .rgb goes to the RGB32_SFLOAT plane, the hit distance to split->{ diffuse, specular }HitDist if given and nowhere otherwise; the output of REBLUR_OCCLUSION is
+// R32_SFLOAT already, a companion for it -> INVALID_ARGUMENT. Sample layers (nrdHipPackInputsSamples rules): the layer stride of an RGB32_SFLOAT stack or of a companion is a
+// multiple of 4 and >= rowPitchBytes x height; a companion has the layer count of its signal; the rule of RGBA32_SFLOAT stacks (a multiple of 16) is unchanged.
+// Every output byte equals what the call above writes for RGBA32_SFLOAT planes holding the same .xyz and the companion's value in .w: the arithmetic is the same code, only loads
+// and stores differ. split == NULL or zeroed with every plane RGBA32_SFLOAT is exactly nrdHipPackInputsSamples( desc, options, samples, stream ) / nrdHipResolveOutputsEx( desc,
+// options, stream ): the same kernels, the same bytes. The contract is the one above: validated before the first HIP call, nothing enqueued on an error, no allocation, no
+// synchronisation, capturable into a graph, errors through nrdHipGetLastFrontEndError.
+typedef struct NrdHipFrontEndSplit {
+    NrdHipPlaneDesc roughness;          // in, R32_SFLOAT: .w of normalRoughness when that plane is RGB32_SFLOAT
+    NrdHipPlaneDesc diffuseHitDist;     // in, R32_SFLOAT: .w of diffuse.radianceHitDist when that plane is RGB32_SFLOAT (or absent: the occlusion mode)
+    NrdHipPlaneDesc specularHitDist;    // in, R32_SFLOAT: the same for the specular signal
+    uint64_t diffuseHitDistLayerBytes;  // distance from sample layer s to layer s + 1 of diffuseHitDist
+    uint64_t specularHitDistLayerBytes; // the same for specularHitDist
+} NrdHipFrontEndSplit;
+uint32_t nrdHipPackInputsSplit(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, const NrdHipFrontEndSplit* split, void* hipStream);
+
+typedef struct NrdHipBackEndSplit {
+    NrdHipPlaneDesc diffuseHitDist, specularHitDist; // out, R32_SFLOAT, optional: .w of diffuse.out / specular.out when those are RGB32_SFLOAT
+} NrdHipBackEndSplit;
+uint32_t nrdHipResolveOutputsSplit(const NrdHipBackEndDesc* desc, const NrdHipBackEndOptions* options, const NrdHipBackEndSplit* split, void* hipStream);
+
+#ifdef __cplusplus
+static_assert(sizeof(NrdHipFrontEndSplit) == 88 && sizeof(NrdHipBackEndSplit) == 48, "mirrored by raytracingdenoiser_amd/api.py");
+#endif
+
 #ifdef __cplusplus
 }
 #endif

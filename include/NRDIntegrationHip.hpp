@@ -109,6 +109,13 @@ public:
         return nrdHipPackInputsSamples(&desc, &options, &samples, m_Stream) == (uint32_t)Result::SUCCESS;
     }
     inline bool ResolveOutputs(const NrdHipBackEndDesc& desc, const NrdHipBackEndOptions& options) { return nrdHipResolveOutputsEx(&desc, &options, m_Stream) == (uint32_t)Result::SUCCESS; }
+    // three-channel and split planes in place (nrdHipPackInputsSplit / nrdHipResolveOutputsSplit): RGB32_SFLOAT planes, .w (roughness, hit distance) in R32_SFLOAT planes of their own
+    inline bool PackInputs(const NrdHipFrontEndDesc& desc, const NrdHipFrontEndOptions& options, const NrdHipFrontEndSamples& samples, const NrdHipFrontEndSplit& split) {
+        return nrdHipPackInputsSplit(&desc, &options, &samples, &split, m_Stream) == (uint32_t)Result::SUCCESS;
+    }
+    inline bool ResolveOutputs(const NrdHipBackEndDesc& desc, const NrdHipBackEndOptions& options, const NrdHipBackEndSplit& split) {
+        return nrdHipResolveOutputsSplit(&desc, &options, &split, m_Stream) == (uint32_t)Result::SUCCESS;
+    }
     inline const char* GetLastFrontEndError() const { return nrdHipGetLastFrontEndError(); }
 
     // Assumes that no work of this integration is in flight on the stream

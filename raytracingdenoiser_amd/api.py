@@ -314,6 +314,15 @@ class HipFrontEndSamples(C.Structure):  # include/NRDHip.h NrdHipFrontEndSamples
     _fields_ = [("diffuse", HipSignalSamples), ("specular", HipSignalSamples), ("hitDistTrimThreshold", C.c_float), ("reserved", C.c_uint32)]
 
 
+class HipFrontEndSplit(C.Structure):  # include/NRDHip.h NrdHipFrontEndSplit
+    _fields_ = [("roughness", HipPlaneDesc), ("diffuseHitDist", HipPlaneDesc), ("specularHitDist", HipPlaneDesc), ("diffuseHitDistLayerBytes", C.c_uint64), ("specularHitDistLayerBytes", C.c_uint64)]
+
+
+class HipBackEndSplit(C.Structure):  # include/NRDHip.h NrdHipBackEndSplit
+    _fields_ = [("diffuseHitDist", HipPlaneDesc), ("specularHitDist", HipPlaneDesc)]
+
+
+assert C.sizeof(HipFrontEndSplit) == 88 and C.sizeof(HipBackEndSplit) == 48
 assert C.sizeof(HipPlaneDesc) == 24 and C.sizeof(HipFrontEndSignal) == 104 and C.sizeof(HipFrontEndDesc) == 552 and C.sizeof(HipBackEndSignal) == 80 and C.sizeof(HipBackEndDesc) == 432
 assert C.sizeof(HipFrontEndOptions) == 8 and C.sizeof(HipBackEndOptions) == 32 and C.sizeof(HipSignalSamples) == 24 and C.sizeof(HipFrontEndSamples) == 56
 
@@ -339,7 +348,7 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipCreateExecutorWithArena", "nrdHipSetProfiling", "nrdHipCollectPassTimings", "nrdHipSetOwnedRows", "nrdHipGetDispatchReach",
                    "nrdHipExecuteDispatchRange", "nrdHipPlanHaloExchange", "nrdHipSetGraphMode", "nrdHipGetGraphStats", "nrdHipGetTileFallbackStats", "nrdHipGetNumericsMode", "nrdHipMeasureCopyBandwidth",
                    "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError",
-                   "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples"]
+                   "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit"]
 
 _libs = {}
 
@@ -412,6 +421,8 @@ def load_library(path=None):
     lib.nrdHipPackInputsEx.argtypes, lib.nrdHipPackInputsEx.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), C.c_void_p], C.c_uint32
     lib.nrdHipPackInputsSamples.argtypes, lib.nrdHipPackInputsSamples.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSamples), C.c_void_p], C.c_uint32
     lib.nrdHipResolveOutputsEx.argtypes, lib.nrdHipResolveOutputsEx.restype = [P(HipBackEndDesc), P(HipBackEndOptions), C.c_void_p], C.c_uint32
+    lib.nrdHipPackInputsSplit.argtypes, lib.nrdHipPackInputsSplit.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSamples), P(HipFrontEndSplit), C.c_void_p], C.c_uint32
+    lib.nrdHipResolveOutputsSplit.argtypes, lib.nrdHipResolveOutputsSplit.restype = [P(HipBackEndDesc), P(HipBackEndOptions), P(HipBackEndSplit), C.c_void_p], C.c_uint32
     _libs[path] = lib
     return lib
 

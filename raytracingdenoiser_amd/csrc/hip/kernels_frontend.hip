@@ -3,6 +3,9 @@
 // denoised OUT_* planes into linear fp32 radiance. One thread per pixel, 64 x 4 workgroups: a wave covers 64 consecutive pixels of one row, so every load
 // and store of a wave is one contiguous segment (16 B per lane for the RGBA32_SFLOAT inputs: global_load_dwordx4). The calls with options (nrdHipPackInputsEx /
 // nrdHipResolveOutputsEx) launch these very kernels when the options are absent or zero, else one of two more: the checkerboard twin of the pack kernel and the re-jitter kernel.
+// nrdHipPackInputsSplit / nrdHipResolveOutputsSplit launch the kernels of those calls when every plane is RGBA32_SFLOAT, else the split twin of the kernel the call would have
+// taken: the same body instantiated with SPLIT = true, in which a colour / vector plane may hold 12-byte RGB32_SFLOAT texels (global_load_dwordx3 / global_store_dwordx3,
+// never a 16-byte access) and `.w` lives in an R32_SFLOAT plane of its own.
 //
 // Arithmetic: include/NRD.hip.h and nothing else -- its contract, and the reference text it is pinned to, is unfused IEEE fp32 with correctly rounded
 // division and square root. The product builds its device sources with -ffp-contract=on, hence the pragma below, in front of every include: no statement
@@ -54,6 +57,24 @@ struct SampleArgs {
     float trim;                // > 0: NRD_FrontEnd_TrimHitDistance on every sample's hit distance
 };
 
+// nrdHipPackInputsSplit: which fp32 planes of PackArgs hold 12-byte RGB32_SFLOAT texels (a bit each), and the R32_SFLOAT planes `.w` comes from instead. A signal whose
+// kSplit*In bit is set takes its hit distance from its companion (its own plane is RGB32_SFLOAT, or absent in the occlusion mode); all of it is uniform: scalar branches
+enum : uint32_t {
+    kSplitNormalRoughness = 1u << 0, kSplitMotion = 1u << 1, kSplitAlbedo = 1u << 2, kSplitRf0 = 1u << 3, kSplitTranslucency = 1u << 4,
+    kSplitDiffIn = 1u << 5, kSplitDiffDir = 1u << 6, kSplitSpecIn = 1u << 7, kSplitSpecDir = 1u << 8,
+    // nrdHipResolveOutputsSplit: the outputs (kSplitAlbedo / kSplitRf0 are its inputs)
+    kSplitDiffOut = 1u << 9, kSplitSpecOut = 1u << 10, kSplitComposed = 1u << 11, kSplitViewVector = 1u << 12, kSplitDiffFactor = 1u << 13, kSplitSpecFactor = 1u << 14
+};
+struct SplitArgs {
+    FePlane roughness, diffHitDist, specHitDist;
+    uint64_t diffHitDistLayer, specHitDistLayer; // sample layers of the two companions (SampleArgs rules)
+    uint32_t rgb;                                // kSplit* bits
+};
+struct ResolveSplitArgs {
+    FePlane diffHitDist, specHitDist; // optional: `.w` of an RGB32_SFLOAT diffOut / specOut
+    uint32_t rgb;
+};
+
 struct ResolveArgs {
     FePlane normalRoughness, viewZ, albedo, rf0;
     FePlane diffIn0, diffIn1, diffOut, specIn0, specIn1, specOut;
@@ -68,6 +89,33 @@ struct ResolveArgs {
 __device__ __forceinline__ Plane AsPlane(const FePlane& p, int w, int h) { return Plane{p.ptr, p.pitch, w, h}; }
 __device__ __forceinline__ float3 Xyz(float4 v) { return make_float3(v.x, v.y, v.z); }
 
+// ---- the loads and stores of the split twins (nrdHipPackInputsSplit / nrdHipResolveOutputsSplit); with SPLIT = false each of them is the access the plain kernels make
+__device__ __forceinline__ uint32_t SplitTexelBytes(uint32_t rgb, uint32_t bit) { return (rgb & bit) ? 12u : 16u; }
+// a plane of which .xyz alone is consumed (albedo, rf0, translucency, direction): 12 bytes per lane whatever the texel size
+template <bool SPLIT>
+__device__ __forceinline__ float3 LoadColour(const FePlane& p, uint32_t rgb, uint32_t bit, int x, int y, int w, int h) {
+    return SPLIT ? LoadXyz32F(AsPlane(p, w, h), x, y, SplitTexelBytes(rgb, bit)) : Xyz(LoadRGBA32F(AsPlane(p, w, h), x, y));
+}
+// a plane consumed whole: one 16-byte load, or 12 bytes + the companion's dword. needXyz = false (a mode that reads .w only): the split form reads the companion alone
+template <bool SPLIT>
+__device__ __forceinline__ float4 LoadTexel(const FePlane& p, const FePlane& companion, uint32_t rgb, uint32_t bit, bool needXyz, int x, int y, int w, int h) {
+    if (SPLIT && (rgb & bit)) {
+        const float3 c = needXyz ? LoadRGB32F(AsPlane(p, w, h), x, y) : make_float3(0.0f, 0.0f, 0.0f);
+        return make_float4(c.x, c.y, c.z, LoadR32F(AsPlane(companion, w, h), x, y));
+    }
+    return LoadRGBA32F(AsPlane(p, w, h), x, y);
+}
+// an fp32 colour output: 16 bytes, or 12 bytes + .w to the companion where one is given (dropped otherwise)
+template <bool SPLIT>
+__device__ __forceinline__ void StoreTexel(const FePlane& p, const FePlane& companion, uint32_t rgb, uint32_t bit, int x, int y, int w, int h, float4 c) {
+    if (SPLIT && (rgb & bit)) {
+        StoreRGB32F(AsPlane(p, w, h), x, y, Xyz(c));
+        if (companion.ptr)
+            StoreR32F(AsPlane(companion, w, h), x, y, c.w);
+    } else
+        StoreRGBA32F(AsPlane(p, w, h), x, y, c);
+}
+
 // V of NRDHip.h: only correctly rounded + - * / sqrt in a fixed order (a float32 numpy restatement is bit-exact)
 __device__ __forceinline__ float3 ViewVector(const FeCamera& c, int x, int y, int w, int h, float viewZ) {
     const float u = (float(x) + 0.5f) / float(w);
@@ -80,10 +128,11 @@ __device__ __forceinline__ float3 ViewVector(const FeCamera& c, int x, int y, in
 }
 
 // (x, y): the pixel whose data is packed; the texels go to column xo of its row (xo = x, or x >> 1 of a checkerboarded frame)
-template <bool SPEC>
-__device__ __forceinline__ void PackSignal(uint32_t mode, const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, int x, int xo, int y, int w, int h, float viewZ,
-    float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
-    const float4 s = LoadRGBA32F(AsPlane(in, w, h), x, y);
+template <bool SPEC, bool SPLIT>
+__device__ __forceinline__ void PackSignal(uint32_t mode, const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, const FePlane& hitDistPlane, uint32_t rgb,
+    int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
+    const float4 s = LoadTexel<SPLIT>(in, hitDistPlane, rgb, SPEC ? kSplitSpecIn : kSplitDiffIn, mode != NRD_HIP_SIGNAL_REBLUR_OCCLUSION && mode != NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION,
+        x, y, w, h);
     float3 radiance = Xyz(s);
     if (demodulate)
         radiance = make_float3(radiance.x / factor.x, radiance.y / factor.y, radiance.z / factor.z);
@@ -92,7 +141,7 @@ __device__ __forceinline__ void PackSignal(uint32_t mode, const FePlane& in, con
     const bool needsDirection = mode == NRD_HIP_SIGNAL_REBLUR_SH || mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION || mode == NRD_HIP_SIGNAL_RELAX_SH;
     float3 direction = make_float3(0.0f, 0.0f, 0.0f);
     if (needsDirection)
-        direction = Xyz(LoadRGBA32F(AsPlane(dirPlane, w, h), x, y));
+        direction = LoadColour<SPLIT>(dirPlane, rgb, SPEC ? kSplitSpecDir : kSplitDiffDir, x, y, w, h);
     const Plane o0 = AsPlane(out0, w, h), o1 = AsPlane(out1, w, h);
     float4 p1;
     switch (mode) { // wave-uniform: a kernel argument
@@ -188,9 +237,19 @@ __device__ __forceinline__ float4 LoadSampleTexel(const Plane& layer, int x, int
 // One signal of one pixel over `num` sample layers, the mode a template argument: the wave-uniform switch sits outside the sample loop (PackSignalSamples).
 // Layer bases advance by scalar 64-bit additions; a lane's byte offset inside a layer is computed once. The loads of four layers are issued before the first of
 // them is consumed (a wave reads one contiguous 1 KiB segment per layer and plane), the remaining num & 3 layers one by one.
-template <bool SPEC, uint32_t MODE>
-__device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, uint64_t inLayer, uint64_t dirLayer, uint32_t num, float trim,
-    int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
+// SPLIT (nrdHipPackInputsSplit): a sample costs two loads per plane instead of one, in the same loop -- 12 bytes of .xyz at a lane stride of 12 or 16, and the dword of .w, which is
+// the companion's (its own pitch and layer stride) or the fourth of the 16-byte texel itself. Which is decided once, in front of the loop, by selecting base, offset and stride.
+struct SplitSignal {
+    FePlane hitDist;       // the companion
+    uint64_t hitDistLayer;
+    uint32_t inBytes, dirBytes; // 12 or 16
+    bool wFromCompanion;
+};
+
+template <bool SPEC, uint32_t MODE, bool SPLIT>
+__device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, uint64_t inLayer, uint64_t dirLayer, const SplitSignal& sp, uint32_t num,
+    float trim, int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
+    constexpr bool kRadiance = MODE != NRD_HIP_SIGNAL_REBLUR_OCCLUSION && MODE != NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION; // (else .xyz is not consumed: not loaded by the split form)
     constexpr bool kDirection = MODE == NRD_HIP_SIGNAL_REBLUR_SH || MODE == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION || MODE == NRD_HIP_SIGNAL_RELAX_SH;
     constexpr bool kSh = MODE == NRD_HIP_SIGNAL_REBLUR_SH || MODE == NRD_HIP_SIGNAL_RELAX_SH;
     constexpr uint32_t kBatch = 4;
@@ -199,13 +258,31 @@ __device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& d
     SampleSums sums = {make_float4(-0.0f, -0.0f, -0.0f, -0.0f), make_float4(-0.0f, -0.0f, -0.0f, -0.0f), NRD_FrontEnd_SpecHitDistAveraging_Begin()};
     Plane layer = AsPlane(in, w, h), dirLayerPlane = AsPlane(kDirection ? dirPlane : in, w, h);
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    // SPLIT: where this lane's .w lives in a layer, and how far the next layer is
+    const Plane wPlane = AsPlane(SPLIT && sp.wFromCompanion ? sp.hitDist : in, w, h);
+    const uint8_t* wPtr = !SPLIT ? nullptr : wPlane.ptr + (sp.wFromCompanion ? TexelOffset(wPlane, x, y, 4u, true) : TexelOffset(wPlane, x, y, 16u, true) + 12u);
+    const uint64_t wLayer = SPLIT && sp.wFromCompanion ? sp.hitDistLayer : inLayer;
+    auto loadSample = [&]() {
+        if (!SPLIT)
+            return LoadSampleTexel(layer, x, y);
+        const float3 c = kRadiance ? LoadXyz32F(layer, x, y, sp.inBytes) : make_float3(0.0f, 0.0f, 0.0f);
+        const float4 t = make_float4(c.x, c.y, c.z, *(const float*)wPtr);
+        wPtr += wLayer;
+        return t;
+    };
+    auto loadDirection = [&]() {
+        if (!SPLIT)
+            return LoadSampleTexel(dirLayerPlane, x, y);
+        const float3 c = LoadXyz32F(dirLayerPlane, x, y, sp.dirBytes);
+        return make_float4(c.x, c.y, c.z, 0.0f);
+    };
     uint32_t s = 0;
     for (; s + kBatch <= num; s += kBatch) {
         float4 t[kBatch], d[kBatch];
 #pragma unroll
         for (uint32_t k = 0; k < kBatch; k++) {
-            t[k] = LoadSampleTexel(layer, x, y);
-            d[k] = kDirection ? LoadSampleTexel(dirLayerPlane, x, y) : zero;
+            t[k] = loadSample();
+            d[k] = kDirection ? loadDirection() : zero;
             layer.ptr += inLayer;
             dirLayerPlane.ptr += dirLayer;
         }
@@ -214,8 +291,8 @@ __device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& d
             AddSample<SPEC, MODE>(sums, t[k], d[k], trim, viewZ, r, hitDistParams, demodulate, factor);
     }
     for (; s < num; s++) {
-        const float4 t = LoadSampleTexel(layer, x, y);
-        const float4 d = kDirection ? LoadSampleTexel(dirLayerPlane, x, y) : zero;
+        const float4 t = loadSample();
+        const float4 d = kDirection ? loadDirection() : zero;
         layer.ptr += inLayer;
         dirLayerPlane.ptr += dirLayer;
         AddSample<SPEC, MODE>(sums, t, d, trim, viewZ, r, hitDistParams, demodulate, factor);
@@ -239,11 +316,11 @@ __device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& d
 
 #define NRD_REDUCE_SIGNAL(MODE) \
     case MODE: \
-        ReduceSignal<SPEC, MODE>(in, dirPlane, out0, out1, inLayer, dirLayer, num, trim, x, xo, y, w, h, viewZ, roughness, hitDistParams, demodulate, factor); \
+        ReduceSignal<SPEC, MODE, SPLIT>(in, dirPlane, out0, out1, inLayer, dirLayer, sp, num, trim, x, xo, y, w, h, viewZ, roughness, hitDistParams, demodulate, factor); \
         break;
-template <bool SPEC>
-__device__ __forceinline__ void PackSignalSamples(uint32_t mode, const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, uint64_t inLayer, uint64_t dirLayer, uint32_t num,
-    float trim, int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
+template <bool SPEC, bool SPLIT>
+__device__ __forceinline__ void PackSignalSamples(uint32_t mode, const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, uint64_t inLayer, uint64_t dirLayer,
+    const SplitSignal& sp, uint32_t num, float trim, int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
     switch (mode) { // wave-uniform: a kernel argument
         NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_RADIANCE)
         NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_SH)
@@ -264,13 +341,15 @@ __device__ __forceinline__ float ClampToHalf(float v) { return isnan(v) ? v : fm
 // ( ( x ^ y ) ^ frameIndex ) & 1 == diffCell (nrdmath.h CheckerBoard), the specular one elsewhere -- and its texel goes to column x >> 1: the left half of the plane.
 // Only those pixels of a signal's fp32 planes are read and no other texel of its packed planes is written.
 // SAMPLES (nrdHipPackInputsSamples): each signal is reduced over its sample layers (PackSignalSamples); the other kernels never look at `sa`.
-template <bool CHECKERBOARD, bool SAMPLES>
-__device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& sa, uint32_t diffCell, uint32_t frameIndex) {
+// SPLIT (nrdHipPackInputsSplit): the fp32 colour / vector planes may hold 12-byte RGB32_SFLOAT texels, `.w` in a plane of its own (`sp`, which the other kernels never look at).
+// The same body: only the loads differ.
+template <bool CHECKERBOARD, bool SAMPLES, bool SPLIT>
+__device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& sa, const SplitArgs& sp, uint32_t diffCell, uint32_t frameIndex) {
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
     const int w = a.w, h = a.h;
     if (x >= w || y >= h)
         return;
-    const float4 nr = LoadRGBA32F(AsPlane(a.normalRoughness, w, h), x, y);
+    const float4 nr = LoadTexel<SPLIT>(a.normalRoughness, sp.roughness, sp.rgb, kSplitNormalRoughness, true, x, y, w, h);
     const float viewZ = LoadR32F(AsPlane(a.viewZ, w, h), x, y) * a.viewZScale;
     const float3 N = Xyz(nr);
     const float roughness = nr.w;
@@ -286,6 +365,9 @@ __device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& s
         if (a.motionIsRG) {
             const float2 m = *TexelPtr<const float2>(AsPlane(a.motion, w, h), x, y);
             mv = make_float4(m.x, m.y, 0.0f, 0.0f);
+        } else if (SPLIT && (sp.rgb & kSplitMotion)) {
+            const float3 m = LoadRGB32F(AsPlane(a.motion, w, h), x, y);
+            mv = make_float4(m.x, m.y, m.z, 0.0f);
         } else
             mv = LoadRGBA32F(AsPlane(a.motion, w, h), x, y);
         StoreRGBA16F(AsPlane(a.outMv, w, h), x, y, make_float4(ClampToHalf(mv.x), ClampToHalf(mv.y), ClampToHalf(mv.z), ClampToHalf(mv.w)));
@@ -294,22 +376,24 @@ __device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& s
     float3 diffFactor = make_float3(1.0f, 1.0f, 1.0f), specFactor = diffFactor;
     if (a.demodulate) {
         const float3 V = ViewVector(a.camera, x, y, w, h, viewZ);
-        NRD_MaterialFactors(N, V, Xyz(LoadRGBA32F(AsPlane(a.albedo, w, h), x, y)), Xyz(LoadRGBA32F(AsPlane(a.rf0, w, h), x, y)), roughness, diffFactor, specFactor);
+        NRD_MaterialFactors(N, V, LoadColour<SPLIT>(a.albedo, sp.rgb, kSplitAlbedo, x, y, w, h), LoadColour<SPLIT>(a.rf0, sp.rgb, kSplitRf0, x, y, w, h), roughness, diffFactor, specFactor);
     }
     const bool diffHere = !CHECKERBOARD || ((((uint32_t)x ^ (uint32_t)y) ^ frameIndex) & 1u) == diffCell;
     const int xo = CHECKERBOARD ? x >> 1 : x;
     if (SAMPLES) {
+        const SplitSignal diffSplit = {sp.diffHitDist, sp.diffHitDistLayer, SplitTexelBytes(sp.rgb, kSplitDiffIn), SplitTexelBytes(sp.rgb, kSplitDiffDir), (sp.rgb & kSplitDiffIn) != 0u};
+        const SplitSignal specSplit = {sp.specHitDist, sp.specHitDistLayer, SplitTexelBytes(sp.rgb, kSplitSpecIn), SplitTexelBytes(sp.rgb, kSplitSpecDir), (sp.rgb & kSplitSpecIn) != 0u};
         if (a.diffMode && diffHere)
-            PackSignalSamples<false>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sa.diffInLayer, sa.diffDirLayer, sa.diffNum, sa.trim, x, xo, y, w, h, viewZ, roughness, a.hitDistParams,
-                a.demodulate != 0u, diffFactor);
+            PackSignalSamples<false, SPLIT>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sa.diffInLayer, sa.diffDirLayer, diffSplit, sa.diffNum, sa.trim, x, xo, y, w, h, viewZ, roughness,
+                a.hitDistParams, a.demodulate != 0u, diffFactor);
         if (a.specMode && (!CHECKERBOARD || !diffHere))
-            PackSignalSamples<true>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, sa.specInLayer, sa.specDirLayer, sa.specNum, sa.trim, x, xo, y, w, h, viewZ, roughness, a.hitDistParams,
-                a.demodulate != 0u, specFactor);
+            PackSignalSamples<true, SPLIT>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, sa.specInLayer, sa.specDirLayer, specSplit, sa.specNum, sa.trim, x, xo, y, w, h, viewZ, roughness,
+                a.hitDistParams, a.demodulate != 0u, specFactor);
     } else {
         if (a.diffMode && diffHere)
-            PackSignal<false>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, diffFactor);
+            PackSignal<false, SPLIT>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sp.diffHitDist, sp.rgb, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, diffFactor);
         if (a.specMode && (!CHECKERBOARD || !diffHere))
-            PackSignal<true>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, specFactor);
+            PackSignal<true, SPLIT>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, sp.specHitDist, sp.rgb, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, specFactor);
     }
 
     if (a.outPenumbra.ptr || a.outTranslucency.ptr) {
@@ -317,18 +401,33 @@ __device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& s
         if (a.outPenumbra.ptr)
             StoreR16F(AsPlane(a.outPenumbra, w, h), x, y, SIGMA_FrontEnd_PackPenumbra(distanceToOccluder, a.tanOfLightAngularRadius));
         if (a.outTranslucency.ptr)
-            StoreRGBA8Unorm(AsPlane(a.outTranslucency, w, h), x, y, SIGMA_FrontEnd_PackTranslucency(distanceToOccluder, Xyz(LoadRGBA32F(AsPlane(a.translucency, w, h), x, y))));
+            StoreRGBA8Unorm(AsPlane(a.outTranslucency, w, h), x, y, SIGMA_FrontEnd_PackTranslucency(distanceToOccluder, LoadColour<SPLIT>(a.translucency, sp.rgb, kSplitTranslucency, x, y, w, h)));
     }
 }
 
-__global__ void __launch_bounds__(256) PackInputsKernel(const PackArgs a) { PackPixel<false, false>(a, SampleArgs{}, 0u, 0u); }
+__global__ void __launch_bounds__(256) PackInputsKernel(const PackArgs a) { PackPixel<false, false, false>(a, SampleArgs{}, SplitArgs{}, 0u, 0u); }
 
-__global__ void __launch_bounds__(256) PackCheckerboardKernel(const PackArgs a, const uint32_t diffCell, const uint32_t frameIndex) { PackPixel<true, false>(a, SampleArgs{}, diffCell, frameIndex); }
+__global__ void __launch_bounds__(256) PackCheckerboardKernel(const PackArgs a, const uint32_t diffCell, const uint32_t frameIndex) {
+    PackPixel<true, false, false>(a, SampleArgs{}, SplitArgs{}, diffCell, frameIndex);
+}
 
 // the multi-sample twin of the two (nrdHipPackInputsSamples with more than one sample layer or a trim threshold), templated on checkerboard like them
 template <bool CHECKERBOARD>
 __global__ void __launch_bounds__(256) PackSamplesKernel(const PackArgs a, const SampleArgs sa, const uint32_t diffCell, const uint32_t frameIndex) {
-    PackPixel<CHECKERBOARD, true>(a, sa, diffCell, frameIndex);
+    PackPixel<CHECKERBOARD, true, false>(a, sa, SplitArgs{}, diffCell, frameIndex);
+}
+
+// the split twins of the four (nrdHipPackInputsSplit with an RGB32_SFLOAT plane or a companion): further instantiations of the same body, their kernel arguments those of
+// their siblings plus SplitArgs
+__global__ void __launch_bounds__(256) PackInputsSplitKernel(const PackArgs a, const SplitArgs sp) { PackPixel<false, false, true>(a, SampleArgs{}, sp, 0u, 0u); }
+
+__global__ void __launch_bounds__(256) PackCheckerboardSplitKernel(const PackArgs a, const SplitArgs sp, const uint32_t diffCell, const uint32_t frameIndex) {
+    PackPixel<true, false, true>(a, SampleArgs{}, sp, diffCell, frameIndex);
+}
+
+template <bool CHECKERBOARD>
+__global__ void __launch_bounds__(256) PackSamplesSplitKernel(const PackArgs a, const SampleArgs sa, const SplitArgs sp, const uint32_t diffCell, const uint32_t frameIndex) {
+    PackPixel<CHECKERBOARD, true, true>(a, sa, sp, diffCell, frameIndex);
 }
 
 __device__ __forceinline__ float4 LoadSignalTexel(const FePlane& p, bool wide, int x, int y, int w, int h) {
@@ -336,9 +435,9 @@ __device__ __forceinline__ float4 LoadSignalTexel(const FePlane& p, bool wide, i
 }
 
 // one signal of the back end: returns the colour written to `out` (for the composition)
-template <bool SPEC>
-__device__ __forceinline__ float3 ResolveSignal(uint32_t mode, uint32_t resolve, bool wide, const FePlane& in0, const FePlane& in1, const FePlane& out, int x, int y, int w, int h, float viewZ,
-    float3 N, float3 V, float roughness, float4 hitDistParams, bool denormalize, bool remodulate, float3 factor) {
+template <bool SPEC, bool SPLIT>
+__device__ __forceinline__ float3 ResolveSignal(uint32_t mode, uint32_t resolve, bool wide, const FePlane& in0, const FePlane& in1, const FePlane& out, const FePlane& outHitDist, uint32_t splitBits,
+    int x, int y, int w, int h, float viewZ, float3 N, float3 V, float roughness, float4 hitDistParams, bool denormalize, bool remodulate, float3 factor) {
     const float r = SPEC ? roughness : 1.0f;
     const Plane o = AsPlane(out, w, h);
     if (mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION) {
@@ -375,11 +474,15 @@ __device__ __forceinline__ float3 ResolveSignal(uint32_t mode, uint32_t resolve,
         c.w = REBLUR_GetHitDist(c.w, viewZ, hitDistParams, r);
     if (remodulate)
         c = make_float4(c.x * factor.x, c.y * factor.y, c.z * factor.z, c.w);
-    StoreRGBA32F(o, x, y, c);
+    StoreTexel<SPLIT>(out, outHitDist, splitBits, SPEC ? kSplitSpecOut : kSplitDiffOut, x, y, w, h, c);
     return Xyz(c);
 }
 
-__global__ void __launch_bounds__(256) ResolveOutputsKernel(const ResolveArgs a) {
+// one pixel of the back end. SPLIT (nrdHipResolveOutputsSplit): albedo / rf0 and the colour outputs may hold 12-byte RGB32_SFLOAT texels, the hit distance of a signal then goes
+// to a plane of its own or nowhere (`sp`, which the plain kernel never looks at). The same body: only the loads of albedo / rf0 and the stores differ.
+template <bool SPLIT>
+__device__ __forceinline__ void ResolvePixel(const ResolveArgs& a, const ResolveSplitArgs& sp) {
+    const FePlane none = {nullptr, 0};
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
     const int w = a.w, h = a.h;
     if (x >= w || y >= h)
@@ -396,25 +499,25 @@ __global__ void __launch_bounds__(256) ResolveOutputsKernel(const ResolveArgs a)
     if (a.needV) {
         V = ViewVector(a.camera, x, y, w, h, viewZ);
         if (a.outViewVector.ptr)
-            StoreRGBA32F(AsPlane(a.outViewVector, w, h), x, y, make_float4(V.x, V.y, V.z, 0.0f));
+            StoreTexel<SPLIT>(a.outViewVector, none, sp.rgb, kSplitViewVector, x, y, w, h, make_float4(V.x, V.y, V.z, 0.0f));
     }
     float3 diffFactor = make_float3(1.0f, 1.0f, 1.0f), specFactor = diffFactor;
     if (a.needFactors) {
-        NRD_MaterialFactors(N, V, Xyz(LoadRGBA32F(AsPlane(a.albedo, w, h), x, y)), Xyz(LoadRGBA32F(AsPlane(a.rf0, w, h), x, y)), roughness, diffFactor, specFactor);
+        NRD_MaterialFactors(N, V, LoadColour<SPLIT>(a.albedo, sp.rgb, kSplitAlbedo, x, y, w, h), LoadColour<SPLIT>(a.rf0, sp.rgb, kSplitRf0, x, y, w, h), roughness, diffFactor, specFactor);
         if (a.outDiffFactor.ptr)
-            StoreRGBA32F(AsPlane(a.outDiffFactor, w, h), x, y, make_float4(diffFactor.x, diffFactor.y, diffFactor.z, 0.0f));
+            StoreTexel<SPLIT>(a.outDiffFactor, none, sp.rgb, kSplitDiffFactor, x, y, w, h, make_float4(diffFactor.x, diffFactor.y, diffFactor.z, 0.0f));
         if (a.outSpecFactor.ptr)
-            StoreRGBA32F(AsPlane(a.outSpecFactor, w, h), x, y, make_float4(specFactor.x, specFactor.y, specFactor.z, 0.0f));
+            StoreTexel<SPLIT>(a.outSpecFactor, none, sp.rgb, kSplitSpecFactor, x, y, w, h, make_float4(specFactor.x, specFactor.y, specFactor.z, 0.0f));
     }
     float3 diff = make_float3(0.0f, 0.0f, 0.0f), spec = diff;
     if (a.diffMode)
-        diff = ResolveSignal<false>(a.diffMode, a.diffResolve, a.diffWide != 0u, a.diffIn0, a.diffIn1, a.diffOut, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
+        diff = ResolveSignal<false, SPLIT>(a.diffMode, a.diffResolve, a.diffWide != 0u, a.diffIn0, a.diffIn1, a.diffOut, sp.diffHitDist, sp.rgb, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
             a.remodulate != 0u, diffFactor);
     if (a.specMode)
-        spec = ResolveSignal<true>(a.specMode, a.specResolve, a.specWide != 0u, a.specIn0, a.specIn1, a.specOut, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
+        spec = ResolveSignal<true, SPLIT>(a.specMode, a.specResolve, a.specWide != 0u, a.specIn0, a.specIn1, a.specOut, sp.specHitDist, sp.rgb, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
             a.remodulate != 0u, specFactor);
     if (a.outComposed.ptr)
-        StoreRGBA32F(AsPlane(a.outComposed, w, h), x, y, make_float4(diff.x + spec.x, diff.y + spec.y, diff.z + spec.z, 0.0f));
+        StoreTexel<SPLIT>(a.outComposed, none, sp.rgb, kSplitComposed, x, y, w, h, make_float4(diff.x + spec.x, diff.y + spec.y, diff.z + spec.z, 0.0f));
     if (a.outShadow.ptr) {
         if (a.shadowIsRGBA)
             StoreRGBA32F(AsPlane(a.outShadow, w, h), x, y, SIGMA_BackEnd_UnpackShadow(LoadRGBA8Unorm(AsPlane(a.shadow, w, h), x, y)));
@@ -422,6 +525,10 @@ __global__ void __launch_bounds__(256) ResolveOutputsKernel(const ResolveArgs a)
             StoreR32F(AsPlane(a.outShadow, w, h), x, y, SIGMA_BackEnd_UnpackShadow(LoadR8Unorm(AsPlane(a.shadow, w, h), x, y)));
     }
 }
+
+__global__ void __launch_bounds__(256) ResolveOutputsKernel(const ResolveArgs a) { ResolvePixel<false>(a, ResolveSplitArgs{}); }
+
+__global__ void __launch_bounds__(256) ResolveOutputsSplitKernel(const ResolveArgs a, const ResolveSplitArgs sp) { ResolvePixel<true>(a, sp); }
 
 // ---- the high-quality resolve of an SH denoiser (nrdHipResolveOutputsEx with reJitter): SG / SH resolve, NRD_SG_ReJitter, remodulation ---------------
 // NRD_SG_ReJitter is the one stencil of the back end: it wants viewZ and the decoded normal of the four edge neighbours. NRD_REJITTER_TILE = 1 (shipped; DESIGN.md
@@ -457,9 +564,9 @@ __device__ __forceinline__ NRD_SG LoadSg(uint32_t mode, bool wide, const FePlane
 }
 
 // ( resolved.rgb * scale ) * factor, in that order; .w as ResolveSignal writes it
-template <bool SPEC>
-__device__ __forceinline__ float3 StoreReJittered(const ResolveArgs& a, uint32_t mode, uint32_t resolve, const FePlane& out, NRD_SG sg, int x, int y, float viewZ, float3 N, float3 V, float roughness,
-    float scale, float3 factor) {
+template <bool SPEC, bool SPLIT>
+__device__ __forceinline__ float3 StoreReJittered(const ResolveArgs& a, uint32_t mode, uint32_t resolve, const FePlane& out, const FePlane& outHitDist, uint32_t splitBits, NRD_SG sg, int x, int y, float viewZ,
+    float3 N, float3 V, float roughness, float scale, float3 factor) {
     float3 rgb;
     if (resolve == NRD_HIP_RESOLVE_SH)
         rgb = SPEC ? NRD_SH_ResolveSpecular(sg, N, V, roughness) : NRD_SH_ResolveDiffuse(sg, N);
@@ -470,11 +577,14 @@ __device__ __forceinline__ float3 StoreReJittered(const ResolveArgs& a, uint32_t
         c.w = REBLUR_GetHitDist(c.w, viewZ, a.hitDistParams, SPEC ? roughness : 1.0f);
     if (a.remodulate)
         c = make_float4(c.x * factor.x, c.y * factor.y, c.z * factor.z, c.w);
-    StoreRGBA32F(AsPlane(out, a.w, a.h), x, y, c);
+    StoreTexel<SPLIT>(out, outHitDist, splitBits, SPEC ? kSplitSpecOut : kSplitDiffOut, x, y, a.w, a.h, c);
     return Xyz(c);
 }
 
-__global__ void __launch_bounds__(256) ReJitterKernel(const ReJitterArgs args) {
+// SPLIT (nrdHipResolveOutputsSplit with reJitter): the LDS tile is the same; only the loads of rf0 / albedo and the stores differ
+template <bool SPLIT>
+__device__ __forceinline__ void ReJitterPixel(const ReJitterArgs& args, const ResolveSplitArgs& sp) {
+    const FePlane none = {nullptr, 0};
     const ResolveArgs& a = args.r;
     const int x = (int)(blockIdx.x * (uint32_t)kReJitterTileW + threadIdx.x), y = (int)(blockIdx.y * (uint32_t)kReJitterTileH + threadIdx.y);
     const int w = a.w, h = a.h;
@@ -506,24 +616,24 @@ __global__ void __launch_bounds__(256) ReJitterKernel(const ReJitterArgs args) {
     const float3 N = Xyz(c);
     const float3 V = ViewVector(a.camera, x, y, w, h, viewZ);
     if (a.outViewVector.ptr)
-        StoreRGBA32F(AsPlane(a.outViewVector, w, h), x, y, make_float4(V.x, V.y, V.z, 0.0f));
-    const float3 Rf0 = Xyz(LoadRGBA32F(AsPlane(a.rf0, w, h), x, y));
+        StoreTexel<SPLIT>(a.outViewVector, none, sp.rgb, kSplitViewVector, x, y, w, h, make_float4(V.x, V.y, V.z, 0.0f));
+    const float3 Rf0 = LoadColour<SPLIT>(a.rf0, sp.rgb, kSplitRf0, x, y, w, h);
     float3 diffFactor = make_float3(1.0f, 1.0f, 1.0f), specFactor = diffFactor;
     if (a.needFactors) {
-        NRD_MaterialFactors(N, V, Xyz(LoadRGBA32F(AsPlane(a.albedo, w, h), x, y)), Rf0, roughness, diffFactor, specFactor);
+        NRD_MaterialFactors(N, V, LoadColour<SPLIT>(a.albedo, sp.rgb, kSplitAlbedo, x, y, w, h), Rf0, roughness, diffFactor, specFactor);
         if (a.outDiffFactor.ptr)
-            StoreRGBA32F(AsPlane(a.outDiffFactor, w, h), x, y, make_float4(diffFactor.x, diffFactor.y, diffFactor.z, 0.0f));
+            StoreTexel<SPLIT>(a.outDiffFactor, none, sp.rgb, kSplitDiffFactor, x, y, w, h, make_float4(diffFactor.x, diffFactor.y, diffFactor.z, 0.0f));
         if (a.outSpecFactor.ptr)
-            StoreRGBA32F(AsPlane(a.outSpecFactor, w, h), x, y, make_float4(specFactor.x, specFactor.y, specFactor.z, 0.0f));
+            StoreTexel<SPLIT>(a.outSpecFactor, none, sp.rgb, kSplitSpecFactor, x, y, w, h, make_float4(specFactor.x, specFactor.y, specFactor.z, 0.0f));
     }
     const NRD_SG diffSg = LoadSg<false>(a.diffMode, a.diffWide != 0u, a.diffIn0, a.diffIn1, x, y, w, h), specSg = LoadSg<true>(a.specMode, a.specWide != 0u, a.specIn0, a.specIn1, x, y, w, h);
     const float2 scale = NRD_SG_ReJitter(diffSg, specSg, Rf0, V, roughness, viewZ, e.w, wn.w, n.w, s.w, N, Xyz(e), Xyz(wn), Xyz(n), Xyz(s));
     if (args.outScale.ptr)
         *TexelPtr<float2>(AsPlane(args.outScale, w, h), x, y) = scale;
-    const float3 diff = StoreReJittered<false>(a, a.diffMode, a.diffResolve, a.diffOut, diffSg, x, y, viewZ, N, V, roughness, scale.x, diffFactor);
-    const float3 spec = StoreReJittered<true>(a, a.specMode, a.specResolve, a.specOut, specSg, x, y, viewZ, N, V, roughness, scale.y, specFactor);
+    const float3 diff = StoreReJittered<false, SPLIT>(a, a.diffMode, a.diffResolve, a.diffOut, sp.diffHitDist, sp.rgb, diffSg, x, y, viewZ, N, V, roughness, scale.x, diffFactor);
+    const float3 spec = StoreReJittered<true, SPLIT>(a, a.specMode, a.specResolve, a.specOut, sp.specHitDist, sp.rgb, specSg, x, y, viewZ, N, V, roughness, scale.y, specFactor);
     if (a.outComposed.ptr)
-        StoreRGBA32F(AsPlane(a.outComposed, w, h), x, y, make_float4(diff.x + spec.x, diff.y + spec.y, diff.z + spec.z, 0.0f));
+        StoreTexel<SPLIT>(a.outComposed, none, sp.rgb, kSplitComposed, x, y, w, h, make_float4(diff.x + spec.x, diff.y + spec.y, diff.z + spec.z, 0.0f));
     if (a.outShadow.ptr) {
         if (a.shadowIsRGBA)
             StoreRGBA32F(AsPlane(a.outShadow, w, h), x, y, SIGMA_BackEnd_UnpackShadow(LoadRGBA8Unorm(AsPlane(a.shadow, w, h), x, y)));
@@ -531,6 +641,10 @@ __global__ void __launch_bounds__(256) ReJitterKernel(const ReJitterArgs args) {
             StoreR32F(AsPlane(a.outShadow, w, h), x, y, SIGMA_BackEnd_UnpackShadow(LoadR8Unorm(AsPlane(a.shadow, w, h), x, y)));
     }
 }
+
+__global__ void __launch_bounds__(256) ReJitterKernel(const ReJitterArgs args) { ReJitterPixel<false>(args, ResolveSplitArgs{}); }
+
+__global__ void __launch_bounds__(256) ReJitterSplitKernel(const ReJitterArgs args, const ResolveSplitArgs sp) { ReJitterPixel<true>(args, sp); }
 
 // ---- host side: validation (all of it in front of the first HIP call) and the launch ---------------------------------------------------------------
 thread_local std::string t_LastError;
@@ -547,6 +661,7 @@ uint32_t TexelBytes(nrd::Format f) {
         case F::R16_UNORM: case F::R16_SFLOAT: return 2;
         case F::RGBA8_UNORM: case F::RGBA8_SNORM: case F::R10_G10_B10_A2_UNORM: case F::R32_SFLOAT: return 4;
         case F::RGBA16_UNORM: case F::RGBA16_SNORM: case F::RGBA16_SFLOAT: case F::RG32_SFLOAT: return 8;
+        case F::RGB32_SFLOAT: return 12;
         case F::RGBA32_SFLOAT: return 16;
         default: return 0;
     }
@@ -560,6 +675,8 @@ struct Checker {
     const char* entry;
     uint32_t result = (uint32_t)nrd::Result::SUCCESS;
     uint16_t w = 0, h = 0;
+    bool split = false;   // nrdHipPackInputsSplit / nrdHipResolveOutputsSplit: CheckColour accepts RGB32_SFLOAT
+    uint32_t rgb = 0;     // kSplit* bits of the planes that hold it
 
     bool Failed() const { return result != (uint32_t)nrd::Result::SUCCESS; }
     void Error(nrd::Result r, const char* plane, const char* what) {
@@ -585,7 +702,9 @@ struct Checker {
             Error(nrd::Result::INVALID_ARGUMENT, name, "empty plane");
         else if (w && (p.width != w || p.height != h))
             Error(nrd::Result::INVALID_ARGUMENT, name, "size differs from the other planes of the call");
-        else if ((p.rowPitchBytes % bpt) != 0 || ((uintptr_t)p.data % bpt) != 0)
+        else if (bpt == 12u && ((p.rowPitchBytes % 4u) != 0 || ((uintptr_t)p.data % 4u) != 0)) // three packed dwords: dword alignment, rows need not start on a texel multiple
+            Error(nrd::Result::INVALID_ARGUMENT, name, "row pitch or pointer of an RGB32_SFLOAT plane is not a multiple of 4");
+        else if (bpt != 12u && ((p.rowPitchBytes % bpt) != 0 || ((uintptr_t)p.data % bpt) != 0))
             Error(nrd::Result::INVALID_ARGUMENT, name, "row pitch or pointer is not a multiple of the texel size");
         else if (p.rowPitchBytes < (uint32_t)p.width * bpt)
             Error(nrd::Result::INVALID_ARGUMENT, name, "row pitch below the row size");
@@ -598,6 +717,26 @@ struct Checker {
         out.ptr = (uint8_t*)p.data;
         out.pitch = p.rowPitchBytes;
         return out;
+    }
+    // a plane documented as RGBA32_SFLOAT (f1: its other format, if any): the split calls take RGB32_SFLOAT as well and note it under `bit`; the old calls answer UNSUPPORTED as ever
+    FePlane CheckColour(const NrdHipPlaneDesc& p, const char* name, const char* required, uint32_t bit, nrd::Format f1 = nrd::Format::MAX_NUM) {
+        if (split && p.data && p.format == (uint32_t)nrd::Format::RGB32_SFLOAT) {
+            const FePlane out = Check(p, name, required, nrd::Format::RGB32_SFLOAT);
+            if (out.ptr)
+                rgb |= bit;
+            return out;
+        }
+        return Check(p, name, required, nrd::Format::RGBA32_SFLOAT, f1);
+    }
+    // the R32_SFLOAT plane `.w` of an RGB32_SFLOAT plane comes from / goes to: required next to RGB32_SFLOAT (when `required`), refused next to RGBA32_SFLOAT
+    FePlane CheckCompanion(const NrdHipPlaneDesc& p, const char* name, bool ownerIsRgb, const char* required, const char* ownerName) {
+        if (Failed())
+            return FePlane{nullptr, 0};
+        if (p.data && !ownerIsRgb) {
+            Error(nrd::Result::INVALID_ARGUMENT, name, (std::string("given next to an RGBA32_SFLOAT ") + ownerName + ": .w would have two sources").c_str());
+            return FePlane{nullptr, 0};
+        }
+        return ownerIsRgb ? Check(p, name, required, nrd::Format::R32_SFLOAT) : FePlane{nullptr, 0};
     }
 };
 
@@ -638,25 +777,42 @@ bool Camera(Checker& c, const void* commonSettings, const char* why, FeCamera& o
 
 bool IsSh(uint32_t mode) { return mode == NRD_HIP_SIGNAL_REBLUR_SH || mode == NRD_HIP_SIGNAL_RELAX_SH; }
 
-void FrontEndSignal(Checker& c, const NrdHipFrontEndSignal& s, const char* name, FePlane& in, FePlane& dir, FePlane& out0, FePlane& out1) {
+// hitDistDesc: the signal's companion of NrdHipFrontEndSplit (an absent plane for the old calls); inBit / dirBit: the kSplit* bits of its two fp32 planes
+void FrontEndSignal(Checker& c, const NrdHipFrontEndSignal& s, const char* name, const NrdHipPlaneDesc& hitDistDesc, uint32_t inBit, uint32_t dirBit, FePlane& in, FePlane& dir, FePlane& out0,
+    FePlane& out1, FePlane& hitDist) {
     using F = nrd::Format;
-    if (s.mode == NRD_HIP_SIGNAL_NONE)
+    const std::string n(name), companion = "split: " + n + "HitDist";
+    if (s.mode == NRD_HIP_SIGNAL_NONE) {
+        if (hitDistDesc.data)
+            c.Error(nrd::Result::INVALID_ARGUMENT, companion.c_str(), "given for a signal whose mode is NONE");
         return;
-    const std::string n(name);
-    in = c.Check(s.radianceHitDist, (n + ".radianceHitDist").c_str(), "the signal's mode needs it", F::RGBA32_SFLOAT);
+    }
+    if (c.split && s.mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION && !s.radianceHitDist.data && hitDistDesc.data) { // the mode reads .w only: the companion alone will do
+        hitDist = c.Check(hitDistDesc, companion.c_str(), nullptr, F::R32_SFLOAT);
+        if (hitDist.ptr)
+            c.rgb |= inBit;
+    } else {
+        in = c.CheckColour(s.radianceHitDist, (n + ".radianceHitDist").c_str(), "the signal's mode needs it", inBit);
+        hitDist = c.CheckCompanion(hitDistDesc, companion.c_str(), (c.rgb & inBit) != 0u, "radianceHitDist is RGB32_SFLOAT: the hit distance comes from this plane", (n + ".radianceHitDist").c_str());
+    }
     if (IsSh(s.mode) || s.mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
-        dir = c.Check(s.direction, (n + ".direction").c_str(), "the signal's mode needs a direction plane", F::RGBA32_SFLOAT);
+        dir = c.CheckColour(s.direction, (n + ".direction").c_str(), "the signal's mode needs a direction plane", dirBit);
     const F outFormat = s.mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION ? F::R16_UNORM : s.mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION ? F::RGBA16_SNORM : F::RGBA16_SFLOAT;
     out0 = c.Check(s.out0, (n + ".out0").c_str(), "the signal's mode needs it", outFormat);
     if (IsSh(s.mode))
         out1 = c.Check(s.out1, (n + ".out1").c_str(), "the SH modes write SH1 there", F::RGBA16_SFLOAT);
 }
 
-void BackEndSignal(Checker& c, const NrdHipBackEndSignal& s, const char* name, FePlane& in0, FePlane& in1, FePlane& out, uint32_t& wide) {
+// hitDistDesc: the signal's companion of NrdHipBackEndSplit (an absent plane for the old calls); outBit: the kSplit* bit of its output
+void BackEndSignal(Checker& c, const NrdHipBackEndSignal& s, const char* name, const NrdHipPlaneDesc& hitDistDesc, uint32_t outBit, FePlane& in0, FePlane& in1, FePlane& out, FePlane& outHitDist,
+    uint32_t& wide) {
     using F = nrd::Format;
-    if (s.mode == NRD_HIP_SIGNAL_NONE)
+    const std::string n(name), companion = "split: " + n + "HitDist";
+    if (s.mode == NRD_HIP_SIGNAL_NONE) {
+        if (hitDistDesc.data)
+            c.Error(nrd::Result::INVALID_ARGUMENT, companion.c_str(), "given for a signal whose mode is NONE");
         return;
-    const std::string n(name);
+    }
     if (s.mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION)
         in0 = c.Check(s.in0, (n + ".in0").c_str(), "the signal's mode needs it", F::R16_UNORM);
     else if (s.mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
@@ -669,7 +825,14 @@ void BackEndSignal(Checker& c, const NrdHipBackEndSignal& s, const char* name, F
         if (!c.Failed() && s.in1.format != s.in0.format)
             c.Error(nrd::Result::INVALID_ARGUMENT, (n + ".in1").c_str(), "SH0 and SH1 must have the same format");
     }
-    out = c.Check(s.out, (n + ".out").c_str(), "the signal's mode needs it", s.mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION ? F::R32_SFLOAT : F::RGBA32_SFLOAT);
+    if (s.mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION) {
+        out = c.Check(s.out, (n + ".out").c_str(), "the signal's mode needs it", F::R32_SFLOAT);
+        if (hitDistDesc.data)
+            c.Error(nrd::Result::INVALID_ARGUMENT, companion.c_str(), "the occlusion mode's output is the hit distance already (R32_SFLOAT): nothing to split");
+        return;
+    }
+    out = c.CheckColour(s.out, (n + ".out").c_str(), "the signal's mode needs it", outBit);
+    outHitDist = c.CheckCompanion(hitDistDesc, companion.c_str(), (c.rgb & outBit) != 0u, nullptr, (n + ".out").c_str()); // optional: the hit distance is dropped without it
 }
 
 } // namespace
@@ -691,18 +854,23 @@ uint32_t CheckSamples(const NrdHipSignalSamples& s, uint32_t mode, const char* n
     return (uint32_t)nrd::Result::SUCCESS;
 }
 
-// a layer stride of a plane the kernel reads `num` > 1 layers of
-void CheckLayerBytes(Checker& c, uint64_t layerBytes, const FePlane& plane, uint32_t num, const char* field) {
+// a layer stride of a plane the kernel reads `num` > 1 layers of; dwords: an RGB32_SFLOAT stack or an R32_SFLOAT companion (nrdHipPackInputsSplit)
+void CheckLayerBytes(Checker& c, uint64_t layerBytes, const FePlane& plane, uint32_t num, const char* field, bool dwords = false) {
     if (c.Failed() || num <= 1u || !plane.ptr)
         return;
-    if (layerBytes % 16u)
+    if (dwords && layerBytes % 4u)
+        c.Error(nrd::Result::INVALID_ARGUMENT, field, "the layer stride is not a multiple of 4");
+    else if (!dwords && layerBytes % 16u)
         c.Error(nrd::Result::INVALID_ARGUMENT, field, "the layer stride is not a multiple of 16 (the texel size)");
     else if (layerBytes < (uint64_t)plane.pitch * c.h)
         c.Error(nrd::Result::INVALID_ARGUMENT, field, "the layer stride is below rowPitchBytes x height of the plane");
 }
 
-uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, void* hipStream) {
+// split != nullptr or splitEntry: nrdHipPackInputsSplit -- RGB32_SFLOAT planes and their companions are accepted
+uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, const NrdHipFrontEndSplit* split, bool splitEntry, void* hipStream) {
     using F = nrd::Format;
+    static const NrdHipFrontEndSplit noSplit = {};
+    const NrdHipFrontEndSplit& sd = split ? *split : noSplit;
     if (!d)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputs: null descriptor");
     if (d->diffuse.mode > NRD_HIP_SIGNAL_RELAX_SH || d->specular.mode > NRD_HIP_SIGNAL_RELAX_SH || d->specular.mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
@@ -726,32 +894,47 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
         sa.trim = samples->hitDistTrimThreshold;
     }
     const bool multiSample = sa.diffNum > 1u || sa.specNum > 1u || sa.trim > 0.0f; // else: the kernels of nrdHipPackInputsEx, the same bytes, no extra loads
-    Checker c{"nrdHipPackInputs"};
+    const char* entry = splitEntry ? "nrdHipPackInputsSplit" : "nrdHipPackInputs";
+    Checker c{entry};
+    c.split = splitEntry;
     PackArgs a = {};
-    a.normalRoughness = c.Check(d->normalRoughness, "normalRoughness", "required", F::RGBA32_SFLOAT);
+    SplitArgs sp = {};
+    a.normalRoughness = c.CheckColour(d->normalRoughness, "normalRoughness", "required", kSplitNormalRoughness);
+    sp.roughness = c.CheckCompanion(sd.roughness, "split: roughness", (c.rgb & kSplitNormalRoughness) != 0u, "normalRoughness is RGB32_SFLOAT: the roughness comes from this plane", "normalRoughness");
     a.viewZ = c.Check(d->viewZ, "viewZ", "required", F::R32_SFLOAT);
     a.materialID = c.Check(d->materialID, "materialID", nullptr, F::R32_SFLOAT);
     a.outNormalRoughness = c.Check(d->outNormalRoughness, "outNormalRoughness", nullptr, kNormalRoughnessFormat);
     a.outViewZ = c.Check(d->outViewZ, "outViewZ", nullptr, F::R32_SFLOAT);
     a.outMv = c.Check(d->outMv, "outMv", nullptr, F::RGBA16_SFLOAT);
-    a.motion = c.Check(d->motion, "motion", a.outMv.ptr ? "outMv needs it" : nullptr, F::RGBA32_SFLOAT, F::RG32_SFLOAT);
+    a.motion = c.CheckColour(d->motion, "motion", a.outMv.ptr ? "outMv needs it" : nullptr, kSplitMotion, F::RG32_SFLOAT);
     a.motionIsRG = d->motion.format == (uint32_t)F::RG32_SFLOAT;
     a.outPenumbra = c.Check(d->outPenumbra, "outPenumbra", nullptr, F::R16_SFLOAT);
     a.outTranslucency = c.Check(d->outTranslucency, "outTranslucency", nullptr, F::RGBA8_UNORM);
     a.occluder = c.Check(d->distanceToOccluder, "distanceToOccluder", a.outPenumbra.ptr || a.outTranslucency.ptr ? "outPenumbra / outTranslucency need it" : nullptr, F::R32_SFLOAT);
-    a.translucency = c.Check(d->translucency, "translucency", a.outTranslucency.ptr ? "outTranslucency needs it" : nullptr, F::RGBA32_SFLOAT);
+    a.translucency = c.CheckColour(d->translucency, "translucency", a.outTranslucency.ptr ? "outTranslucency needs it" : nullptr, kSplitTranslucency);
     const bool demodulate = d->albedo.data || d->rf0.data;
-    a.albedo = c.Check(d->albedo, "albedo", demodulate ? "demodulation needs albedo and rf0" : nullptr, F::RGBA32_SFLOAT);
-    a.rf0 = c.Check(d->rf0, "rf0", demodulate ? "demodulation needs albedo and rf0" : nullptr, F::RGBA32_SFLOAT);
-    FrontEndSignal(c, d->diffuse, "diffuse", a.diffIn, a.diffDir, a.diffOut0, a.diffOut1);
-    FrontEndSignal(c, d->specular, "specular", a.specIn, a.specDir, a.specOut0, a.specOut1);
-    if (multiSample && samples) {
+    a.albedo = c.CheckColour(d->albedo, "albedo", demodulate ? "demodulation needs albedo and rf0" : nullptr, kSplitAlbedo);
+    a.rf0 = c.CheckColour(d->rf0, "rf0", demodulate ? "demodulation needs albedo and rf0" : nullptr, kSplitRf0);
+    FrontEndSignal(c, d->diffuse, "diffuse", sd.diffuseHitDist, kSplitDiffIn, kSplitDiffDir, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sp.diffHitDist);
+    FrontEndSignal(c, d->specular, "specular", sd.specularHitDist, kSplitSpecIn, kSplitSpecDir, a.specIn, a.specDir, a.specOut0, a.specOut1, sp.specHitDist);
+    if (multiSample && samples && splitEntry) { // the same rules, in dwords where the stack holds RGB32_SFLOAT texels, and for the companions
+        CheckLayerBytes(c, sa.diffInLayer = samples->diffuse.radianceHitDistLayerBytes, a.diffIn, sa.diffNum, "samples: diffuse.radianceHitDistLayerBytes", (c.rgb & kSplitDiffIn) != 0u);
+        CheckLayerBytes(c, sa.diffDirLayer = samples->diffuse.directionLayerBytes, a.diffDir, sa.diffNum, "samples: diffuse.directionLayerBytes", (c.rgb & kSplitDiffDir) != 0u);
+        CheckLayerBytes(c, sa.specInLayer = samples->specular.radianceHitDistLayerBytes, a.specIn, sa.specNum, "samples: specular.radianceHitDistLayerBytes", (c.rgb & kSplitSpecIn) != 0u);
+        CheckLayerBytes(c, sa.specDirLayer = samples->specular.directionLayerBytes, a.specDir, sa.specNum, "samples: specular.directionLayerBytes", (c.rgb & kSplitSpecDir) != 0u);
+        CheckLayerBytes(c, sp.diffHitDistLayer = sd.diffuseHitDistLayerBytes, sp.diffHitDist, sa.diffNum, "split: diffuseHitDistLayerBytes", true);
+        CheckLayerBytes(c, sp.specHitDistLayer = sd.specularHitDistLayerBytes, sp.specHitDist, sa.specNum, "split: specularHitDistLayerBytes", true);
+        if (!a.diffIn.ptr) // (the occlusion mode on its companion alone: no plane to step through)
+            sa.diffInLayer = 0;
+        if (!a.specIn.ptr)
+            sa.specInLayer = 0;
+    } else if (multiSample && samples) {
         c.entry = "nrdHipPackInputsSamples";
         CheckLayerBytes(c, sa.diffInLayer = samples->diffuse.radianceHitDistLayerBytes, a.diffIn, sa.diffNum, "samples: diffuse.radianceHitDistLayerBytes");
         CheckLayerBytes(c, sa.diffDirLayer = samples->diffuse.directionLayerBytes, a.diffDir, sa.diffNum, "samples: diffuse.directionLayerBytes");
         CheckLayerBytes(c, sa.specInLayer = samples->specular.radianceHitDistLayerBytes, a.specIn, sa.specNum, "samples: specular.radianceHitDistLayerBytes");
         CheckLayerBytes(c, sa.specDirLayer = samples->specular.directionLayerBytes, a.specDir, sa.specNum, "samples: specular.directionLayerBytes");
-        c.entry = "nrdHipPackInputs";
+        c.entry = entry;
     }
     if (demodulate)
         Camera(c, d->commonSettings, "demodulation needs the frame's camera", a.camera);
@@ -767,7 +950,18 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
     a.h = c.h;
     t_LastError.clear();
     const dim3 grid((c.w + 63u) / 64u, (c.h + 3u) / 4u), block(64, 4);
-    if (multiSample) {
+    if (c.rgb) { // something to split: the twins. (Else the kernels of the old calls: the same code, the same bytes.)
+        sp.rgb = c.rgb;
+        const uint32_t diffCell = checkerboardMode == (uint32_t)nrd::CheckerboardMode::BLACK ? 0u : 1u, frameIndex = options ? options->frameIndex & 1u : 0u;
+        if (multiSample && checkerboardMode)
+            hipLaunchKernelGGL(PackSamplesSplitKernel<true>, grid, block, 0, (hipStream_t)hipStream, a, sa, sp, diffCell, frameIndex);
+        else if (multiSample)
+            hipLaunchKernelGGL(PackSamplesSplitKernel<false>, grid, block, 0, (hipStream_t)hipStream, a, sa, sp, 0u, 0u);
+        else if (checkerboardMode)
+            hipLaunchKernelGGL(PackCheckerboardSplitKernel, grid, block, 0, (hipStream_t)hipStream, a, sp, diffCell, frameIndex);
+        else
+            hipLaunchKernelGGL(PackInputsSplitKernel, grid, block, 0, (hipStream_t)hipStream, a, sp);
+    } else if (multiSample) {
         const uint32_t diffCell = checkerboardMode == (uint32_t)nrd::CheckerboardMode::BLACK ? 0u : 1u, frameIndex = options ? options->frameIndex & 1u : 0u;
         if (checkerboardMode)
             hipLaunchKernelGGL(PackSamplesKernel<true>, grid, block, 0, (hipStream_t)hipStream, a, sa, diffCell, frameIndex);
@@ -784,17 +978,27 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
 } // namespace
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsEx(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, void* hipStream) {
-    return PackInputs(d, options, nullptr, hipStream);
+    return PackInputs(d, options, nullptr, nullptr, false, hipStream);
 }
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsSamples(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, void* hipStream) {
-    return PackInputs(d, options, samples, hipStream);
+    return PackInputs(d, options, samples, nullptr, false, hipStream);
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsSplit(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples,
+    const NrdHipFrontEndSplit* split, void* hipStream) {
+    return PackInputs(d, options, samples, split, true, hipStream);
 }
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputs(const NrdHipFrontEndDesc* d, void* hipStream) { return nrdHipPackInputsEx(d, nullptr, hipStream); }
 
-extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsEx(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* options, void* hipStream) {
+namespace {
+
+// splitEntry: nrdHipResolveOutputsSplit -- RGB32_SFLOAT planes and the hit-distance companions are accepted
+uint32_t ResolveOutputs(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* options, const NrdHipBackEndSplit* split, bool splitEntry, void* hipStream) {
     using F = nrd::Format;
+    static const NrdHipBackEndSplit noSplit = {};
+    const NrdHipBackEndSplit& sd = split ? *split : noSplit;
     if (!d)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputs: null descriptor");
     const bool reJitter = options && options->reJitter;
@@ -808,18 +1012,20 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsE
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsEx: options: reJitter scales a resolved colour: the resolve of both signals must be SH or SG, not SG_EXTRACT_COLOR");
     if (!reJitter && options && options->outReJitterScale.data)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsEx: options: outReJitterScale: given without reJitter");
-    Checker c{"nrdHipResolveOutputs"};
+    Checker c{splitEntry ? "nrdHipResolveOutputsSplit" : "nrdHipResolveOutputs"};
+    c.split = splitEntry;
     ReJitterArgs ra = {};
     ResolveArgs& a = ra.r;
-    BackEndSignal(c, ds, "diffuse", a.diffIn0, a.diffIn1, a.diffOut, a.diffWide);
-    BackEndSignal(c, ss, "specular", a.specIn0, a.specIn1, a.specOut, a.specWide);
+    ResolveSplitArgs sp = {};
+    BackEndSignal(c, ds, "diffuse", sd.diffuseHitDist, kSplitDiffOut, a.diffIn0, a.diffIn1, a.diffOut, sp.diffHitDist, a.diffWide);
+    BackEndSignal(c, ss, "specular", sd.specularHitDist, kSplitSpecOut, a.specIn0, a.specIn1, a.specOut, sp.specHitDist, a.specWide);
     a.shadow = c.Check(d->shadow, "shadow", d->outShadow.data ? "outShadow needs it" : nullptr, F::R8_UNORM, F::RGBA8_UNORM);
     a.shadowIsRGBA = d->shadow.format == (uint32_t)F::RGBA8_UNORM;
     a.outShadow = c.Check(d->outShadow, "outShadow", nullptr, a.shadowIsRGBA ? F::RGBA32_SFLOAT : F::R32_SFLOAT);
-    a.outComposed = c.Check(d->outComposed, "outComposed", nullptr, F::RGBA32_SFLOAT);
-    a.outViewVector = c.Check(d->outViewVector, "outViewVector", nullptr, F::RGBA32_SFLOAT);
-    a.outDiffFactor = c.Check(d->outDiffFactor, "outDiffFactor", nullptr, F::RGBA32_SFLOAT);
-    a.outSpecFactor = c.Check(d->outSpecFactor, "outSpecFactor", nullptr, F::RGBA32_SFLOAT);
+    a.outComposed = c.CheckColour(d->outComposed, "outComposed", nullptr, kSplitComposed);
+    a.outViewVector = c.CheckColour(d->outViewVector, "outViewVector", nullptr, kSplitViewVector);
+    a.outDiffFactor = c.CheckColour(d->outDiffFactor, "outDiffFactor", nullptr, kSplitDiffFactor);
+    a.outSpecFactor = c.CheckColour(d->outSpecFactor, "outSpecFactor", nullptr, kSplitSpecFactor);
     auto resolved = [](const NrdHipBackEndSignal& s) { return IsSh(s.mode) || s.mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION; };
     auto carriesColour = [](const NrdHipBackEndSignal& s) { return s.mode != NRD_HIP_SIGNAL_NONE && s.mode != NRD_HIP_SIGNAL_REBLUR_OCCLUSION; };
     const bool reblurSpec = ss.mode >= NRD_HIP_SIGNAL_REBLUR_RADIANCE && ss.mode <= NRD_HIP_SIGNAL_REBLUR_OCCLUSION;
@@ -832,8 +1038,8 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsE
         c.Error(nrd::Result::INVALID_ARGUMENT, "outComposed", "needs a diffuse and a specular signal that carry a colour");
     a.normalRoughness = c.Check(d->normalRoughness, "normalRoughness", needN ? "the chosen resolves / remodulation / specular hit distance need N and the roughness" : nullptr, kNormalRoughnessFormat);
     a.viewZ = c.Check(d->viewZ, "viewZ", needV || (d->denormalizeHitDist && anyReblur) ? "the view vector / denormalizeHitDist need it" : nullptr, F::R32_SFLOAT);
-    a.albedo = c.Check(d->albedo, "albedo", needFactors ? "remodulation needs albedo and rf0" : nullptr, F::RGBA32_SFLOAT);
-    a.rf0 = c.Check(d->rf0, "rf0", needFactors ? "remodulation needs albedo and rf0" : reJitter ? "reJitter needs Rf0" : nullptr, F::RGBA32_SFLOAT);
+    a.albedo = c.CheckColour(d->albedo, "albedo", needFactors ? "remodulation needs albedo and rf0" : nullptr, kSplitAlbedo);
+    a.rf0 = c.CheckColour(d->rf0, "rf0", needFactors ? "remodulation needs albedo and rf0" : reJitter ? "reJitter needs Rf0" : nullptr, kSplitRf0);
     if (reJitter)
         ra.outScale = c.Check(options->outReJitterScale, "outReJitterScale", nullptr, F::RG32_SFLOAT);
     if (!c.Failed() && !c.w)
@@ -854,12 +1060,28 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsE
     a.w = c.w;
     a.h = c.h;
     t_LastError.clear();
-    if (reJitter)
+    sp.rgb = c.rgb;
+    const dim3 reJitterGrid((c.w + (uint32_t)kReJitterTileW - 1u) / (uint32_t)kReJitterTileW, (c.h + (uint32_t)kReJitterTileH - 1u) / (uint32_t)kReJitterTileH);
+    if (c.rgb && reJitter) // something to split: the twins. (Else the kernels of the old calls: the same code, the same bytes.)
+        hipLaunchKernelGGL(ReJitterSplitKernel, reJitterGrid, dim3(kReJitterTileW, kReJitterTileH), 0, (hipStream_t)hipStream, ra, sp);
+    else if (c.rgb)
+        hipLaunchKernelGGL(ResolveOutputsSplitKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a, sp);
+    else if (reJitter)
         hipLaunchKernelGGL(ReJitterKernel, dim3((c.w + (uint32_t)kReJitterTileW - 1u) / (uint32_t)kReJitterTileW, (c.h + (uint32_t)kReJitterTileH - 1u) / (uint32_t)kReJitterTileH),
             dim3(kReJitterTileW, kReJitterTileH), 0, (hipStream_t)hipStream, ra);
     else
         hipLaunchKernelGGL(ResolveOutputsKernel, dim3((c.w + 63u) / 64u, (c.h + 3u) / 4u), dim3(64, 4), 0, (hipStream_t)hipStream, a);
     return hipGetLastError() == hipSuccess ? (uint32_t)nrd::Result::SUCCESS : Fail(nrd::Result::FAILURE, "nrdHipResolveOutputs: the kernel launch failed");
+}
+
+} // namespace
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsEx(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* options, void* hipStream) {
+    return ResolveOutputs(d, options, nullptr, false, hipStream);
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsSplit(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* options, const NrdHipBackEndSplit* split, void* hipStream) {
+    return ResolveOutputs(d, options, split, true, hipStream);
 }
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputs(const NrdHipBackEndDesc* d, void* hipStream) { return nrdHipResolveOutputsEx(d, nullptr, hipStream); }

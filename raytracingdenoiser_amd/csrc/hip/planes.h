@@ -243,6 +243,21 @@ NRD_D void StoreRGBA16FHinted(const Plane& p, int x, int y, float4 v) {
 NRD_D float4 LoadRGBA32F(const Plane& p, int x, int y) { return *TexelPtr<const float4>(p, x, y); }
 NRD_D void StoreRGBA32F(const Plane& p, int x, int y, float4 v) { *TexelPtr<float4>(p, x, y) = v; }
 
+// ---- RGB32_SFLOAT ---------------------------------------------------------------------------------------------------
+// 12-byte texels, 4-byte aligned: one global_load_dwordx3 / global_store_dwordx3 per lane, a wave covers 768 contiguous bytes of a row. Never a 16-byte access: a load
+// would read past the end of the plane, a store would overwrite .x of the next texel (or the row padding). x * 12 stays inside the 24-bit multiply of TexelOffset.
+struct Rgb32Texel {
+    float x, y, z;
+};
+static_assert(sizeof(Rgb32Texel) == 12 && alignof(Rgb32Texel) == 4, "RGB32_SFLOAT texels are three packed dwords");
+// `.xyz` of a texel whose size is a uniform of the kernel: bytesPerTexel = 12 (RGB32_SFLOAT) or 16 (RGBA32_SFLOAT, .w not read) -- the same 12-byte load at either lane stride
+NRD_D float3 LoadXyz32F(const Plane& p, int x, int y, uint32_t bytesPerTexel) {
+    const Rgb32Texel v = *(const Rgb32Texel*)(p.ptr + TexelOffset(p, x, y, bytesPerTexel, true));
+    return make_float3(v.x, v.y, v.z);
+}
+NRD_D float3 LoadRGB32F(const Plane& p, int x, int y) { return LoadXyz32F(p, x, y, 12u); }
+NRD_D void StoreRGB32F(const Plane& p, int x, int y, float3 v) { *TexelPtr<Rgb32Texel>(p, x, y) = Rgb32Texel{v.x, v.y, v.z}; }
+
 // ---- UNORM --------------------------------------------------------------------------------------------------------
 NRD_D float Saturate(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 NRD_D uint32_t ToUnorm(float x, float maxValue) { return (uint32_t)floorf(Saturate(x) * maxValue + 0.5f); }

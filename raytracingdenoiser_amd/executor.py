@@ -70,7 +70,7 @@ class HipExecutor:
     def resolve(self, diffuse_mode=None, specular_mode=None, resolve=0, shadow=False, **kw):
         """frontend.resolve_outputs on the planes bound to this executor: the OUT_* planes of the given signal modes (frontend.SignalMode; `resolve` = frontend.ResolveMode for the
         SH modes), OUT_SHADOW_TRANSLUCENCY with shadow=True, IN_NORMAL_ROUGHNESS / IN_VIEWZ where bound, the camera of the last SetCommonSettings, on the executor's stream.
-        Further keywords (albedo, rf0, remodulate, denormalize_hit_dist, want, out, ...) are passed on. Returns fp32 tensors by name."""
+        Further keywords (albedo, rf0, remodulate, denormalize_hit_dist, want, out, channels=3 for [H, W, 3] colour outputs, ...) are passed on. Returns fp32 tensors by name."""
         from . import frontend
 
         args = dict(normal_roughness=self._bound.get(int(api.ResourceType.IN_NORMAL_ROUGHNESS)), viewz=self._bound.get(int(api.ResourceType.IN_VIEWZ)),

@@ -1,7 +1,8 @@
 """Front end / back end on the device: plumbing over nrdHipPackInputs(Ex) / nrdHipResolveOutputs(Ex) (include/NRDHip.h).
 
 pack_inputs() turns an application's fp32 buffers into the packed planes HipExecutor.bind accepts, resolve_outputs() turns the denoised OUT_* planes into
-linear fp32 radiance -- one kernel launch each, asynchronous on the current stream, usable inside torch.cuda.graph. This module allocates and calls the
+linear fp32 radiance -- one kernel launch each, asynchronous on the current stream, usable inside torch.cuda.graph. Buffers may be four-channel, or three-channel with `.w`
+(roughness, hit distance) in an array of its own, as a tensor host holds them: those are read and written where they lie (nrdHipPackInputsSplit / nrdHipResolveOutputsSplit). This module allocates and calls the
 C-ABI; it computes nothing (no arithmetic on tensors, no fallback). Planes are CUDA tensors; numpy arrays are accepted as well, for a library whose "device
 memory" is host memory (the CPU emulation of the device sources that the test-suite builds).
 """
@@ -71,7 +72,7 @@ def _fp32_plane(t, channels, what):
     """HipPlaneDesc of an fp32 [H, W, channels] ([H, W] for one channel) array"""
     assert _dtype_name(t) == "float32", "%s must be float32" % what
     assert (t.ndim == 2 and channels == 1) or (t.ndim == 3 and t.shape[2] == channels), "%s: expected %d channel(s) per pixel, got shape %s" % (what, channels, tuple(t.shape))
-    return _plane(t, {1: F.R32_SFLOAT, 2: F.RG32_SFLOAT, 4: F.RGBA32_SFLOAT}[channels])
+    return _plane(t, {1: F.R32_SFLOAT, 2: F.RG32_SFLOAT, 3: F.RGB32_SFLOAT, 4: F.RGBA32_SFLOAT}[channels])
 
 
 def rgba(xyz, w=None):
@@ -85,30 +86,64 @@ def rgba(xyz, w=None):
     return out
 
 
-def _rgba_arg(t, what):
-    if isinstance(t, (tuple, list)):
+def _is_pair(t):
+    return isinstance(t, (tuple, list))
+
+
+def _rgba_arg(t, what, in_place=False, needs_w=False):
+    """(array the plane points into, its HipPlaneDesc). Three-channel data -- an (xyz, w) pair or an [H, W, 3] array -- is widened into a new [H, W, 4] copy, or with in_place
+    described where it lies as RGB32_SFLOAT (nrdHipPackInputsSplit / nrdHipResolveOutputsSplit; the w of a pair goes into the split struct: pack_split). needs_w: a plane whose .w
+    is consumed -- a bare [H, W, 3] array has none to give in place and is widened with zeros as ever."""
+    if _stays(t, in_place, needs_w):
+        xyz = t[0] if _is_pair(t) else t
+        return xyz, _fp32_plane(xyz, 3, what)
+    if _is_pair(t):
         t = rgba(*t)
     elif t.ndim == 3 and t.shape[2] == 3:
         t = rgba(t)
     return t, _fp32_plane(t, 4, what)
 
 
-def _layers(t):
+def _stride0_bytes(t):
+    return t.strides[0] if _is_numpy(t) else t.stride(0) * t.element_size()
+
+
+def _rows_dense(t, channels):
+    """are the rows of `t` ([.., W, channels], or [.., W] for channels = 0) dense float32 -- what a plane descriptor can point at"""
+    strides = [x // t.itemsize for x in t.strides] if _is_numpy(t) else list(t.stride())
+    want = [channels, 1] if channels else [1]
+    return _dtype_name(t) == "float32" and (t.shape[-1] == channels or not channels) and strides[-len(want):] == want
+
+
+def _stays(t, in_place, needs_w):
+    """is three-channel data `t` -- an (xyz, w) pair, or an [.., 3] array where .w is not consumed -- described where it lies (see _rgba_arg)? Data whose rows are not dense
+    (a [..., :3] view of a wider tensor) is widened as ever."""
+    if not in_place:
+        return False
+    if _is_pair(t):
+        return (t[0] is None or _rows_dense(t[0], 3)) and _rows_dense(t[1], 0)
+    return not needs_w and t.shape[-1] == 3 and _rows_dense(t, 3)
+
+
+def _layers(t, in_place=False, needs_w=False):
     """(is it a stack of sample layers, N, bytes from one layer to the next) of a signal argument: [N, H, W, 4], [N, H, W, 3] or an ([N, H, W, 3], [N, H, W]) pair are stacks --
-    a three-channel stack is widened into a dense copy -- anything else is one layer"""
-    first = t[0] if isinstance(t, (tuple, list)) else t
-    if first.ndim != 4:
+    a three-channel stack is widened into a dense copy, or with in_place described where it lies -- anything else is one layer"""
+    first = t[0] if _is_pair(t) else t
+    if first is None or first.ndim != 4:
         return False, 1, 0
-    if isinstance(t, (tuple, list)) or first.shape[3] == 3:
+    if (_is_pair(t) or first.shape[3] == 3) and not _stays(t, in_place, needs_w):
         return True, first.shape[0], first.shape[1] * first.shape[2] * 16
-    return True, first.shape[0], (first.strides[0] if _is_numpy(first) else first.stride(0) * first.element_size())
+    return True, first.shape[0], _stride0_bytes(first)
 
 
-def _signal_arg(t, what):
+def _signal_arg(t, what, in_place=False, needs_w=False):
     """_rgba_arg for a signal plane that may be a stack of sample layers: the plane is that of layer 0"""
     if not _layers(t)[0]:
-        return _rgba_arg(t, what)
-    if isinstance(t, (tuple, list)):
+        return _rgba_arg(t, what, in_place, needs_w)
+    if _stays(t, in_place, needs_w):
+        xyz = t[0] if _is_pair(t) else t
+        return xyz, _fp32_plane(xyz[0], 3, what)
+    if _is_pair(t):
         t = rgba(*t)
     elif t.shape[3] == 3:
         t = rgba(t)
@@ -126,9 +161,10 @@ def _stream(like, stream):
 
 
 class _stream_scope:
-    """torch tensors: makes `stream` (a torch.cuda.Stream) the current one for the body, so that what the body allocates -- the widened [H, W, 4] copies of three-channel inputs,
-    which die when the call returns while the launch is still in flight -- is allocated, filled and released in the order of the stream the kernel runs on (the caching
-    allocator is stream-ordered). A raw stream handle (an int) cannot be made current: such a caller passes four-channel planes, or keeps to the current stream."""
+    """torch tensors: makes `stream` (a torch.cuda.Stream) the current one for the body, so that what the body allocates -- the output planes, and with in_place=False the widened
+    [H, W, 4] copies of three-channel inputs, which die when the call returns while the launch is still in flight -- is allocated, filled and released in the order of the
+    stream the kernel runs on (the caching allocator is stream-ordered). A raw stream handle (an int) cannot be made current: such a caller passes `out`, and three-channel
+    inputs in place (the default) or four-channel planes."""
 
     def __init__(self, like, stream):
         self.ctx = None
@@ -166,17 +202,27 @@ def _reuse(out, key, like, shape, dtype):
 
 # ---- front end -------------------------------------------------------------------------------------------------------------------------------------------
 def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0, **kw):
-    """see describe_pack; launches on `stream` (a torch.cuda.Stream, or a raw handle with four-channel inputs only; default: the current stream) and returns the packed planes.
+    """see describe_pack; launches on `stream` (a torch.cuda.Stream or a raw handle; default: the current stream) and returns the packed planes. Three-channel arrays, (xyz, w)
+    pairs and [N, H, W, 3] stacks are read where they lie through nrdHipPackInputsSplit -- no copy, no allocation (in_place=False: widened into [.., 4] copies first, as before;
+    that path allocates, so a raw stream handle suits it with four-channel inputs only); four-channel arguments take the calls they always took.
     checkerboard_mode (api.CheckerboardMode) other than OFF: the noisy signals are traced for every other pixel of frame `frame_index` (CommonSettings::frameIndex) and their
     texels go to the left half of the signal planes, whose other texels are left as they are (NRDHip.h nrdHipPackInputsEx). A signal given as a stack of sample layers
     ([N, H, W, 4]: many paths per pixel) or hit_dist_trim != 0 goes through nrdHipPackInputsSamples, which reduces the layers by the reference's rules in the same launch;
     every other call is the call it was."""
+    given = inspect.signature(describe_pack).bind(normal_roughness, viewz, *args, **kw).arguments
+    in_place = given.get("in_place")
+    in_place = PACK_IN_PLACE if in_place is None else bool(in_place)
+    kw = dict(kw, in_place=in_place)
     with _stream_scope(viewz, kw.get("stream")):
         res, d, keep = describe_pack(normal_roughness, viewz, *args, **kw)
         lib = kw.get("lib") or api.load_library()
-        given = inspect.signature(describe_pack).bind(normal_roughness, viewz, *args, **kw).arguments
         layered = any(_layers(sig[k])[0] for sig in (given.get("diffuse"), given.get("specular")) if sig for k in ("radiance_hitdist", "direction") if sig.get(k) is not None)
-        if layered or given.get("hit_dist_trim", 0.0) != 0.0:  # many paths per pixel (NRDHip.h nrdHipPackInputsSamples)
+        split = pack_split(normal_roughness, given.get("diffuse"), given.get("specular")) if in_place else None
+        if split is not None and _anything_split(d, split):  # three-channel planes and (xyz, w) pairs where they lie (NRDHip.h nrdHipPackInputsSplit): no copy, no allocation
+            samples = pack_samples(given.get("diffuse"), given.get("specular"), given.get("hit_dist_trim", 0.0), in_place=True)
+            options = pack_options(checkerboard_mode, frame_index)
+            _check(lib, lib.nrdHipPackInputsSplit(C.byref(d), C.byref(options), C.byref(samples), C.byref(split), _stream(viewz, kw.get("stream"))), "nrdHipPackInputsSplit")
+        elif layered or given.get("hit_dist_trim", 0.0) != 0.0:  # many paths per pixel (NRDHip.h nrdHipPackInputsSamples)
             samples = pack_samples(given.get("diffuse"), given.get("specular"), given.get("hit_dist_trim", 0.0))
             options = pack_options(checkerboard_mode, frame_index)
             _check(lib, lib.nrdHipPackInputsSamples(C.byref(d), C.byref(options), C.byref(samples), _stream(viewz, kw.get("stream"))), "nrdHipPackInputsSamples")
@@ -193,24 +239,57 @@ def pack_options(checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0):
     return api.HipFrontEndOptions(int(checkerboard_mode), int(frame_index) & 0xFFFFFFFF)
 
 
-def pack_samples(diffuse=None, specular=None, hit_dist_trim=0.0):
+def pack_samples(diffuse=None, specular=None, hit_dist_trim=0.0, in_place=False):
     """api.HipFrontEndSamples for nrdHipPackInputsSamples, next to the descriptor of describe_pack, from the same diffuse / specular dicts: the sample counts and the layer
-    strides (the arrays' stride(0); a three-channel stack or a pair is widened by describe_pack into a dense [N, H, W, 4] copy). hit_dist_trim > 0: every sample's hit
-    distance goes through NRD_FrontEnd_TrimHitDistance first."""
+    strides (the arrays' stride(0); a three-channel stack or a pair is widened by describe_pack into a dense [N, H, W, 4] copy -- with in_place, as given to describe_pack,
+    it stays where it is and the stride is its own). hit_dist_trim > 0: every sample's hit distance goes through NRD_FrontEnd_TrimHitDistance first."""
     samples = api.HipFrontEndSamples()
     samples.hitDistTrimThreshold = float(hit_dist_trim)
     for sig, dst in ((diffuse, samples.diffuse), (specular, samples.specular)):
         if sig is None:
             continue
-        _, dst.samplesNum, dst.radianceHitDistLayerBytes = _layers(sig["radiance_hitdist"])
+        rh = sig["radiance_hitdist"]
+        if _is_pair(rh) and rh[0] is None:  # the occlusion mode on its hit-distance plane alone (in_place)
+            dst.samplesNum = rh[1].shape[0] if rh[1].ndim == 3 else 1
+        else:
+            _, dst.samplesNum, dst.radianceHitDistLayerBytes = _layers(rh, in_place, True)
         if sig.get("direction") is not None:
-            _, n, dst.directionLayerBytes = _layers(sig["direction"])
+            _, n, dst.directionLayerBytes = _layers(sig["direction"], in_place)
             assert n == dst.samplesNum, "direction and radiance_hitdist must have the same number of sample layers"
     return samples
 
 
+# Whether pack_inputs takes three-channel input where it lies by default (in_place=None). Decided by tools/frontend_bench.py --split (DESIGN.md section 3.4, the `split` object of
+# profiles/frontend_bench.json): at 2560 x 1440 the in-place call takes 0.068 ms against 0.119 ms of widening + 0.066 ms of the four-channel call.
+PACK_IN_PLACE = True
+
+
+def pack_split(normal_roughness, diffuse=None, specular=None):
+    """api.HipFrontEndSplit for nrdHipPackInputsSplit, next to the descriptor of describe_pack(in_place=True), from the same arguments: the w halves of the (xyz, w) pairs --
+    roughness [H, W] of a (normal, roughness) pair, hit_dist [H, W] (or [N, H, W] with its layer stride) of a (radiance, hit_dist) pair; (None, hit_dist) in the occlusion mode.
+    The struct points at the caller's arrays: a relaunch sees what they hold then."""
+    split = api.HipFrontEndSplit()
+    if _stays(normal_roughness, True, True):
+        split.roughness = _fp32_plane(normal_roughness[1], 1, "roughness")
+    for which, sig in (("diffuse", diffuse), ("specular", specular)):
+        if sig is None or not _stays(sig["radiance_hitdist"], True, True):
+            continue
+        hit = sig["radiance_hitdist"][1]
+        if hit.ndim == 3:
+            setattr(split, which + "HitDistLayerBytes", _stride0_bytes(hit))
+            hit = hit[0]
+        setattr(split, which + "HitDist", _fp32_plane(hit, 1, which + " hit_dist"))
+    return split
+
+
+def _anything_split(d, split):
+    planes = [d.normalRoughness, d.motion, d.albedo, d.rf0, d.translucency, d.diffuse.radianceHitDist, d.diffuse.direction, d.specular.radianceHitDist, d.specular.direction]
+    return any(p.data and p.format == int(F.RGB32_SFLOAT) for p in planes) or any(p.data for p in (split.roughness, split.diffuseHitDist, split.specularHitDist))
+
+
 def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffuse=None, specular=None, albedo=None, rf0=None, distance_to_occluder=None, translucency=None,
-                  common_settings=None, hit_dist_params=HIT_DIST_PARAMS, viewz_scale=1.0, tan_of_light_angular_radius=0.0, out=None, stream=None, lib=None, hit_dist_trim=0.0):
+                  common_settings=None, hit_dist_params=HIT_DIST_PARAMS, viewz_scale=1.0, tan_of_light_angular_radius=0.0, out=None, stream=None, lib=None, hit_dist_trim=0.0,
+                  in_place=None):
     """The descriptor of one nrdHipPackInputs launch, without launching: (packed planes, api.HipFrontEndDesc, arrays the descriptor points into besides its arguments) -- for a
     caller that launches the same frame layout repeatedly through the C-ABI itself. fp32 inputs: normal_roughness [H, W, 4] (or a (normal [H, W, 3], roughness [H, W]) pair), viewz [H, W], material_id [H, W],
     motion [H, W, 4] or [H, W, 2], albedo / rf0 / translucency [H, W, 4] or [H, W, 3], distance_to_occluder [H, W]; diffuse / specular: dict(mode=SignalMode,
@@ -218,10 +297,15 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
     common_settings switch demodulation on. Many paths per pixel: a signal's radiance_hitdist may be [N, H, W, 4] or ([N, H, W, 3], [N, H, W]) and its direction
     [N, H, W, 4] or [N, H, W, 3] with the same N (layers may be pitched or padded: the layer stride is stride(0)); the descriptor then holds layer 0 and pack_samples
     the rest, with hit_dist_trim, for nrdHipPackInputsSamples. Returns {ResourceType: (packed array, Format)}, ready for HipExecutor.bind_packed; `out` = a dict returned earlier, whose
-    arrays are written again instead of allocating."""
+    arrays are written again instead of allocating.
+    in_place=True (default here: False -- the descriptor then suits nrdHipPackInputs / Ex / Samples): three-channel arrays, (xyz, w) pairs and [N, H, W, 3] stacks are not widened;
+    the descriptor points at the caller's own arrays as RGB32_SFLOAT planes and is for nrdHipPackInputsSplit alone, with pack_split(...) for the w halves and
+    pack_samples(..., in_place=True): a relaunch after the caller refreshed its tensors packs the new values. (A bare [H, W, 3] normal_roughness / radiance_hitdist, which has
+    no w anywhere, is still widened with zeros.) A signal in the occlusion mode may give radiance_hitdist=(None, hit_dist)."""
+    in_place = bool(in_place)
     d = api.HipFrontEndDesc()
     keep = []  # widened copies must outlive the launch call
-    nr, d.normalRoughness = _rgba_arg(normal_roughness, "normal_roughness")
+    nr, d.normalRoughness = _rgba_arg(normal_roughness, "normal_roughness", in_place, needs_w=True)
     keep.append(nr)
     h, w = viewz.shape
     d.viewZ = _fp32_plane(viewz, 1, "viewz")
@@ -241,18 +325,19 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
     if material_id is not None:
         d.materialID = _fp32_plane(material_id, 1, "material_id")
     if motion is not None:
+        assert motion.shape[2] != 3 or in_place, "motion [H, W, 3] is read in place only (in_place=True)"
         d.motion = _fp32_plane(motion, motion.shape[2], "motion")
         d.outMv = output(R.IN_MV, (h, w, 4), "float16", F.RGBA16_SFLOAT)
     for name, t in (("albedo", albedo), ("rf0", rf0)):
         if t is not None:
-            t, plane = _rgba_arg(t, name)
+            t, plane = _rgba_arg(t, name, in_place)
             keep.append(t)
             setattr(d, name, plane)
     if distance_to_occluder is not None:
         d.distanceToOccluder = _fp32_plane(distance_to_occluder, 1, "distance_to_occluder")
         d.outPenumbra = output(R.IN_PENUMBRA, (h, w), "float16", F.R16_SFLOAT)
         if translucency is not None:
-            t, d.translucency = _rgba_arg(translucency, "translucency")
+            t, d.translucency = _rgba_arg(translucency, "translucency", in_place)
             keep.append(t)
             d.outTranslucency = output(R.IN_TRANSLUCENCY, (h, w, 4), "uint8", F.RGBA8_UNORM)
     for which, sig, dst in (("diffuse", diffuse, d.diffuse), ("specular", specular, d.specular)):
@@ -260,10 +345,11 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
             continue
         mode = SignalMode(sig["mode"])
         dst.mode = int(mode)
-        t, dst.radianceHitDist = _signal_arg(sig["radiance_hitdist"], which + " radiance_hitdist")
-        keep.append(t)
+        if not (_stays(sig["radiance_hitdist"], in_place, True) and sig["radiance_hitdist"][0] is None):
+            t, dst.radianceHitDist = _signal_arg(sig["radiance_hitdist"], which + " radiance_hitdist", in_place, needs_w=True)
+            keep.append(t)
         if sig.get("direction") is not None:
-            t, dst.direction = _signal_arg(sig["direction"], which + " direction")
+            t, dst.direction = _signal_arg(sig["direction"], which + " direction", in_place)
             keep.append(t)
         slot0, slot1 = signal_slots(which, mode, "IN")
         dtype, ch, fmt = _SIGNAL_OUT[mode]
@@ -286,13 +372,18 @@ def _packed_plane(t, what):
 
 def resolve_outputs(rejitter=False, **kw):
     """see describe_resolve; launches on `stream` (as pack_inputs) and returns the fp32 planes. rejitter=True (both signals in an SH mode, resolve SH or SG; needs rf0): the
-    resolved colours are multiplied by NRD_SG_ReJitter before the remodulation (NRDHip.h nrdHipResolveOutputsEx); "rejitter_scale" in `want` adds the two factors, fp32 [H, W, 2]."""
+    resolved colours are multiplied by NRD_SG_ReJitter before the remodulation (NRDHip.h nrdHipResolveOutputsEx); "rejitter_scale" in `want` adds the two factors, fp32 [H, W, 2].
+    channels=3 (describe_resolve) goes through nrdHipResolveOutputsSplit."""
     like = next(t for t in (kw.get("shadow"), kw.get("viewz"), kw.get("normal_roughness"), (kw.get("diffuse") or {}).get("in0"), (kw.get("specular") or {}).get("in0")) if t is not None)
     with _stream_scope(like, kw.get("stream")):
         want = tuple(kw.get("want", ()))
         res, d, keep = describe_resolve(**dict(kw, want=tuple(n for n in want if n != "rejitter_scale")))
         lib = kw.get("lib") or api.load_library()
-        if not rejitter and "rejitter_scale" not in want:
+        if int(kw.get("channels", 4)) == 3:
+            options = resolve_options(res, like, rejitter=rejitter, want_scale="rejitter_scale" in want, out=kw.get("out"))
+            split = resolve_split(res)
+            _check(lib, lib.nrdHipResolveOutputsSplit(C.byref(d), C.byref(options), C.byref(split), _stream(like, kw.get("stream"))), "nrdHipResolveOutputsSplit")
+        elif not rejitter and "rejitter_scale" not in want:
             _check(lib, lib.nrdHipResolveOutputs(C.byref(d), _stream(like, kw.get("stream"))), "nrdHipResolveOutputs")
         else:
             options = resolve_options(res, like, rejitter=rejitter, want_scale="rejitter_scale" in want, out=kw.get("out"))
@@ -312,12 +403,27 @@ def resolve_options(res, like, rejitter=True, want_scale=False, out=None):
     return options
 
 
+def resolve_split(res):
+    """api.HipBackEndSplit for nrdHipResolveOutputsSplit, next to the descriptor of describe_resolve(channels=3): `res` is the dict it returned, whose "diffuse_hit_dist" /
+    "specular_hit_dist" planes (there when asked for in `want`) take the hit distances"""
+    split = api.HipBackEndSplit()
+    for which in ("diffuse", "specular"):
+        if which + "_hit_dist" in res:
+            setattr(split, which + "HitDist", _fp32_plane(res[which + "_hit_dist"], 1, which + "_hit_dist"))
+    return split
+
+
 def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=None, viewz=None, albedo=None, rf0=None, common_settings=None, hit_dist_params=HIT_DIST_PARAMS,
-                     denormalize_hit_dist=False, remodulate=False, want=(), out=None, stream=None, lib=None):
+                     denormalize_hit_dist=False, remodulate=False, want=(), out=None, stream=None, lib=None, channels=4):
     """The descriptor of one nrdHipResolveOutputs launch, without launching: (fp32 planes, api.HipBackEndDesc, arrays it points into besides its arguments). diffuse / specular: dict(mode=SignalMode, resolve=ResolveMode, in0=OUT_*_RADIANCE_HITDIST / _SH0 / _HITDIST / DIRECTION_HITDIST array,
     in1=OUT_*_SH1 array) -- the arrays bound as outputs (fp16 / int16) or fp32 [H, W, 4]; shadow: the OUT_SHADOW_TRANSLUCENCY array (uint8 [H, W] or [H, W, 4]);
     normal_roughness / viewz: the packed IN_NORMAL_ROUGHNESS / IN_VIEWZ arrays; want: any of "composed", "view_vector", "factors". Returns fp32 arrays under
-    "diffuse", "specular", "shadow", "composed", "view_vector", "diff_factor", "spec_factor"."""
+    "diffuse", "specular", "shadow", "composed", "view_vector", "diff_factor", "spec_factor".
+    channels=3 (default 4): "diffuse", "specular", "composed", "view_vector", "diff_factor" and "spec_factor" are [H, W, 3] (RGB32_SFLOAT planes), the hit distances go to
+    "diffuse_hit_dist" / "specular_hit_dist" [H, W] where `want` asks for them and nowhere otherwise, and albedo / rf0 given as [H, W, 3] are read where they lie; the
+    descriptor is then for nrdHipResolveOutputsSplit alone, with resolve_split(res)."""
+    assert channels in (3, 4), "channels: 3 or 4"
+    colour, colour_format = (3, F.RGB32_SFLOAT) if channels == 3 else (4, F.RGBA32_SFLOAT)
     d = api.HipBackEndDesc()
     like = next(t for t in (shadow, viewz, normal_roughness, (diffuse or {}).get("in0"), (specular or {}).get("in0")) if t is not None)
     h, w = like.shape[:2]
@@ -337,7 +443,7 @@ def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=
         d.viewZ = _fp32_plane(viewz, 1, "viewz")
     for name, t in (("albedo", albedo), ("rf0", rf0)):
         if t is not None:
-            t, plane = _rgba_arg(t, name)
+            t, plane = _rgba_arg(t, name, channels == 3)
             keep.append(t)
             setattr(d, name, plane)
     for which, sig, dst in (("diffuse", diffuse, d.diffuse), ("specular", specular, d.specular)):
@@ -348,15 +454,18 @@ def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=
         dst.in0 = _packed_plane(sig["in0"], which + " in0")
         if sig.get("in1") is not None:
             dst.in1 = _packed_plane(sig["in1"], which + " in1")
-        dst.out = output(which, (h, w), F.R32_SFLOAT) if mode == SignalMode.REBLUR_OCCLUSION else output(which, (h, w, 4), F.RGBA32_SFLOAT)
+        dst.out = output(which, (h, w), F.R32_SFLOAT) if mode == SignalMode.REBLUR_OCCLUSION else output(which, (h, w, colour), colour_format)
+        if channels == 3 and which + "_hit_dist" in want:
+            assert mode != SignalMode.REBLUR_OCCLUSION, "the occlusion mode's output is the hit distance already"
+            output(which + "_hit_dist", (h, w), F.R32_SFLOAT)
     if shadow is not None:
         d.shadow = _packed_plane(shadow, "shadow")
         d.outShadow = output("shadow", tuple(shadow.shape), F.R32_SFLOAT if shadow.ndim == 2 else F.RGBA32_SFLOAT)
     if "composed" in want:
-        d.outComposed = output("composed", (h, w, 4), F.RGBA32_SFLOAT)
+        d.outComposed = output("composed", (h, w, colour), colour_format)
     if "view_vector" in want:
-        d.outViewVector = output("view_vector", (h, w, 4), F.RGBA32_SFLOAT)
+        d.outViewVector = output("view_vector", (h, w, colour), colour_format)
     if "factors" in want:
-        d.outDiffFactor = output("diff_factor", (h, w, 4), F.RGBA32_SFLOAT)
-        d.outSpecFactor = output("spec_factor", (h, w, 4), F.RGBA32_SFLOAT)
+        d.outDiffFactor = output("diff_factor", (h, w, colour), colour_format)
+        d.outSpecFactor = output("spec_factor", (h, w, colour), colour_format)
     return res, d, keep + [common_settings]

@@ -9,7 +9,10 @@ python tools/build_variant.py rejitter_plain -DNRD_REJITTER_TILE=0), and nrdHipP
 layers each. Alternated in one process: (a) nrdHipPackInputsSamples, (b) the best composition there was before it -- torch reductions to the same two single-sample planes (mean for the
 radiance and the diffuse hit distance, masked amin for the specular one) followed by nrdHipPackInputs -- and (c) the plain single-sample pack, for scale; with the algorithmic bytes of (a),
 its GB/s and its fraction of the copy rate of the same run, and the static facts of the kernel (samples_isa()). The run fails if (a) is slower than (b).
-usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]]"""
+--split is a run of its own that adds the `split` and `isa_split` objects to the output file: the plane set of `pack` held as a tensor host holds it (normal [H, W, 3], roughness [H, W],
+two radiance [H, W, 3] and two hit_dist [H, W]); alternated in one process: widen_ms (the frontend.rgba() copies the four-channel path needs), pack_ms (nrdHipPackInputs on the widened
+planes), pack_split_ms (nrdHipPackInputsSplit in place), and the same three for resolve ([H, W, 3] outputs against [H, W, 4] outputs + [..., :3].contiguous()); split_isa(): the twins' static facts.
+usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]] [--split]"""
 import argparse
 import ctypes as C
 import json
@@ -119,6 +122,50 @@ def samples_isa():
     return out
 
 
+SPLIT_KERNELS = {"PackInputsSplitKernel": "pack_split", "PackCheckerboardSplitKernel": "pack_checkerboard_split", "ResolveOutputsSplitKernel": "resolve_split", "ReJitterSplitKernel": "rejitter_split"}
+
+
+def split_isa():
+    """static facts about the split twins behind nrdHipPackInputsSplit / nrdHipResolveOutputsSplit (the `isa_split` object of profiles/frontend_bench.json), as isa(): VGPRs, waves per
+    SIMD, scratch, LDS and the 12- and 16-byte accesses of "pack_split", "pack_checkerboard_split", "pack_samples_split", "pack_samples_checkerboard_split", "resolve_split" and
+    "rejitter_split"; sibling_*: the same facts of the kernel each is a twin of; the samples twins also hold the loads inside their sample loops"""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_frontend.s")
+        flags = [f for f in B._flags(SRC) if f not in ("-x", "hip")]
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+        txt = open(listing).read()
+
+    def facts(s):
+        c = s["counter"]
+        return {"vgprs": s["vgpr"], "waves_per_simd": s["occ"], "scratch_bytes": s["scratch"], "lds_bytes": s["ldsb"], "valu": s["valu"], "salu": s["salu"], "vmem": s["vmem"],
+                "global_load_dwordx3": c.get("global_load_dwordx3", 0), "global_load_dwordx4": c.get("global_load_dwordx4", 0), "global_load_dword": c.get("global_load_dword", 0),
+                "global_store_dwordx3": c.get("global_store_dwordx3", 0), "global_store_dwordx4": c.get("global_store_dwordx4", 0)}
+
+    def name_of(mangled):
+        if "PackSamplesSplitKernel" in mangled or "PackSamplesKernel" in mangled:
+            return "pack_samples" + ("_checkerboard" if "ILb1E" in mangled else "") + ("_split" if "Split" in mangled else "")
+        for kernel, name in SPLIT_KERNELS.items():
+            if kernel in mangled:
+                return name
+            if kernel.replace("Split", "") in mangled:
+                return name[:-len("_split")]
+        return None
+
+    named = {name_of(m): (m, s) for m, s in stats.items() if name_of(m)}
+    out = {}
+    for name, (mangled, s) in named.items():
+        if not name.endswith("_split"):
+            continue
+        out[name] = facts(s)
+        sibling = facts(named[name[:-len("_split")]][1])
+        out[name].update({"sibling_vgprs": sibling["vgprs"], "sibling_waves_per_simd": sibling["waves_per_simd"]})
+        if "samples" in name:
+            out[name]["sample_loop_loads"] = _loop_loads(txt[txt.index("\n" + mangled + ":"):].split(".Lfunc_end")[0])
+    assert len(out) == 6, list(stats)
+    return out
+
+
 def samples_main(args):
     """--samples: see the module text"""
     result = {"isa_samples": samples_isa()}
@@ -209,6 +256,120 @@ def samples_main(args):
     assert not slower, "nrdHipPackInputsSamples is slower than torch reductions + nrdHipPackInputs at N = %s: the kernel is not finished" % slower
 
 
+def split_main(args):
+    """--split: see the module text"""
+    result = {"isa_split": split_isa()}
+    if args.isa_only:
+        print(json.dumps(result))
+        return
+    import torch
+
+    from raytracingdenoiser_amd import api, frontend
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    w, h = args.width, args.height
+    px = w * h
+    g = torch.Generator(device="cuda").manual_seed(7)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    normal = rand(h, w, 3) * 2.0 - 1.0
+    normal = (normal / normal.norm(dim=-1, keepdim=True).clamp_min(1e-6)).contiguous()
+    scale = torch.tensor([4.0, 3.0, 5.0], device="cuda")
+    # held the way synth.render_frame(want=("raw",)) holds it
+    raw = {"normal": normal, "roughness": rand(h, w), "material": torch.floor(rand(h, w) * 4.0), "viewz": 0.5 + rand(h, w) * 100.0, "motion": rand(h, w, 4) - 0.5,
+           "diff_radiance": rand(h, w, 3) * scale, "diff_hit_dist": rand(h, w) * 30.0, "spec_radiance": rand(h, w, 3) * scale, "spec_hit_dist": rand(h, w) * 30.0}
+    mode = frontend.SignalMode.REBLUR_RADIANCE
+    lib = api.load_library()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def widen():  # the copies the four-channel path needs for these planes: three allocations, six strided copies
+        return frontend.rgba(raw["normal"], raw["roughness"]), frontend.rgba(raw["diff_radiance"], raw["diff_hit_dist"]), frontend.rgba(raw["spec_radiance"], raw["spec_hit_dist"])
+
+    nr4, diff4, spec4 = widen()
+    gbuffer = dict(material_id=raw["material"], motion=raw["motion"])
+    packed, desc4, keep4 = frontend.describe_pack(nr4, raw["viewz"], diffuse=dict(mode=mode, radiance_hitdist=diff4), specular=dict(mode=mode, radiance_hitdist=spec4), **gbuffer)
+    pairs = dict(diffuse=dict(mode=mode, radiance_hitdist=(raw["diff_radiance"], raw["diff_hit_dist"])), specular=dict(mode=mode, radiance_hitdist=(raw["spec_radiance"], raw["spec_hit_dist"])))
+    packed3, desc3, keep3 = frontend.describe_pack((raw["normal"], raw["roughness"]), raw["viewz"], in_place=True, **pairs, **gbuffer)
+    split = frontend.pack_split((raw["normal"], raw["roughness"]), **pairs)
+
+    def pack():
+        assert lib.nrdHipPackInputs(C.byref(desc4), stream) == 0
+
+    def pack_split():
+        assert lib.nrdHipPackInputsSplit(C.byref(desc3), None, None, C.byref(split), stream) == 0
+
+    pack(), pack_split()
+    torch.cuda.synchronize()
+    for rt in packed:  # the same bytes, or the times below compare nothing
+        assert torch.equal(packed[rt][0].view(torch.uint8), packed3[rt][0].view(torch.uint8)), rt
+    R = api.ResourceType
+    resolve_args = dict(diffuse=dict(mode=mode, in0=packed[R.IN_DIFF_RADIANCE_HITDIST][0]), specular=dict(mode=mode, in0=packed[R.IN_SPEC_RADIANCE_HITDIST][0]),
+                        normal_roughness=packed[R.IN_NORMAL_ROUGHNESS][0], viewz=packed[R.IN_VIEWZ][0], denormalize_hit_dist=True)
+    resolved4, rdesc4, rkeep4 = frontend.describe_resolve(**resolve_args)
+    resolved3, rdesc3, rkeep3 = frontend.describe_resolve(channels=3, **resolve_args)
+    rsplit = frontend.resolve_split(resolved3)
+
+    def resolve():
+        assert lib.nrdHipResolveOutputs(C.byref(rdesc4), stream) == 0
+
+    def narrow():  # what a caller of the four-channel call does to hold [H, W, 3]
+        return resolved4["diffuse"][..., :3].contiguous(), resolved4["specular"][..., :3].contiguous()
+
+    def resolve_split():
+        assert lib.nrdHipResolveOutputsSplit(C.byref(rdesc3), None, C.byref(rsplit), stream) == 0
+
+    resolve(), resolve_split()
+    torch.cuda.synchronize()
+    for name in ("diffuse", "specular"):
+        assert torch.equal(resolved4[name][..., :3].contiguous().view(torch.uint8), resolved3[name].view(torch.uint8)), name
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(args.reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / args.reps
+
+    calls = {"widen_ms": widen, "pack_ms": pack, "pack_split_ms": pack_split, "narrow_ms": narrow, "resolve_ms": resolve, "resolve_split_ms": resolve_split}
+    rounds = [{k: timed(fn) for k, fn in calls.items()} for _ in range(2)]  # alternated twice: the spread between the rounds says how much a difference means
+    best = {k: min(r[k] for r in rounds) for k in rounds[0]}
+    spread = {k: abs(rounds[0][k] - rounds[1][k]) for k in rounds[0]}
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
+    pack_bytes, resolve4_bytes = sum(PACK_READ.values()) + sum(PACK_WRITE.values()), sum(RESOLVE_READ.values()) + sum(RESOLVE_WRITE.values())
+    resolve3_bytes = sum(RESOLVE_READ.values()) + 24
+    rate = lambda bytes_per_px, ms: bytes_per_px * px / (ms * 1e-3) / 1e9
+    baseline, margin = best["widen_ms"] + best["pack_ms"], spread["widen_ms"] + spread["pack_ms"] + spread["pack_split_ms"]
+    ratio, ratio_spread = best["pack_split_ms"] / best["pack_ms"], (spread["pack_split_ms"] + spread["pack_ms"]) / best["pack_ms"]
+    result["split"] = dict(
+        best, rounds=rounds, spread_between_rounds_ms=spread, device=torch.cuda.get_device_name(0), width=w, height=h, reps=args.reps, warmup=args.warmup,
+        planes="the plane set of `pack`, held as synth's raw holds it: normal [H, W, 3] + roughness [H, W], two radiance [H, W, 3] + hit_dist [H, W], viewz, material, motion [H, W, 4]",
+        widen_is="frontend.rgba() for normal + roughness and the two radiance + hit distance pairs: three allocations, six strided copies -- what the four-channel path costs such a caller",
+        narrow_is="[..., :3].contiguous() of the two [H, W, 4] outputs", widen_plus_pack_ms=baseline, pack_split_over_widen_plus_pack=best["pack_split_ms"] / baseline,
+        pack_split_over_pack=ratio, pack_split_over_pack_spread=ratio_spread, in_place_is_no_slower=bool(best["pack_split_ms"] <= baseline + margin),
+        narrow_plus_resolve_ms=best["narrow_ms"] + best["resolve_ms"], resolve_split_over_narrow_plus_resolve=best["resolve_split_ms"] / (best["narrow_ms"] + best["resolve_ms"]),
+        resolve_split_over_resolve=best["resolve_split_ms"] / best["resolve_ms"], pack_bytes_per_pixel=pack_bytes, resolve_bytes_per_pixel=resolve4_bytes,
+        resolve_split_bytes_per_pixel=resolve3_bytes, copy_gigabytes_per_second=gbps.value, pack_split_fraction_of_copy_rate=rate(pack_bytes, best["pack_split_ms"]) / gbps.value,
+        resolve_split_fraction_of_copy_rate=rate(resolve3_bytes, best["resolve_split_ms"]) / gbps.value,
+        times_are="device events around --reps back-to-back calls, per call, the best of two alternated rounds",
+        fraction_is_not="a share of HBM bandwidth: the working set partly fits the memory-side cache, as for pack and resolve (DESIGN.md section 3.4)")
+    record = {}
+    if os.path.exists(args.out):  # the other fields of the record are another run's: kept as they are
+        with open(args.out) as fp:
+            record = json.load(fp)
+    record.update(result)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fp:
+        json.dump(record, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps({k: v for k, v in result["split"].items() if k != "rounds"}))
+
+
 def synth_pack(raw, synth, torch):
     """the packing of synth.render_frame for REBLUR_DIFFUSE_SPECULAR on the raw values: its packers, elementwise torch operations with fp32 intermediates"""
     out = {"normal_roughness": synth.pack_normal_roughness(raw["normal"], raw["roughness"], raw["material"]).contiguous(), "viewz": raw["viewz"].clone(),
@@ -285,7 +446,11 @@ def main():
     ap.add_argument("--ab-library", help="with --rejitter: a build of the other re-jitter form (-DNRD_REJITTER_TILE=0), timed on the same planes in the same rounds")
     ap.add_argument("--samples", type=int, nargs="*", help="a run of its own: nrdHipPackInputsSamples with N sample layers per signal (default 4) against torch reductions + nrdHipPackInputs")
     ap.add_argument("--samples-out", default=os.path.join(ROOT, "profiles", "frontend_samples_bench.json"))
+    ap.add_argument("--split", action="store_true", help="a run of its own: nrdHipPackInputsSplit / nrdHipResolveOutputsSplit on three-channel planes in place against widening + the "
+                    "four-channel calls; adds the `split` and `isa_split` objects to --out and leaves its other fields as they are")
     args = ap.parse_args()
+    if args.split:
+        return split_main(args)
     if args.samples is not None:
         args.samples = args.samples or [4]
         return samples_main(args)
