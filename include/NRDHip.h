@@ -139,6 +139,45 @@ uint32_t nrdHipMeasureMotionRows(NrdHipExecutor* executor, const void* dispatchD
 uint32_t nrdHipSetHistoryReachWord(NrdHipExecutor* executor, void* deviceWord);
 uint32_t nrdHipMeasureMotionRowsAsync(NrdHipExecutor* executor, const void* dispatchDescs, uint32_t dispatchDescsNum, uint32_t rowBegin, uint32_t rowEnd, void* deviceMaxRows);
 
+// The input side of the contract, audited on the device: are the bound IN_* planes inside NRD's input rules (reference README "NOISY & NON-NOISY DATA REQUIREMENTS", "NOISY
+// INPUTS") for the frame the given dispatch list describes (the list of THIS frame, before it is executed)? The denoisers promise nothing outside these rules and a broken one
+// poisons the history planes silently; the pack calls below sanitise, a host that binds planes it encoded itself has this call. It only reports: nothing is fixed or written but
+// the report. One streaming kernel over the rect, which tests exactly the texels the passes read, loads nothing outside the rect and touches only planes that can hold a non-finite value (UNORM / SNORM planes -- normals,
+// confidences, IN_*_HITDIST, IN_DIFF_DIRECTION_HITDIST, translucency, base colour -- are never touched).
+//   rule                    violated by a pixel of the rect when
+#define NRD_HIP_INPUT_RULE_VIEWZ_NOT_FINITE 0u   // guide: IN_VIEWZ is NaN / INF
+#define NRD_HIP_INPUT_RULE_MV_NOT_FINITE 1u      // guide: .x, .y or .z of IN_MV is NaN / INF
+#define NRD_HIP_INPUT_RULE_DIFF_NOT_FINITE 2u    // noisy: any channel of IN_DIFF_RADIANCE_HITDIST, or of IN_DIFF_SH0 / IN_DIFF_SH1, is NaN / INF
+#define NRD_HIP_INPUT_RULE_SPEC_NOT_FINITE 3u    // noisy: the same for IN_SPEC_RADIANCE_HITDIST, IN_SPEC_SH0 / IN_SPEC_SH1
+#define NRD_HIP_INPUT_RULE_DIFF_HITDIST_RANGE 4u // noisy: .w of the radiance / SH0 plane is finite and < 0; for a slot read by REBLUR passes only (normalised hit distance), also > 1
+#define NRD_HIP_INPUT_RULE_SPEC_HITDIST_RANGE 5u
+#define NRD_HIP_INPUT_RULE_PENUMBRA_INVALID 6u   // noisy: IN_PENUMBRA is NaN / INF or < 0
+#define NRD_HIP_INPUT_RULE_SIGNAL_NOT_FINITE 7u  // any channel of REFERENCE's IN_SIGNAL is NaN / INF
+#define NRD_HIP_INPUT_RULES_NUM 8u
+// Which rules: *rulesChecked (host side, written by both calls) has bit r set for every rule that applies -- a dispatch of the list names the rule's IN_* slot among its
+// resources and the slot holds a float format in this build. A list to which no rule applies (the REBLUR occlusion family without its guides, an empty list) is SUCCESS with mask
+// 0, pixels = inRangePixels = 0 and nothing but the clearing of the report enqueued. The > 1 bound of rules 4 / 5 applies when every dispatch naming the slot is a REBLUR pass.
+// Which texels: rect, rectOrigin, denoisingRange, viewZScale, frameIndex and the checkerboard cells are those of the list's constants. Guides are read at rectOrigin + (x, y) for
+// every pixel (x, y) of the rect, noisy planes at (x, y); a checkerboarded signal only where ( ( x ^ y ) ^ frameIndex ) & 1 equals the signal's cell, at column x >> 1. The noisy
+// rules 2 .. 6 are tested only where the pixel is in range by the passes' own predicate, !( abs( viewZ * viewZScale ) > denoisingRange ) (RELAX: abs( viewZ )), and viewZ is
+// finite: garbage beyond the range and outside the rect is allowed and not reported; a pixel whose viewZ is not finite counts under rule 0 only. Guides are tested on the sky too.
+// IN_SIGNAL has no range test. -0.0 is not negative; a NaN or INF hit distance counts under the NOT_FINITE rule only.
+typedef struct NrdHipInputReport {
+    uint32_t pixels;                         // pixels of the rect
+    uint32_t inRangePixels;                  // of which the passes denoise (not sky by the predicate above; all of them for a list that does not read IN_VIEWZ)
+    uint32_t count[NRD_HIP_INPUT_RULES_NUM]; // pixels violating the rule (a pixel counts once per rule, however many channels or planes are bad)
+    uint32_t first[NRD_HIP_INPUT_RULES_NUM]; // smallest y * rectWidth + x (rect coordinates) among them; 0xFFFFFFFF when count is 0
+} NrdHipInputReport;
+// INVALID_ARGUMENT + nrdHipGetLastError, with nothing enqueued and the report untouched: a NULL pointer (Async: or one that is not 4-byte aligned), a slot a checked rule needs
+// that is not bound (IN_VIEWZ for every noisy rule), a rect that leaves a bound plane. UNSUPPORTED, likewise with nothing enqueued: a list that reads a signal both as
+// *_RADIANCE_HITDIST and as *_SH0 / *_SH1 (two denoisers of one instance: check them one at a time), or *_SH1 without *_SH0. A list of several pass families (REBLUR + RELAX +
+// SIGMA denoisers in one instance) is audited with the constants of the FIRST family block in it: its viewZScale and its form of the sky predicate hold for every pixel and plane. Both calls cover the whole rect whatever nrdHipSetOwnedRows says. The sync form keeps its device buffer in the executor (made on first
+// use), synchronises the stream and copies the report back. The Async form zeroes and fills sizeof( NrdHipInputReport ) bytes of the CALLER'S device memory (4-byte aligned) in
+// stream order: no allocation, no synchronisation, capturable into a graph. Counts are integers: the report does not depend on the order in which the waves arrive.
+uint32_t nrdHipCheckInputs(NrdHipExecutor* executor, const void* dispatchDescs, uint32_t dispatchDescsNum, NrdHipInputReport* report, uint32_t* rulesChecked);
+uint32_t nrdHipCheckInputsAsync(NrdHipExecutor* executor, const void* dispatchDescs, uint32_t dispatchDescsNum, void* deviceReport, uint32_t* rulesChecked);
+const char* nrdHipGetInputRuleString(uint32_t rule); // "VIEWZ_NOT_FINITE", ...; NULL beyond the table
+
 // Per-pass GPU timing. When enabled, every dispatch is bracketed by hipEvents on the executor's stream.
 // nrdHipCollectPassTimings synchronises the stream, folds all brackets recorded since the last collect into per-pipeline
 // totals and returns the number of pipelines written: pipelineIndices[i] (index into InstanceDesc::pipelines),
@@ -390,6 +429,7 @@ uint32_t nrdHipResolveOutputsSplit(const NrdHipBackEndDesc* desc, const NrdHipBa
 
 #ifdef __cplusplus
 static_assert(sizeof(NrdHipFrontEndSplit) == 88 && sizeof(NrdHipBackEndSplit) == 48, "mirrored by raytracingdenoiser_amd/api.py");
+static_assert(sizeof(NrdHipInputReport) == 72, "mirrored by raytracingdenoiser_amd/api.py");
 #endif
 
 #ifdef __cplusplus

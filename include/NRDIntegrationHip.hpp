@@ -15,6 +15,7 @@
 #include <array>
 #include <stdint.h>
 #include <stdio.h>
+#include <vector>
 
 #define NRD_INTEGRATION_HIP_MAJOR 1
 #define NRD_INTEGRATION_HIP_MINOR 0
@@ -74,15 +75,18 @@ public:
     inline void NewFrame() {
         NRD_INTEGRATION_ASSERT(m_Instance != nullptr, "Uninitialized! Did you forget to call 'Initialize'?");
         m_FrameIndex++;
+        m_CheckedDispatches = nullptr; // a list "CheckInputs" fetched for a frame that was never denoised is stale
     }
 
     // Explicitly call the eponymous NRD API functions
     inline bool SetCommonSettings(const CommonSettings& commonSettings) {
         NRD_INTEGRATION_ASSERT(m_Instance != nullptr, "Uninitialized! Did you forget to call 'Initialize'?");
+        m_CheckedDispatches = nullptr; // new settings: a list fetched before them no longer describes the frame
         return nrd::SetCommonSettings(*m_Instance, commonSettings) == Result::SUCCESS;
     }
     inline bool SetDenoiserSettings(Identifier denoiser, const void* denoiserSettings) {
         NRD_INTEGRATION_ASSERT(m_Instance != nullptr, "Uninitialized! Did you forget to call 'Initialize'?");
+        m_CheckedDispatches = nullptr;
         return nrd::SetDenoiserSettings(*m_Instance, denoiser, denoiserSettings) == Result::SUCCESS;
     }
 
@@ -95,7 +99,47 @@ public:
             if (userPool[slot].data && nrdHipBindResource(m_Executor, (uint32_t)slot, &userPool[slot]) != (uint32_t)Result::SUCCESS)
                 return false;
         }
+        if (m_CheckedDispatches && m_CheckedIdentifiers == std::vector<Identifier>(denoisers, denoisers + denoisersNum)) {
+            // CheckInputs fetched this frame's list already (GetComputeDispatches advances the instance's ping-pong state: once per frame): execute that very list
+            const DispatchDesc* descs = m_CheckedDispatches;
+            m_CheckedDispatches = nullptr;
+            return nrdHipExecuteDispatches(m_Executor, descs, m_CheckedDispatchesNum) == (uint32_t)Result::SUCCESS;
+        }
+        m_CheckedDispatches = nullptr;
         return nrdHipDenoise(m_Executor, denoisers, denoisersNum) == (uint32_t)Result::SUCCESS;
+    }
+
+    // Audits the inputs of the frame against NRD's input rules BEFORE it is denoised (NRDHip.h nrdHipCheckInputs: one launch, a stream synchronisation and a 72-byte
+    // read-back): call after SetCommonSettings / SetDenoiserSettings, with the pool "Denoise" will get. report.count[ rule ] / report.first[ rule ] say which rule of
+    // NRD_HIP_INPUT_RULE_* fails and where; *rulesChecked (optional) which rules applied. Returns false (GetLastError() says why) on an argument error only -- a violation
+    // is a report, not a failure; "IsClean" below folds it into a bool. The frame's dispatch list is fetched here, and the "Denoise" of the same denoisers that follows executes
+    // it -- unless "SetCommonSettings", "SetDenoiserSettings" or "NewFrame" came in between: they drop it, and "Denoise" fetches the list of the frame it is called for. A fetched
+    // list is meant to be executed: a frame that is checked and then dropped has still advanced the ping-pong planes (as any unexecuted GetComputeDispatches does), so restart
+    // the accumulation (AccumulationMode::RESTART) on the next one. A host that calls nrd::GetComputeDispatches on GetInstance() itself between the two calls overwrites the list.
+    inline bool CheckInputs(const Identifier* denoisers, uint32_t denoisersNum, const UserPoolHip& userPool, NrdHipInputReport& report, uint32_t* rulesChecked = nullptr) {
+        uint32_t mask = 0;
+        if (!FetchForCheck(denoisers, denoisersNum, userPool))
+            return false;
+        const bool ok = nrdHipCheckInputs(m_Executor, m_CheckedDispatches, m_CheckedDispatchesNum, &report, &mask) == (uint32_t)Result::SUCCESS;
+        if (ok && rulesChecked)
+            *rulesChecked = mask;
+        return ok;
+    }
+    // The same audit without the host round trip (nrdHipCheckInputsAsync): sizeof( NrdHipInputReport ) bytes of the caller's device memory are filled in stream order
+    inline bool CheckInputsAsync(const Identifier* denoisers, uint32_t denoisersNum, const UserPoolHip& userPool, void* deviceReport, uint32_t* rulesChecked = nullptr) {
+        uint32_t mask = 0;
+        if (!FetchForCheck(denoisers, denoisersNum, userPool))
+            return false;
+        const bool ok = nrdHipCheckInputsAsync(m_Executor, m_CheckedDispatches, m_CheckedDispatchesNum, deviceReport, &mask) == (uint32_t)Result::SUCCESS;
+        if (ok && rulesChecked)
+            *rulesChecked = mask;
+        return ok;
+    }
+    static inline bool IsClean(const NrdHipInputReport& report) {
+        uint32_t n = 0;
+        for (uint32_t r = 0; r < NRD_HIP_INPUT_RULES_NUM; r++)
+            n += report.count[r];
+        return n == 0;
     }
 
     // Front end / back end on the device (NRDHip.h nrdHipPackInputs / nrdHipResolveOutputs) on this integration's stream: pack the application's fp32 buffers
@@ -139,6 +183,25 @@ public:
 
 private:
     IntegrationHip(const IntegrationHip&) = delete;
+
+    inline bool FetchForCheck(const Identifier* denoisers, uint32_t denoisersNum, const UserPoolHip& userPool) {
+        NRD_INTEGRATION_ASSERT(m_Executor != nullptr, "Uninitialized! Did you forget to call 'Initialize'?");
+        m_CheckedDispatches = nullptr;
+        for (size_t slot = 0; slot < userPool.size(); slot++) {
+            if (userPool[slot].data && nrdHipBindResource(m_Executor, (uint32_t)slot, &userPool[slot]) != (uint32_t)Result::SUCCESS)
+                return false;
+        }
+        const DispatchDesc* descs = nullptr;
+        if (GetComputeDispatches(*m_Instance, denoisers, denoisersNum, descs, m_CheckedDispatchesNum) != Result::SUCCESS)
+            return false;
+        m_CheckedIdentifiers.assign(denoisers, denoisers + denoisersNum);
+        m_CheckedDispatches = descs;
+        return true;
+    }
+
+    const DispatchDesc* m_CheckedDispatches = nullptr; // the list "CheckInputs" fetched for the frame that "Denoise" has not executed yet
+    uint32_t m_CheckedDispatchesNum = 0;
+    std::vector<Identifier> m_CheckedIdentifiers;
 
     Instance* m_Instance = nullptr;
     NrdHipExecutor* m_Executor = nullptr;

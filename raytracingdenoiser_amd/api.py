@@ -322,6 +322,15 @@ class HipBackEndSplit(C.Structure):  # include/NRDHip.h NrdHipBackEndSplit
     _fields_ = [("diffuseHitDist", HipPlaneDesc), ("specularHitDist", HipPlaneDesc)]
 
 
+# include/NRDHip.h NRD_HIP_INPUT_RULE_*: bit r of nrdHipCheckInputs' rulesChecked, index r of NrdHipInputReport::count / first
+INPUT_RULES = ("VIEWZ_NOT_FINITE", "MV_NOT_FINITE", "DIFF_NOT_FINITE", "SPEC_NOT_FINITE", "DIFF_HITDIST_RANGE", "SPEC_HITDIST_RANGE", "PENUMBRA_INVALID", "SIGNAL_NOT_FINITE")
+
+
+class HipInputReport(C.Structure):  # include/NRDHip.h NrdHipInputReport
+    _fields_ = [("pixels", C.c_uint32), ("inRangePixels", C.c_uint32), ("count", C.c_uint32 * len(INPUT_RULES)), ("first", C.c_uint32 * len(INPUT_RULES))]
+
+
+assert C.sizeof(HipInputReport) == 72
 assert C.sizeof(HipFrontEndSplit) == 88 and C.sizeof(HipBackEndSplit) == 48
 assert C.sizeof(HipPlaneDesc) == 24 and C.sizeof(HipFrontEndSignal) == 104 and C.sizeof(HipFrontEndDesc) == 552 and C.sizeof(HipBackEndSignal) == 80 and C.sizeof(HipBackEndDesc) == 432
 assert C.sizeof(HipFrontEndOptions) == 8 and C.sizeof(HipBackEndOptions) == 32 and C.sizeof(HipSignalSamples) == 24 and C.sizeof(HipFrontEndSamples) == 56
@@ -348,7 +357,8 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipCreateExecutorWithArena", "nrdHipSetProfiling", "nrdHipCollectPassTimings", "nrdHipSetOwnedRows", "nrdHipGetDispatchReach",
                    "nrdHipExecuteDispatchRange", "nrdHipPlanHaloExchange", "nrdHipSetGraphMode", "nrdHipGetGraphStats", "nrdHipGetTileFallbackStats", "nrdHipGetNumericsMode", "nrdHipMeasureCopyBandwidth",
                    "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError",
-                   "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit"]
+                   "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit",
+                   "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString"]
 
 _libs = {}
 
@@ -423,8 +433,51 @@ def load_library(path=None):
     lib.nrdHipResolveOutputsEx.argtypes, lib.nrdHipResolveOutputsEx.restype = [P(HipBackEndDesc), P(HipBackEndOptions), C.c_void_p], C.c_uint32
     lib.nrdHipPackInputsSplit.argtypes, lib.nrdHipPackInputsSplit.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSamples), P(HipFrontEndSplit), C.c_void_p], C.c_uint32
     lib.nrdHipResolveOutputsSplit.argtypes, lib.nrdHipResolveOutputsSplit.restype = [P(HipBackEndDesc), P(HipBackEndOptions), P(HipBackEndSplit), C.c_void_p], C.c_uint32
+    lib.nrdHipCheckInputs.argtypes, lib.nrdHipCheckInputs.restype = [C.c_void_p, C.c_void_p, C.c_uint32, P(HipInputReport), P(C.c_uint32)], C.c_uint32
+    lib.nrdHipCheckInputsAsync.argtypes, lib.nrdHipCheckInputsAsync.restype = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, P(C.c_uint32)], C.c_uint32
+    lib.nrdHipGetInputRuleString.argtypes, lib.nrdHipGetInputRuleString.restype = [C.c_uint32], C.c_char_p
     _libs[path] = lib
     return lib
+
+
+class InputCheck:
+    """What nrdHipCheckInputs (include/NRDHip.h) found on the bound inputs of one frame. Truthy when no checked rule is violated.
+      pixels, in_range_pixels   pixels of the rect, and of those the ones the passes denoise
+      rules                     {name: (count, first)} for every rule that was checked; first = (x, y) in rect coordinates of the raster-first violating pixel, or None
+      violations                the entries of `rules` with count > 0"""
+
+    def __init__(self, report, rules_checked, rect_width):
+        self.pixels, self.in_range_pixels, self.rules_checked = report.pixels, report.inRangePixels, rules_checked
+        self.rules = {}
+        for r, name in enumerate(INPUT_RULES):
+            if rules_checked >> r & 1:
+                first = report.first[r]
+                self.rules[name] = (report.count[r], None if first == 0xFFFFFFFF else (first % rect_width, first // rect_width))
+        self.violations = {name: v for name, v in self.rules.items() if v[0]}
+
+    def __bool__(self):
+        return not self.violations
+
+    def __str__(self):
+        if not self.violations:
+            return "inputs inside NRD's input rules (%d of %d pixels in range; checked: %s)" % (self.in_range_pixels, self.pixels, ", ".join(self.rules) or "nothing")
+        return "inputs break NRD's input rules: " + "; ".join("%s at %d pixel%s, first at (x, y) = (%d, %d)" % (name, n, "" if n == 1 else "s", xy[0], xy[1])
+                                                              for name, (n, xy) in self.violations.items())
+
+    __repr__ = __str__
+
+
+def check_inputs(lib, executor_handle, dispatch_ptr, num, rect_width, raise_on_violation=False):
+    """nrdHipCheckInputs on a fetched, not yet executed dispatch list -> InputCheck. rect_width: CommonSettings::rectSize[0] of the frame (turns `first` into (x, y)).
+    Raises RuntimeError on an argument error (unbound slot, rect outside a plane), ValueError naming rule, count and first pixel on a violation when asked to."""
+    report, mask = HipInputReport(), C.c_uint32()
+    r = Result(lib.nrdHipCheckInputs(executor_handle, C.cast(dispatch_ptr, C.c_void_p), num, C.byref(report), C.byref(mask)))
+    if r != Result.SUCCESS:
+        raise RuntimeError("nrdHipCheckInputs failed: %s (%s)" % (r.name, lib.nrdHipGetLastError(executor_handle).decode()))
+    check = InputCheck(report, mask.value, rect_width)
+    if raise_on_violation and not check:
+        raise ValueError(str(check))
+    return check
 
 
 class Dispatch:
@@ -460,6 +513,9 @@ class Instance:
             raise RuntimeError("nrd::CreateInstance failed: %s" % r.name)
         self.handle = handle
         self.identifiers = [i for i, _ in denoisers]
+        # counts the calls that make a fetched dispatch list stale: new settings, and the next fetch (which overwrites the list's memory). HipExecutor.check_inputs holds
+        # the list it fetched for the denoise() that follows only while this stands still.
+        self.list_generation = 0
         d = self.desc
         self.pipelines = [d.pipelines[i].shaderFileName.decode() for i in range(d.pipelinesNum)]
         self.permanent_pool = [(Format(d.permanentPool[i].format), d.permanentPool[i].downsampleFactor) for i in range(d.permanentPoolSize)]
@@ -471,9 +527,11 @@ class Instance:
 
     def set_common_settings(self, cs):
         self.last_common_settings = cs  # kept for hosts that derive per-frame bounds from the camera (sharding.HaloSharder)
+        self.list_generation += 1
         return Result(self.lib.SetCommonSettings(self.handle, C.byref(cs)))
 
     def set_denoiser_settings(self, identifier, settings):
+        self.list_generation += 1
         return Result(self.lib.SetDenoiserSettings(self.handle, identifier, C.cast(C.byref(settings), C.c_void_p)))
 
     def get_compute_dispatches_raw(self, identifiers=None):
@@ -481,6 +539,7 @@ class Instance:
         arr = (C.c_uint32 * len(ids))(*ids)
         out = C.POINTER(DispatchDesc)()
         num = C.c_uint32()
+        self.list_generation += 1
         r = Result(self.lib.GetComputeDispatches(self.handle, arr, len(ids), C.byref(out), C.byref(num)))
         return r, out, num.value
 

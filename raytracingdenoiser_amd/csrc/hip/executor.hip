@@ -109,6 +109,7 @@ struct NrdHipExecutor {
     Plane roughnessWord = {};          // internal 4-B/px copy of the decoded normals' w word, written with viewPos (passes.h PassArgs::roughnessWord)
     uint32_t* historyReachWord = nullptr; // nrdHipSetHistoryReachWord: the CALLER'S device word the temporal passes report their history reach into (passes.h); null = not tracked
     uint32_t* motionBits = nullptr;    // nrdHipMeasureMotionRows: the reduction's result (float bits), own 4-byte allocation made on first use
+    uint32_t* inputReport = nullptr;   // nrdHipCheckInputs: the device copy of the NrdHipInputReport, own allocation made on first use
     std::vector<nrd::Format> permanentFormat, transientFormat;
 
     Plane user[(size_t)nrd::ResourceType::MAX_NUM] = {};
@@ -312,6 +313,8 @@ extern "C" __attribute__((visibility("default"))) void nrdHipDestroyExecutor(Nrd
         (void)hipFree(e->tileFlags.ptr);
     if (e->motionBits)
         (void)hipFree(e->motionBits);
+    if (e->inputReport)
+        (void)hipFree(e->inputReport);
     for (Plane& p : e->shifted)
         if (p.ptr)
             (void)hipFree(p.ptr);
@@ -1416,6 +1419,167 @@ static uint32_t EnqueueMotionRows(NrdHipExecutor* e, const void* dispatchDescs, 
     if (hipMemsetAsync(deviceWord, 0, sizeof(uint32_t), e->stream) != hipSuccess)
         return e->Fail(nrd::Result::FAILURE, "nrdHipMeasureMotionRows: hipMemsetAsync failed");
     LaunchMotionRows(e->stream, z, mv, p, r0, r1, deviceWord);
+    return (uint32_t)nrd::Result::SUCCESS;
+}
+
+// ---- nrdHipCheckInputs (include/NRDHip.h): the bound inputs of THIS frame's list against NRD's input rules, in one launch of kernels_check_inputs.hip -----------------------
+static const char* const kInputRuleNames[NRD_HIP_INPUT_RULES_NUM] = {"VIEWZ_NOT_FINITE", "MV_NOT_FINITE", "DIFF_NOT_FINITE", "SPEC_NOT_FINITE", "DIFF_HITDIST_RANGE", "SPEC_HITDIST_RANGE",
+    "PENUMBRA_INVALID", "SIGNAL_NOT_FINITE"};
+
+extern "C" __attribute__((visibility("default"))) const char* nrdHipGetInputRuleString(uint32_t rule) { return rule < NRD_HIP_INPUT_RULES_NUM ? kInputRuleNames[rule] : nullptr; }
+
+static bool IsFloatFormat(nrd::Format f) {
+    using F = nrd::Format;
+    return f == F::R16_SFLOAT || f == F::RG16_SFLOAT || f == F::RGBA16_SFLOAT || f == F::R32_SFLOAT || f == F::RG32_SFLOAT || f == F::RGB32_SFLOAT || f == F::RGBA32_SFLOAT;
+}
+
+// Validates everything, then (enqueue) clears deviceReport and launches the audit on the executor's stream. mask = the rules that apply, whether enqueued or not; launched = false:
+// no rule applies and only the clearing was enqueued.
+static uint32_t EnqueueCheckInputs(NrdHipExecutor* e, const void* dispatchDescs, uint32_t dispatchDescsNum, uint32_t* deviceReport, uint32_t& mask) {
+    using R = nrd::ResourceType;
+    mask = 0;
+    const nrd::DispatchDesc* descs = (const nrd::DispatchDesc*)dispatchDescs;
+    const nrd::InstanceDesc& idesc = nrd::GetInstanceDesc(*e->instance);
+    CheckInputsParams p = {};
+    p.viewZScale = 1.0f;
+    p.diffCell = p.specCell = 2u;
+    int originX = 0, originY = 0;
+    bool haveConstants = false;
+    bool named[(size_t)R::MAX_NUM] = {}, namedOutsideReblur[(size_t)R::MAX_NUM] = {};
+    for (uint32_t i = 0; i < dispatchDescsNum; i++) {
+        const nrd::DispatchDesc& d = descs[i];
+        if (d.pipelineIndex >= idesc.pipelinesNum)
+            continue;
+        const char* shader = idesc.pipelines[d.pipelineIndex].shaderFileName;
+        const bool reblur = !strncmp(shader, "REBLUR_", 7);
+        for (uint32_t r = 0; r < d.resourcesNum; r++) {
+            const uint32_t t = (uint32_t)d.resources[r].type;
+            if (t < (uint32_t)R::MAX_NUM) {
+                named[t] = true;
+                namedOutsideReblur[t] = namedOutsideReblur[t] || !reblur;
+            }
+        }
+        if (haveConstants || !d.constantBufferData)
+            continue;
+        // the frame's rect, range and checkerboard: the first constant block of a pass family (every block of a list carries the same CommonSettings)
+        auto common = [&](const auto& c) {
+            p.rectW = (int)c.gRectSize.x, p.rectH = (int)c.gRectSize.y;
+            originX = (int)c.gRectOrigin.x, originY = (int)c.gRectOrigin.y;
+            p.viewZScale = c.gViewZScale, p.denoisingRange = c.gDenoisingRange;
+            p.frameIndex = c.gFrameIndex;
+            haveConstants = true;
+        };
+        if (reblur && d.constantBufferDataSize >= sizeof(nrdc::ReblurConstants)) {
+            nrdc::ReblurConstants c;
+            memcpy(&c, d.constantBufferData, sizeof(c));
+            common(c);
+            p.diffCell = c.gDiffCheckerboard, p.specCell = c.gSpecCheckerboard;
+        } else if (!strncmp(shader, "RELAX_", 6) && d.constantBufferDataSize >= sizeof(nrdc::RelaxConstants)) {
+            nrdc::RelaxConstants c;
+            memcpy(&c, d.constantBufferData, sizeof(c));
+            common(c);
+            p.viewZScale = 1.0f; // RELAX classifies its tiles by Abs( z ) > range (kernels_common.hip DecodeGuidesClassifyKernel)
+            p.diffCell = c.gDiffCheckerboard, p.specCell = c.gSpecCheckerboard;
+        } else if (!strncmp(shader, "SIGMA_", 6) && d.constantBufferDataSize >= sizeof(nrdc::SigmaConstants)) {
+            nrdc::SigmaConstants c;
+            memcpy(&c, d.constantBufferData, sizeof(c));
+            common(c);
+        } else if (!strcmp(shader, "REFERENCE_Copy.cs") && d.constantBufferDataSize >= sizeof(nrdc::ReferenceCopyConstants)) {
+            // REFERENCE's blocks carry the rect as its inverse only: 1 / ( 1 / n ) rounds back to n for every 16-bit n. Its kernels address IN_SIGNAL at the pixel itself.
+            nrdc::ReferenceCopyConstants c;
+            memcpy(&c, d.constantBufferData, sizeof(c));
+            p.rectW = (int)std::lround(1.0f / c.gRectSizeInv.x), p.rectH = (int)std::lround(1.0f / c.gRectSizeInv.y);
+            haveConstants = true;
+        }
+    }
+    auto applies = [&](R t) { return named[(size_t)t] && IsFloatFormat(ExpectedUserFormat(t, e->translucentShadow)); };
+    const bool diffRadiance = applies(R::IN_DIFF_RADIANCE_HITDIST), diffSh = applies(R::IN_DIFF_SH0), specRadiance = applies(R::IN_SPEC_RADIANCE_HITDIST), specSh = applies(R::IN_SPEC_SH0);
+    if (haveConstants) {
+        mask |= applies(R::IN_VIEWZ) ? 1u << NRD_HIP_INPUT_RULE_VIEWZ_NOT_FINITE : 0u;
+        mask |= applies(R::IN_MV) ? 1u << NRD_HIP_INPUT_RULE_MV_NOT_FINITE : 0u;
+        mask |= (diffRadiance || diffSh || applies(R::IN_DIFF_SH1)) ? 1u << NRD_HIP_INPUT_RULE_DIFF_NOT_FINITE : 0u;
+        mask |= (specRadiance || specSh || applies(R::IN_SPEC_SH1)) ? 1u << NRD_HIP_INPUT_RULE_SPEC_NOT_FINITE : 0u;
+        mask |= (diffRadiance || diffSh) ? 1u << NRD_HIP_INPUT_RULE_DIFF_HITDIST_RANGE : 0u;
+        mask |= (specRadiance || specSh) ? 1u << NRD_HIP_INPUT_RULE_SPEC_HITDIST_RANGE : 0u;
+        mask |= applies(R::IN_PENUMBRA) ? 1u << NRD_HIP_INPUT_RULE_PENUMBRA_INVALID : 0u;
+        mask |= applies(R::IN_SIGNAL) ? 1u << NRD_HIP_INPUT_RULE_SIGNAL_NOT_FINITE : 0u;
+    }
+    if ((diffRadiance && diffSh) || (specRadiance && specSh))
+        return e->Fail(nrd::Result::UNSUPPORTED, "nrdHipCheckInputs: the list reads a signal both as RADIANCE_HITDIST and as SH0 / SH1; check the denoisers one at a time");
+
+    // the planes the kernel reads, each with the area it is addressed in: guides at rectOrigin + pixel, noisy planes at the pixel, a checkerboarded signal in the left half
+    std::string problem;
+    auto take = [&](Plane& dst, R t, bool needed, bool atOrigin, uint32_t cell) {
+        if (!needed || !problem.empty())
+            return;
+        const char* name = nrd::GetResourceTypeString(t);
+        if (!e->userBound[(size_t)t]) {
+            problem = std::string("nrdHipCheckInputs: resource not bound: ") + (name ? name : "?");
+            return;
+        }
+        dst = e->user[(size_t)t];
+        const int ox = atOrigin ? originX : 0, oy = atOrigin ? originY : 0, w = cell != 2u ? (p.rectW + 1) / 2 : p.rectW;
+        if (ox + w > dst.w || oy + p.rectH > dst.h) {
+            problem = std::string("nrdHipCheckInputs: the rect leaves the bound plane ") + (name ? name : "?");
+            return;
+        }
+        dst.ptr += (size_t)oy * dst.pitch + (size_t)ox * BytesPerTexel(ExpectedUserFormat(t, e->translucentShadow));
+    };
+    const uint32_t noisyRules = 1u << NRD_HIP_INPUT_RULE_DIFF_NOT_FINITE | 1u << NRD_HIP_INPUT_RULE_SPEC_NOT_FINITE | 1u << NRD_HIP_INPUT_RULE_DIFF_HITDIST_RANGE |
+                                1u << NRD_HIP_INPUT_RULE_SPEC_HITDIST_RANGE | 1u << NRD_HIP_INPUT_RULE_PENUMBRA_INVALID;
+    take(p.viewZ, R::IN_VIEWZ, (mask & (noisyRules | 1u << NRD_HIP_INPUT_RULE_VIEWZ_NOT_FINITE)) != 0u, true, 2u); // the range test of every noisy rule
+    take(p.mv, R::IN_MV, (mask & 1u << NRD_HIP_INPUT_RULE_MV_NOT_FINITE) != 0u, true, 2u);
+    take(p.diff0, diffSh ? R::IN_DIFF_SH0 : R::IN_DIFF_RADIANCE_HITDIST, diffRadiance || diffSh, false, p.diffCell);
+    take(p.diff1, R::IN_DIFF_SH1, applies(R::IN_DIFF_SH1), false, p.diffCell);
+    take(p.spec0, specSh ? R::IN_SPEC_SH0 : R::IN_SPEC_RADIANCE_HITDIST, specRadiance || specSh, false, p.specCell);
+    take(p.spec1, R::IN_SPEC_SH1, applies(R::IN_SPEC_SH1), false, p.specCell);
+    take(p.penumbra, R::IN_PENUMBRA, applies(R::IN_PENUMBRA), false, 2u);
+    take(p.signal, R::IN_SIGNAL, applies(R::IN_SIGNAL), false, 2u);
+    if (!problem.empty())
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, problem);
+    if ((p.diff1.ptr && !p.diff0.ptr) || (p.spec1.ptr && !p.spec0.ptr))
+        return e->Fail(nrd::Result::UNSUPPORTED, "nrdHipCheckInputs: the list reads SH1 of a signal without its SH0");
+    // the > 1 bound: a normalised hit distance, which is what a slot holds that only REBLUR passes read
+    p.diffNormalized = !namedOutsideReblur[(size_t)(diffSh ? R::IN_DIFF_SH0 : R::IN_DIFF_RADIANCE_HITDIST)];
+    p.specNormalized = !namedOutsideReblur[(size_t)(specSh ? R::IN_SPEC_SH0 : R::IN_SPEC_RADIANCE_HITDIST)];
+
+    // { pixels 0, inRangePixels 0, count[] 0, first[] 0xFFFFFFFF }
+    const size_t head = offsetof(NrdHipInputReport, first);
+    if (hipMemsetAsync(deviceReport, 0, head, e->stream) != hipSuccess || hipMemsetAsync((uint8_t*)deviceReport + head, 0xFF, sizeof(NrdHipInputReport) - head, e->stream) != hipSuccess)
+        return e->Fail(nrd::Result::FAILURE, "nrdHipCheckInputs: hipMemsetAsync failed");
+    if (mask)
+        LaunchCheckInputs(e->stream, p, deviceReport);
+    return (uint32_t)nrd::Result::SUCCESS;
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipCheckInputsAsync(NrdHipExecutor* e, const void* dispatchDescs, uint32_t dispatchDescsNum, void* deviceReport, uint32_t* rulesChecked) {
+    if (!e)
+        return (uint32_t)nrd::Result::INVALID_ARGUMENT;
+    if (!deviceReport || !rulesChecked || (!dispatchDescs && dispatchDescsNum) || ((uintptr_t)deviceReport & 3u) != 0)
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipCheckInputsAsync: a NULL or misaligned pointer");
+    uint32_t mask = 0;
+    const uint32_t r = EnqueueCheckInputs(e, dispatchDescs, dispatchDescsNum, (uint32_t*)deviceReport, mask);
+    if (r == (uint32_t)nrd::Result::SUCCESS)
+        *rulesChecked = mask;
+    return r;
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipCheckInputs(NrdHipExecutor* e, const void* dispatchDescs, uint32_t dispatchDescsNum, NrdHipInputReport* report, uint32_t* rulesChecked) {
+    if (!e)
+        return (uint32_t)nrd::Result::INVALID_ARGUMENT;
+    if (!report || !rulesChecked || (!dispatchDescs && dispatchDescsNum))
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipCheckInputs: a NULL pointer");
+    if (!e->inputReport && hipMalloc((void**)&e->inputReport, sizeof(NrdHipInputReport)) != hipSuccess)
+        return e->Fail(nrd::Result::FAILURE, "nrdHipCheckInputs: cannot allocate the device report");
+    uint32_t mask = 0;
+    const uint32_t r = EnqueueCheckInputs(e, dispatchDescs, dispatchDescsNum, e->inputReport, mask);
+    if (r != (uint32_t)nrd::Result::SUCCESS)
+        return r;
+    NrdHipInputReport host;
+    if (hipStreamSynchronize(e->stream) != hipSuccess || hipMemcpy(&host, e->inputReport, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess)
+        return e->Fail(nrd::Result::FAILURE, "nrdHipCheckInputs: cannot read the report back");
+    *report = host;
+    *rulesChecked = mask;
     return (uint32_t)nrd::Result::SUCCESS;
 }
 

@@ -62,6 +62,24 @@ struct MotionParams {
 };
 void LaunchMotionRows(hipStream_t stream, const Plane& viewZ, const Plane& mv, const MotionParams& p, int rowBegin, int rowEnd, uint32_t* outMaxBits);
 
+// nrdHipCheckInputs (include/NRDHip.h): what the audit kernel of kernels_check_inputs.hip reads. A plane with ptr == nullptr is not read and its rule not tested; the guide planes
+// (viewZ, mv) arrive offset to the rect origin, the noisy ones as bound. The executor has checked that every texel the kernel can address lies inside its plane.
+struct CheckInputsParams {
+    Plane viewZ, mv;         // R32_SFLOAT, RGBA16_SFLOAT (.xyz tested)
+    Plane diff0, diff1;      // RGBA16_SFLOAT: radiance + hit distance or SH0 (.w = hit distance), SH1
+    Plane spec0, spec1;
+    Plane penumbra;          // R16_SFLOAT
+    Plane signal;            // RGBA32_SFLOAT, no range test
+    float viewZScale;        // 1 for RELAX, whose sky predicate is Abs( z ) > range
+    float denoisingRange;
+    int rectW, rectH;
+    uint32_t frameIndex;
+    uint32_t diffCell, specCell;             // gDiffCheckerboard / gSpecCheckerboard: 2 = every pixel carries data at its own column
+    uint32_t diffNormalized, specNormalized; // != 0: a hit distance above 1 violates too (REBLUR)
+};
+// report: sizeof( NrdHipInputReport ) bytes of device memory holding { 0, 0, count 0 x 8, first 0xFFFFFFFF x 8 } when the stream gets to the kernel
+void LaunchCheckInputs(hipStream_t stream, const CheckInputsParams& p, uint32_t* report);
+
 struct LaunchRecord {
     const void* func;
     dim3 grid, block;

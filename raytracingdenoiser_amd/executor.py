@@ -47,6 +47,7 @@ class HipExecutor:
             raise RuntimeError("nrdHipCreateExecutorWithArena failed: %s" % r.name)
         self.handle = handle
         self._bound = {}  # keeps tensors alive
+        self._checked_list = None  # (identifiers, pointer, count, instance.list_generation): the list check_inputs fetched for the denoise() that follows
 
     def _check(self, code, what):
         r = api.Result(code)
@@ -86,8 +87,48 @@ class HipExecutor:
 
     def denoise(self, identifiers=None):
         ids = identifiers if identifiers is not None else self.instance.identifiers
+        checked, self._checked_list = self._checked_list, None
+        if checked is not None and checked[0] == list(ids) and checked[3] == self.instance.list_generation:
+            # check_inputs fetched this frame's list already (nrd::GetComputeDispatches advances the instance's ping-pong state: once per frame): execute that very list.
+            # Only while nothing happened to the instance since -- new settings or another fetch make the list stale (a dropped frame, settings changed after the check),
+            # and this frame's is fetched below as if there had been no check.
+            self.execute_raw(checked[1], checked[2])
+            return
         arr = (C.c_uint32 * len(ids))(*ids)
         self._check(self.lib.nrdHipDenoise(self.handle, arr, len(ids)), "nrdHipDenoise")
+
+    def check_inputs(self, identifiers=None, raise_on_violation=False, dispatches=None):
+        """Audits the bound inputs against NRD's input rules before the frame is denoised -- include/NRDHip.h nrdHipCheckInputs: one launch, a stream synchronisation and a
+        72-byte read-back. Call it after set_common_settings / set_denoiser_settings of the frame. Returns an api.InputCheck: truthy when clean, `rules` = {name: (count,
+        first (x, y) or None)} per checked rule; raise_on_violation=True raises ValueError naming rule, count and first pixel instead.
+        The frame's dispatch list is fetched here, and the denoise() that follows with the same identifiers executes that list instead of fetching it again -- unless
+        settings were set or a list was fetched on the instance in between: then the held list is stale, it is dropped and denoise() fetches its own. A fetched list
+        is meant to be executed: a frame that is checked and then dropped has still advanced the instance's ping-pong planes, as any unexecuted GetComputeDispatches
+        does, so restart the accumulation (AccumulationMode.RESTART) on the next frame. dispatches = (pointer, count) checks a list the caller fetched (and executes) itself."""
+        if not hasattr(self.instance, "last_common_settings"):
+            raise RuntimeError("check_inputs: call instance.set_common_settings(cs) for this frame first (the rect of the report comes from it)")
+        ptr, n = self._frame_list(identifiers, dispatches)
+        return api.check_inputs(self.lib, self.handle, ptr, n, int(self.instance.last_common_settings.rectSize[0]), raise_on_violation)
+
+    def _frame_list(self, identifiers, dispatches):
+        if dispatches is not None:
+            return dispatches
+        ids = list(identifiers if identifiers is not None else self.instance.identifiers)
+        r, ptr, n = self.instance.get_compute_dispatches_raw(ids)
+        if r != api.Result.SUCCESS:
+            raise RuntimeError("nrd::GetComputeDispatches failed: %s" % r.name)
+        self._checked_list = (ids, ptr, n, self.instance.list_generation)
+        return ptr, n
+
+    def check_inputs_async(self, device_report, identifiers=None, dispatches=None):
+        """the same audit enqueued on the executor's stream: device_report (18 x int32 / uint32 or 72 x uint8 on the device) receives the NrdHipInputReport in stream order, with
+        no allocation and no synchronisation (capturable into a graph) -- include/NRDHip.h nrdHipCheckInputsAsync. The list: as for check_inputs.
+        Returns the mask of the rules checked (bit r = api.INPUT_RULES[r])."""
+        assert device_report.is_cuda and device_report.is_contiguous() and device_report.numel() * device_report.element_size() >= C.sizeof(api.HipInputReport)
+        ptr, n = self._frame_list(identifiers, dispatches)
+        mask = C.c_uint32()
+        self._check(self.lib.nrdHipCheckInputsAsync(self.handle, C.cast(ptr, C.c_void_p), n, C.c_void_p(device_report.data_ptr()), C.byref(mask)), "nrdHipCheckInputsAsync")
+        return mask.value
 
     def execute_raw(self, dispatch_ptr, num):
         self._check(self.lib.nrdHipExecuteDispatches(self.handle, C.cast(dispatch_ptr, C.c_void_p), num), "nrdHipExecuteDispatches")

@@ -12,7 +12,11 @@ its GB/s and its fraction of the copy rate of the same run, and the static facts
 --split is a run of its own that adds the `split` and `isa_split` objects to the output file: the plane set of `pack` held as a tensor host holds it (normal [H, W, 3], roughness [H, W],
 two radiance [H, W, 3] and two hit_dist [H, W]); alternated in one process: widen_ms (the frontend.rgba() copies the four-channel path needs), pack_ms (nrdHipPackInputs on the widened
 planes), pack_split_ms (nrdHipPackInputsSplit in place), and the same three for resolve ([H, W, 3] outputs against [H, W, 4] outputs + [..., :3].contiguous()); split_isa(): the twins' static facts.
-usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]] [--split]"""
+--check-inputs is a run of its own that adds the `check_inputs` and `isa_check_inputs` objects to the output file: nrdHipCheckInputsAsync on the bound REBLUR_DIFFUSE_SPECULAR planes
+of raytracingdenoiser_amd/synth.py (28 B per pixel: viewZ 4, IN_MV 8, two signals 8 + 8) against (a) the copy rate of the same run and (b) what a tensor host does today for the same
+answer: torch.isfinite over the four planes, masked with the range test, .all(). The run fails if the kernel is slower than (b).
+usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]] [--split]
+       [--check-inputs]"""
 import argparse
 import ctypes as C
 import json
@@ -370,6 +374,119 @@ def split_main(args):
     print(json.dumps({k: v for k, v in result["split"].items() if k != "rounds"}))
 
 
+CHECK_SRC = os.path.join(B.CSRC, "hip", "kernels_check_inputs.hip")
+CHECK_READ = {"IN_VIEWZ R32_SFLOAT": 4, "IN_MV RGBA16_SFLOAT": 8, "IN_DIFF_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "IN_SPEC_RADIANCE_HITDIST RGBA16_SFLOAT": 8}
+
+
+def check_inputs_isa():
+    """static facts about the kernel behind nrdHipCheckInputs (the `isa_check_inputs` object of profiles/frontend_bench.json), as isa(), per instantiation ("planes_<mask>";
+    "diffuse_specular" = the one the measurement runs); atomics: the global atomics of the listing -- all of them sit behind the wave's exit"""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_check_inputs.s")
+        flags = [f for f in B._flags(CHECK_SRC) if f not in ("-x", "hip")]
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", CHECK_SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+    out = {}
+    for mangled, s in stats.items():
+        m = re.search(r"CheckInputsKernelILj(\d+)E", mangled)
+        if not m:
+            continue
+        c = s["counter"]
+        facts = {"vgprs": s["vgpr"], "waves_per_simd": s["occ"], "scratch_bytes": s["scratch"], "lds_bytes": s["ldsb"], "valu": s["valu"], "salu": s["salu"], "vmem": s["vmem"],
+                 "global_load_dword": c.get("global_load_dword", 0), "global_load_dwordx2": c.get("global_load_dwordx2", 0),
+                 "atomics": {k: v for k, v in c.items() if k.startswith("global_atomic")}}
+        out["planes_%s" % m.group(1)] = facts
+        if int(m.group(1)) == 23:  # viewZ, IN_MV, diffuse and specular radiance: the plane set of the measurement
+            out["diffuse_specular"] = facts
+    assert "diffuse_specular" in out and len(out) == 11, list(stats)
+    return out
+
+
+def check_inputs_main(args):
+    """--check-inputs: see the module text"""
+    result = {"isa_check_inputs": check_inputs_isa()}
+    if args.isa_only:
+        print(json.dumps(result))
+        return
+    import torch
+
+    from raytracingdenoiser_amd import api, scene, synth
+    from raytracingdenoiser_amd.executor import HipExecutor
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    w, h = args.width, args.height
+    px = w * h
+    name = "REBLUR_DIFFUSE_SPECULAR"
+    frames = [synth.render_frame(w, h, f, device="cuda", want=tuple(scene.DENOISERS[name][1])) for f in range(2)]
+    inst = api.Instance([(0, scene.DENOISERS[name][0])])
+    ex = HipExecutor(inst, w, h)
+    for rt, t, fmt in scene.user_planes(name, frames[1]):
+        ex.bind(rt, t.contiguous(), fmt)
+    cs = scene.common_settings(frames[1]["camera"], frames[0]["camera"], w, h, 1)
+    assert inst.set_denoiser_settings(0, scene.denoiser_settings(name, frames[1], None)) == api.Result.SUCCESS and inst.set_common_settings(cs) == api.Result.SUCCESS
+    r, ptr, n = inst.get_compute_dispatches_raw()
+    assert r == api.Result.SUCCESS
+    lib, stream = inst.lib, C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    report = torch.zeros(18, dtype=torch.int32, device="cuda")
+    mask, raw_ptr, raw_report = C.c_uint32(), C.cast(ptr, C.c_void_p), C.c_void_p(report.data_ptr())
+
+    def kernel():
+        assert lib.nrdHipCheckInputsAsync(ex.handle, raw_ptr, n, raw_report, C.byref(mask)) == 0
+
+    viewz, mv, diff, spec = (ex._bound[int(rt)] for rt in (api.ResourceType.IN_VIEWZ, api.ResourceType.IN_MV, api.ResourceType.IN_DIFF_RADIANCE_HITDIST, api.ResourceType.IN_SPEC_RADIANCE_HITDIST))
+    denoising_range, scale = float(cs.denoisingRange), float(cs.viewZScale)
+
+    def torch_host():  # the same yes / no without the rect origin, the checkerboard, the counts and the positions: four reductions, one answer left on the device
+        sky = ((viewz * scale).abs() > denoising_range).unsqueeze(-1)
+        return (torch.isfinite(viewz).all() & torch.isfinite(mv[..., :3]).all() & (torch.isfinite(diff) | sky).all() & (torch.isfinite(spec) | sky).all())
+
+    kernel()
+    torch.cuda.synchronize()
+    words = report.cpu().numpy().view("uint32")
+    assert mask.value == 0x3F and int(words[0]) == px and 0 < int(words[1]) < px and not words[2:10].any() and bool(torch_host()), words  # a clean frame, for both
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(args.reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / args.reps
+
+    rounds = [{"check_inputs_ms": timed(kernel), "torch_isfinite_ms": timed(torch_host)} for _ in range(2)]
+    best = {k: min(r[k] for r in rounds) for k in rounds[0]}
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
+    bytes_per_px = sum(CHECK_READ.values())
+    rate = bytes_per_px * px / (best["check_inputs_ms"] * 1e-3) / 1e9
+    result["check_inputs"] = dict(
+        best, rounds=rounds, device=torch.cuda.get_device_name(0), width=w, height=h, reps=args.reps, warmup=args.warmup, in_range_pixels=int(words[1]), pixels=px,
+        planes="the bound REBLUR_DIFFUSE_SPECULAR inputs of synth.render_frame, frame 1: IN_VIEWZ, IN_MV, IN_DIFF_RADIANCE_HITDIST, IN_SPEC_RADIANCE_HITDIST",
+        torch_isfinite_is="torch.isfinite over the four planes, the noisy ones masked with the range test, .all() of each, the four answers ANDed on the device; no rect origin, no "
+                          "checkerboard, no counts, no positions", read_bytes_per_pixel=CHECK_READ, bytes_per_pixel=bytes_per_px,
+        bytes_are="what the kernel loads: every texel of the four planes inside the rect, the noisy texels of sky pixels included (they are masked, not skipped)", gigabytes_per_second=rate, copy_gigabytes_per_second=gbps.value,
+        fraction_of_copy_rate=rate / gbps.value, check_inputs_over_torch_isfinite=best["check_inputs_ms"] / best["torch_isfinite_ms"],
+        times_are="device events around --reps back-to-back calls (each call: two 40- / 32-byte memsets and the kernel), per call, the best of two alternated rounds",
+        fraction_is_not="a share of HBM bandwidth: the working set partly fits the memory-side cache, as for pack and resolve (DESIGN.md section 3.4)")
+    record = {}
+    if os.path.exists(args.out):  # the other fields of the record are another run's: kept as they are
+        with open(args.out) as fp:
+            record = json.load(fp)
+    record.update(result)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fp:
+        json.dump(record, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps({k: v for k, v in result["check_inputs"].items() if k != "rounds"}))
+    print(json.dumps(result["isa_check_inputs"]["diffuse_specular"]))
+    assert best["check_inputs_ms"] <= best["torch_isfinite_ms"], "nrdHipCheckInputs is slower than the torch.isfinite chain it replaces: the kernel is not finished"
+
+
 def synth_pack(raw, synth, torch):
     """the packing of synth.render_frame for REBLUR_DIFFUSE_SPECULAR on the raw values: its packers, elementwise torch operations with fp32 intermediates"""
     out = {"normal_roughness": synth.pack_normal_roughness(raw["normal"], raw["roughness"], raw["material"]).contiguous(), "viewz": raw["viewz"].clone(),
@@ -448,7 +565,11 @@ def main():
     ap.add_argument("--samples-out", default=os.path.join(ROOT, "profiles", "frontend_samples_bench.json"))
     ap.add_argument("--split", action="store_true", help="a run of its own: nrdHipPackInputsSplit / nrdHipResolveOutputsSplit on three-channel planes in place against widening + the "
                     "four-channel calls; adds the `split` and `isa_split` objects to --out and leaves its other fields as they are")
+    ap.add_argument("--check-inputs", action="store_true", help="a run of its own: nrdHipCheckInputsAsync on the bound REBLUR_DIFFUSE_SPECULAR planes against the copy rate and a "
+                    "torch.isfinite chain; adds the `check_inputs` and `isa_check_inputs` objects to --out and leaves its other fields as they are")
     args = ap.parse_args()
+    if args.check_inputs:
+        return check_inputs_main(args)
     if args.split:
         return split_main(args)
     if args.samples is not None:
@@ -456,6 +577,7 @@ def main():
         return samples_main(args)
     result = {"isa": isa(), "isa_options": options_isa()}
     if args.isa_only:  # the static half of the record: nothing here is a time
+        result["isa_check_inputs"] = check_inputs_isa()
         print(json.dumps(result))
         return
     import torch
