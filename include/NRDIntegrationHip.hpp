@@ -160,6 +160,10 @@ public:
     inline bool ResolveOutputs(const NrdHipBackEndDesc& desc, const NrdHipBackEndOptions& options, const NrdHipBackEndSplit& split) {
         return nrdHipResolveOutputsSplit(&desc, &options, &split, m_Stream) == (uint32_t)Result::SUCCESS;
     }
+    // SIGMA for point, spot, sphere and directional lights, up to NRD_HIP_MAX_SHADOW_LIGHTS per pixel (nrdHipPackShadowLights / nrdHipResolveShadowLights): IN_PENUMBRA /
+    // IN_TRANSLUCENCY per light, or combined for one SIGMA_SHADOW_TRANSLUCENCY pass; then the shadowed radiance of all lights from the denoised OUT_SHADOW_TRANSLUCENCY
+    inline bool PackShadowLights(const NrdHipShadowLightsPackDesc& desc) { return nrdHipPackShadowLights(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
+    inline bool ResolveShadowLights(const NrdHipShadowLightsResolveDesc& desc) { return nrdHipResolveShadowLights(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
     inline const char* GetLastFrontEndError() const { return nrdHipGetLastFrontEndError(); }
 
     // Assumes that no work of this integration is in flight on the stream

@@ -322,6 +322,39 @@ class HipBackEndSplit(C.Structure):  # include/NRDHip.h NrdHipBackEndSplit
     _fields_ = [("diffuseHitDist", HipPlaneDesc), ("specularHitDist", HipPlaneDesc)]
 
 
+class LightType(enum.IntEnum):  # include/NRDHip.h NRD_HIP_LIGHT_*
+    DIRECTIONAL = 0
+    LOCAL = 1
+
+
+class ShadowsMode(enum.IntEnum):  # include/NRDHip.h NRD_HIP_SHADOWS_*
+    PER_LIGHT = 0
+    COMBINED = 1
+
+
+MAX_SHADOW_LIGHTS = 32  # include/NRDHip.h NRD_HIP_MAX_SHADOW_LIGHTS
+
+
+class HipShadowLight(C.Structure):  # include/NRDHip.h NrdHipShadowLight
+    _fields_ = [("type", C.c_uint32), ("tanOfLightAngularRadius", C.c_float), ("lightSize", C.c_float), ("reserved", C.c_uint32)]
+
+
+class HipShadowLightsPackDesc(C.Structure):  # include/NRDHip.h NrdHipShadowLightsPackDesc
+    _fields_ = [("mode", C.c_uint32), ("lightsNum", C.c_uint32), ("lights", C.POINTER(HipShadowLight)),
+                ("distanceToOccluder", HipPlaneDesc), ("distanceToLight", HipPlaneDesc), ("translucency", HipPlaneDesc), ("lighting", HipPlaneDesc), ("weight", HipPlaneDesc),
+                ("distanceToOccluderLayerBytes", C.c_uint64), ("distanceToLightLayerBytes", C.c_uint64), ("translucencyLayerBytes", C.c_uint64), ("lightingLayerBytes", C.c_uint64),
+                ("weightLayerBytes", C.c_uint64), ("outPenumbra", HipPlaneDesc), ("outTranslucency", HipPlaneDesc), ("outLightingSum", HipPlaneDesc),
+                ("outPenumbraLayerBytes", C.c_uint64), ("outTranslucencyLayerBytes", C.c_uint64)]
+
+
+class HipShadowLightsResolveDesc(C.Structure):  # include/NRDHip.h NrdHipShadowLightsResolveDesc
+    _fields_ = [("mode", C.c_uint32), ("lightsNum", C.c_uint32), ("shadow", HipPlaneDesc), ("lighting", HipPlaneDesc), ("shadowLayerBytes", C.c_uint64), ("lightingLayerBytes", C.c_uint64),
+                ("out", HipPlaneDesc)]
+
+
+assert C.sizeof(HipShadowLight) == 16 and C.sizeof(HipShadowLightsPackDesc) == 264 and C.sizeof(HipShadowLightsResolveDesc) == 96
+
+
 # include/NRDHip.h NRD_HIP_INPUT_RULE_*: bit r of nrdHipCheckInputs' rulesChecked, index r of NrdHipInputReport::count / first
 INPUT_RULES = ("VIEWZ_NOT_FINITE", "MV_NOT_FINITE", "DIFF_NOT_FINITE", "SPEC_NOT_FINITE", "DIFF_HITDIST_RANGE", "SPEC_HITDIST_RANGE", "PENUMBRA_INVALID", "SIGNAL_NOT_FINITE")
 
@@ -358,7 +391,7 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipExecuteDispatchRange", "nrdHipPlanHaloExchange", "nrdHipSetGraphMode", "nrdHipGetGraphStats", "nrdHipGetTileFallbackStats", "nrdHipGetNumericsMode", "nrdHipMeasureCopyBandwidth",
                    "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError",
                    "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit",
-                   "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString"]
+                   "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString", "nrdHipPackShadowLights", "nrdHipResolveShadowLights"]
 
 _libs = {}
 
@@ -433,6 +466,8 @@ def load_library(path=None):
     lib.nrdHipResolveOutputsEx.argtypes, lib.nrdHipResolveOutputsEx.restype = [P(HipBackEndDesc), P(HipBackEndOptions), C.c_void_p], C.c_uint32
     lib.nrdHipPackInputsSplit.argtypes, lib.nrdHipPackInputsSplit.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSamples), P(HipFrontEndSplit), C.c_void_p], C.c_uint32
     lib.nrdHipResolveOutputsSplit.argtypes, lib.nrdHipResolveOutputsSplit.restype = [P(HipBackEndDesc), P(HipBackEndOptions), P(HipBackEndSplit), C.c_void_p], C.c_uint32
+    lib.nrdHipPackShadowLights.argtypes, lib.nrdHipPackShadowLights.restype = [P(HipShadowLightsPackDesc), C.c_void_p], C.c_uint32
+    lib.nrdHipResolveShadowLights.argtypes, lib.nrdHipResolveShadowLights.restype = [P(HipShadowLightsResolveDesc), C.c_void_p], C.c_uint32
     lib.nrdHipCheckInputs.argtypes, lib.nrdHipCheckInputs.restype = [C.c_void_p, C.c_void_p, C.c_uint32, P(HipInputReport), P(C.c_uint32)], C.c_uint32
     lib.nrdHipCheckInputsAsync.argtypes, lib.nrdHipCheckInputsAsync.restype = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, P(C.c_uint32)], C.c_uint32
     lib.nrdHipGetInputRuleString.argtypes, lib.nrdHipGetInputRuleString.restype = [C.c_uint32], C.c_char_p

@@ -469,3 +469,164 @@ def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=
         d.outDiffFactor = output("diff_factor", (h, w, colour), colour_format)
         d.outSpecFactor = output("spec_factor", (h, w, colour), colour_format)
     return res, d, keep + [common_settings]
+
+
+# ---- SIGMA shadows for local and many lights ------------------------------------------------------------------------------------------------------------------
+LightType, ShadowsMode = api.LightType, api.ShadowsMode
+
+
+def shadow_lights(lights):
+    """a ctypes array of api.HipShadowLight from a sequence whose entries are api.HipShadowLight, dicts (type=LightType, tan_of_light_angular_radius=, light_size=) or
+    (type, value) pairs -- value is the tangent of the angular radius of a DIRECTIONAL light, the size of a LOCAL one"""
+    table = (api.HipShadowLight * len(lights))()
+    for dst, l in zip(table, lights):
+        if isinstance(l, api.HipShadowLight):
+            dst.type, dst.tanOfLightAngularRadius, dst.lightSize, dst.reserved = l.type, l.tanOfLightAngularRadius, l.lightSize, l.reserved
+        elif isinstance(l, dict):
+            dst.type, dst.tanOfLightAngularRadius, dst.lightSize = int(l["type"]), float(l.get("tan_of_light_angular_radius", 0.0)), float(l.get("light_size", 0.0))
+        else:
+            dst.type = int(l[0])
+            if LightType(l[0]) == LightType.LOCAL:
+                dst.lightSize = float(l[1])
+            else:
+                dst.tanOfLightAngularRadius = float(l[1])
+    return table
+
+
+def _light_stack(t, plane_ndim, what):
+    """(layer 0, layers, bytes from one layer to the next) of a stack [N, H, W(, C)] or of one plane [H, W(, C)], read where it lies"""
+    if t.ndim == plane_ndim:
+        return t, 1, 0
+    assert t.ndim == plane_ndim + 1, "%s: expected %d or %d dimensions, got shape %s" % (what, plane_ndim, plane_ndim + 1, tuple(t.shape))
+    return t[0], t.shape[0], _stride0_bytes(t)
+
+
+def light_stack(like, layers, plane_shape, dtype):
+    """an uninitialised [layers, *plane_shape] stack, allocated like `like` (a CUDA tensor or a numpy array), whose layer stride meets the rule of NRDHip.h for light layers:
+    a multiple of 4 bytes. A dense float16 [N, H, W] or uint8 [N, H, W] stack breaks it when H x W is odd / no multiple of 4, so the layers are padded and the stack is a view of
+    them: every layer [i] is dense, the stack as a whole need not be."""
+    elems, itemsize = int(np.prod(plane_shape)), np.dtype(dtype).itemsize
+    padded = -(-elems * itemsize // 4) * 4 // itemsize
+    flat = _empty(like, (layers, padded), dtype)[:, :elems]
+    stack = flat.reshape((layers,) + tuple(plane_shape)) if _is_numpy(flat) else flat.view((layers,) + tuple(plane_shape))
+    assert layers == 1 or _stride0_bytes(stack) == padded * itemsize  # (a view of the padded layers, not a copy)
+    return stack
+
+
+def shadow_stack(like, layers, height, width, channels=1):
+    """the uint8 stack to bind OUT_SHADOW_TRANSLUCENCY layer by layer ([i]: R8_UNORM [H, W], or RGBA8_UNORM [H, W, 4] with channels=4) and to hand to resolve_shadow_lights as
+    it is: see light_stack"""
+    return light_stack(like, layers, (height, width) if channels == 1 else (height, width, channels), "uint8")
+
+
+def _colour_stack(t, what):
+    layer, n, stride = _light_stack(t, 3, what)
+    assert layer.shape[2] in (3, 4), "%s: three or four channels per pixel" % what
+    return _fp32_plane(layer, layer.shape[2], what), n, stride
+
+
+def _scalar_stack(t, what):
+    layer, n, stride = _light_stack(t, 2, what)
+    return _fp32_plane(layer, 1, what), n, stride
+
+
+def describe_pack_shadow_lights(lights, distance_to_occluder, distance_to_light=None, translucency=None, lighting=None, weight=None, mode=ShadowsMode.PER_LIGHT, out=None, stream=None,
+                                lib=None):
+    """The descriptor of one nrdHipPackShadowLights launch, without launching: (packed planes, api.HipShadowLightsPackDesc, what the descriptor points into besides its
+    arguments). lights: see shadow_lights (N entries). fp32 inputs, one layer per light, read where they lie (stride(0) is the layer stride; [H, W(, C)] for one light):
+    distance_to_occluder [N, H, W]; distance_to_light [N, H, W] (needed with a LOCAL light; the layer of a directional light is not read); translucency [N, H, W, 3 or 4]
+    (PER_LIGHT); lighting [N, H, W, 3 or 4] and weight [N, H, W] (COMBINED). Returns {ResourceType: (array, Format)}:
+      PER_LIGHT  IN_PENUMBRA [N, H, W] float16 and, with translucency, IN_TRANSLUCENCY [N, H, W, 4] uint8 -- layer i binds as IN_PENUMBRA / IN_TRANSLUCENCY of light i.
+                 The stacks come from light_stack: every layer [i] is dense, the layer stride is rounded up to the 4 bytes NRDHip.h asks for
+      COMBINED   IN_PENUMBRA [H, W], IN_TRANSLUCENCY [H, W, 4] and "lighting_sum" [H, W, 4] float32 ([H, W, 3] where `out` holds one)
+    `out` = a dict returned earlier, whose arrays are written again instead of allocating."""
+    mode = ShadowsMode(mode)
+    table = shadow_lights(lights)
+    d = api.HipShadowLightsPackDesc()
+    d.mode, d.lightsNum, d.lights = int(mode), len(table), table
+    d.distanceToOccluder, n, d.distanceToOccluderLayerBytes = _scalar_stack(distance_to_occluder, "distance_to_occluder")
+    assert n == len(table), "distance_to_occluder holds %d layers for %d lights" % (n, len(table))
+    h, w = distance_to_occluder.shape[-2:]
+    for t, name, field, stack in ((distance_to_light, "distance_to_light", "distanceToLight", _scalar_stack), (translucency, "translucency", "translucency", _colour_stack),
+                                  (lighting, "lighting", "lighting", _colour_stack), (weight, "weight", "weight", _scalar_stack)):
+        if t is not None:
+            plane, layers, stride = stack(t, name)
+            assert layers == n, "%s holds %d layers for %d lights" % (name, layers, n)
+            setattr(d, field, plane)
+            setattr(d, field + "LayerBytes", stride)
+    res = {}
+
+    def output(slot, shape, dtype, fmt):
+        if mode == ShadowsMode.PER_LIGHT and not (out is not None and slot in out):
+            t = light_stack(distance_to_occluder, shape[0], shape[1:], dtype)  # (a dense [N, H, W] float16 stack of an odd frame would break the layer-stride rule)
+        else:
+            t = _reuse(out, slot, distance_to_occluder, shape, dtype)
+        res[slot] = (t, fmt)
+        layer, _, stride = _light_stack(t, len(shape) - (0 if mode == ShadowsMode.COMBINED else 1), str(slot))
+        return _plane(layer, fmt), stride
+
+    stack = () if mode == ShadowsMode.COMBINED else (n,)
+    d.outPenumbra, d.outPenumbraLayerBytes = output(R.IN_PENUMBRA, stack + (h, w), "float16", F.R16_SFLOAT)
+    if mode == ShadowsMode.COMBINED or translucency is not None:
+        d.outTranslucency, d.outTranslucencyLayerBytes = output(R.IN_TRANSLUCENCY, stack + (h, w, 4), "uint8", F.RGBA8_UNORM)
+    if mode == ShadowsMode.COMBINED:
+        given = out["lighting_sum"] if out is not None and "lighting_sum" in out else None
+        given = given[0] if isinstance(given, tuple) else given
+        channels = 4 if given is None else given.shape[2]
+        d.outLightingSum, _ = output("lighting_sum", (h, w, channels), "float32", F.RGB32_SFLOAT if channels == 3 else F.RGBA32_SFLOAT)
+    return res, d, [table]
+
+
+def pack_shadow_lights(lights, distance_to_occluder, *args, **kw):
+    """see describe_pack_shadow_lights; launches on `stream` (as pack_inputs) and returns the packed planes: the front end of SIGMA for point, spot, sphere and directional
+    lights, many of them per pixel, in one launch -- per light (mode=ShadowsMode.PER_LIGHT: denoise layer by layer with one SIGMA instance whose
+    SigmaSettings.maxStabilizedFrameNum is 0, the README's "stabilizationStrength = 0") or combined into one SIGMA_SHADOW_TRANSLUCENCY pass (ShadowsMode.COMBINED)."""
+    given = inspect.signature(describe_pack_shadow_lights).bind(lights, distance_to_occluder, *args, **kw).arguments  # (stream and lib wherever they were passed)
+    with _stream_scope(distance_to_occluder, given.get("stream")):
+        res, d, keep = describe_pack_shadow_lights(lights, distance_to_occluder, *args, **kw)
+        lib = given.get("lib") or api.load_library()
+        _check(lib, lib.nrdHipPackShadowLights(C.byref(d), _stream(distance_to_occluder, given.get("stream"))), "nrdHipPackShadowLights")
+    return res
+
+
+def describe_resolve_shadow_lights(shadow, lighting, mode=ShadowsMode.PER_LIGHT, lights_num=None, channels=4, out=None, stream=None, lib=None):
+    """The descriptor of one nrdHipResolveShadowLights launch, without launching: (fp32 [H, W, channels] array, api.HipShadowLightsResolveDesc, arrays the descriptor points into besides its arguments). shadow: the denoised
+    OUT_SHADOW_TRANSLUCENCY -- PER_LIGHT: a stack [N, H, W] or [N, H, W, 4] uint8 with lighting [N, H, W, 3 or 4], the unshadowed L_i; COMBINED: one [H, W, 4] plane with
+    lighting = the "lighting_sum" of the pack call. The result is sum( L_i * shadow_i ) in .rgb (and, COMBINED with channels=4, the shadow in .w). `out`: an array to write.
+    Layer strides are those of the arrays (stride(0)) and must be multiples of 4 bytes (16 for a four-channel lighting stack): a shadow stack from shadow_stack(...) is; a dense
+    [N, H, W] uint8 one is only when H x W is a multiple of 4, and is otherwise copied into an aligned stack first (an allocation and a copy: the third element returned holds it)."""
+    mode = ShadowsMode(mode)
+    d = api.HipShadowLightsResolveDesc()
+    d.mode = int(mode)
+    keep = []
+    plane_ndim = shadow.ndim - 1 if lighting.ndim == 4 else shadow.ndim  # (a stack where the lighting is one)
+    if shadow.ndim > plane_ndim and shadow.shape[0] > 1 and _stride0_bytes(shadow) % 4:
+        # a dense [N, H, W] uint8 stack whose H x W is no multiple of 4: the layer-stride rule of NRDHip.h refuses it. Copied into a stack that meets it (shadow_stack
+        # allocates one to bind the denoiser's outputs to in the first place: no copy then)
+        aligned = light_stack(shadow, shadow.shape[0], tuple(shadow.shape[1:]), "uint8")
+        if _is_numpy(aligned):
+            aligned[...] = shadow
+        else:
+            aligned.copy_(shadow)
+        shadow = aligned
+        keep.append(aligned)
+    layer, n, d.shadowLayerBytes = _light_stack(shadow, plane_ndim, "shadow")
+    d.shadow = _packed_plane(layer, "shadow")
+    d.lighting, layers, d.lightingLayerBytes = _colour_stack(lighting, "lighting")
+    assert layers == n, "lighting holds %d layers for %d shadow layers" % (layers, n)
+    d.lightsNum = n if mode == ShadowsMode.PER_LIGHT else (lights_num or 1)
+    h, w = layer.shape[:2]
+    assert channels in (3, 4), "channels: 3 or 4"
+    t = out if out is not None else _empty(shadow, (h, w, channels), "float32")
+    d.out = _fp32_plane(t, t.shape[2], "out")
+    return t, d, keep
+
+
+def resolve_shadow_lights(shadow, lighting, *args, **kw):
+    """see describe_resolve_shadow_lights; launches on `stream` (as pack_inputs) and returns the lit, shadowed radiance: the back end of pack_shadow_lights"""
+    given = inspect.signature(describe_resolve_shadow_lights).bind(shadow, lighting, *args, **kw).arguments
+    with _stream_scope(shadow, given.get("stream")):
+        t, d, keep = describe_resolve_shadow_lights(shadow, lighting, *args, **kw)
+        lib = given.get("lib") or api.load_library()
+        _check(lib, lib.nrdHipResolveShadowLights(C.byref(d), _stream(shadow, given.get("stream"))), "nrdHipResolveShadowLights")
+    return t

@@ -487,6 +487,157 @@ def check_inputs_main(args):
     assert best["check_inputs_ms"] <= best["torch_isfinite_ms"], "nrdHipCheckInputs is slower than the torch.isfinite chain it replaces: the kernel is not finished"
 
 
+LIGHTS_SRC = os.path.join(B.CSRC, "hip", "kernels_shadow_lights.hip")
+LIGHTS_KERNELS = {"PackLightsPerLightKernel": "pack_per_light", "PackLightsCombinedKernel": "pack_combined", "ResolveLightsPerLightKernel": "resolve_per_light",
+                  "ResolveLightsCombinedKernel": "resolve_combined"}
+
+
+def shadow_lights_isa():
+    """static facts about the four kernels behind nrdHipPackShadowLights / nrdHipResolveShadowLights (the `isa_shadow_lights` object of profiles/frontend_bench.json), as isa()"""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_shadow_lights.s")
+        flags = [f for f in B._flags(LIGHTS_SRC) if f not in ("-x", "hip")]
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", LIGHTS_SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+    out = {}
+    for mangled, s in stats.items():
+        for kernel, name in LIGHTS_KERNELS.items():
+            if kernel in mangled:
+                c = s["counter"]
+                out[name] = {"vgprs": s["vgpr"], "waves_per_simd": s["occ"], "scratch_bytes": s["scratch"], "lds_bytes": s["ldsb"], "valu": s["valu"], "salu": s["salu"], "vmem": s["vmem"],
+                             "v_div_scale_f32": c.get("v_div_scale_f32", 0), "transcendental": s["trans"]}
+    assert set(out) == set(LIGHTS_KERNELS.values()), list(stats)
+    return out
+
+
+def shadow_lights_main(args):
+    """--shadow-lights: nrdHipPackShadowLights (PER_LIGHT and COMBINED) and nrdHipResolveShadowLights (both modes) for four local lights at SIGMA's baseline size against the
+    copy rate of the same process and against the same recipes written as torch elementwise operations -- all the parent commit offers a host without kernels"""
+    result = {"isa_shadow_lights": shadow_lights_isa()}
+    if args.isa_only:
+        print(json.dumps(result))
+        return
+    import torch
+
+    from raytracingdenoiser_amd import api, frontend
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    w, h = args.width, args.height
+    px, n = w * h, 4
+    g = torch.Generator(device="cuda").manual_seed(17)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    sizes = [0.5, 1.0, 2.0, 4.0]
+    lights = [(api.LightType.LOCAL, v) for v in sizes]
+    d = 0.05 + 20.0 * rand(n, h, w)
+    d[rand(n, h, w) < 0.4] = 1e5  # lit
+    dl = d + 1.0 + 30.0 * rand(n, h, w)
+    lighting = (4.0 * rand(n, h, w, 4)).contiguous()
+    lib, stream = api.load_library(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    PL, CO = api.ShadowsMode.PER_LIGHT, api.ShadowsMode.COMBINED
+    per_res, per_desc, keep0 = frontend.describe_pack_shadow_lights(lights, d, distance_to_light=dl, mode=PL)
+    com_res, com_desc, keep1 = frontend.describe_pack_shadow_lights(lights, d, distance_to_light=dl, lighting=lighting, mode=CO)
+    shadows = torch.randint(0, 256, (n, h, w), dtype=torch.uint8, device="cuda", generator=g)
+    shadow4 = torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda", generator=g)
+    lsum = com_res["lighting_sum"][0]
+    out_a, rdesc_a, _ = frontend.describe_resolve_shadow_lights(shadows, lighting, mode=PL)
+    out_b, rdesc_b, _ = frontend.describe_resolve_shadow_lights(shadow4, lsum, mode=CO, lights_num=n)
+
+    def call(fn, desc):
+        def f():
+            assert fn(C.byref(desc), stream) == 0
+        return f
+
+    fp16_max, eps = 65504.0, 1e-6
+
+    def penumbra(i):
+        r = (sizes[i] * d[i] / (dl[i] - d[i]).clamp_min(eps)) * 0.5
+        return torch.where(d[i] >= fp16_max, fp16_max, r.clamp_max(32768.0))
+
+    def torch_pack_per_light():
+        return torch.stack([penumbra(i) for i in range(n)]).half()
+
+    def torch_pack_combined():
+        Lsum, LSsum = torch.zeros(h, w, 3, device="cuda"), torch.zeros(h, w, 3, device="cuda")
+        Wsum, Psum, dmin = torch.zeros(h, w, device="cuda"), torch.zeros(h, w, device="cuda"), torch.full((h, w), float("inf"), device="cuda")
+        for i in range(n):
+            L = lighting[i, ..., :3]
+            lit = d[i] >= fp16_max
+            Lsum = Lsum + L
+            LSsum = LSsum + L * lit.unsqueeze(-1)
+            wgt = (~lit) * (L[..., 0] * 0.2126 + L[..., 1] * 0.7152 + L[..., 2] * 0.0722)
+            Wsum, Psum, dmin = Wsum + wgt, Psum + penumbra(i) * wgt, torch.minimum(dmin, d[i])
+        tr = torch.cat([(dmin >= fp16_max).float().unsqueeze(-1), (LSsum / Lsum.clamp_min(eps)).clamp(0.0, 1.0)], -1)
+        return (torch.where(dmin >= fp16_max, fp16_max, Psum / Wsum.clamp_min(eps)).half(), torch.floor(tr * 255.0 + 0.5).to(torch.uint8),
+                torch.cat([Lsum, torch.zeros(h, w, 1, device="cuda")], -1))
+
+    def torch_resolve_per_light():
+        acc = torch.zeros(h, w, 3, device="cuda")
+        for i in range(n):
+            s = shadows[i].float() / 255.0
+            acc = acc + lighting[i, ..., :3] * (s * s).unsqueeze(-1)
+        return torch.cat([acc, torch.zeros(h, w, 1, device="cuda")], -1)
+
+    def torch_resolve_combined():
+        s = shadow4.float() / 255.0
+        s = s * s
+        return torch.cat([lsum[..., :3] * s[..., 1:], s[..., :1]], -1)
+
+    calls = {"pack_per_light": (call(lib.nrdHipPackShadowLights, per_desc), torch_pack_per_light), "pack_combined": (call(lib.nrdHipPackShadowLights, com_desc), torch_pack_combined),
+             "resolve_per_light": (call(lib.nrdHipResolveShadowLights, rdesc_a), torch_resolve_per_light), "resolve_combined": (call(lib.nrdHipResolveShadowLights, rdesc_b), torch_resolve_combined)}
+    # the two forms of each recipe agree (the torch chain is not held to the bits: it is timed, not tested)
+    for name, (kernel, chain) in calls.items():
+        kernel()
+    torch.cuda.synchronize()
+    chain = torch_pack_per_light().float()
+    assert bool(((per_res[api.ResourceType.IN_PENUMBRA][0].float() - chain).abs() <= chain * 2.0 ** -10).all())  # one fp16 step of the value at the most
+    assert float((out_a - torch_resolve_per_light()).abs().max()) <= 1e-3 and float((out_b - torch_resolve_combined()).abs().max()) <= 1e-3
+    assert float((lsum - torch_pack_combined()[2]).abs().max()) <= 1e-4
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(args.reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / args.reps
+
+    rounds = [{name + suffix: timed(fn) for name, pair in calls.items() for suffix, fn in zip(("_ms", "_torch_ms"), pair)} for _ in range(2)]
+    best = {k: min(r[k] for r in rounds) for k in rounds[0]}
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
+    bytes_per_px = {"pack_per_light": n * (4 + 4) + n * 2, "pack_combined": n * (4 + 4 + 16) + 2 + 4 + 16, "resolve_per_light": n * (1 + 16) + 16, "resolve_combined": 4 + 16 + 16}
+    kernels = {}
+    for name in calls:
+        rate = bytes_per_px[name] * px / (best[name + "_ms"] * 1e-3) / 1e9
+        kernels[name] = {"ms": best[name + "_ms"], "torch_ms": best[name + "_torch_ms"], "bytes_per_pixel": bytes_per_px[name], "gigabytes_per_second": rate,
+                         "fraction_of_copy_rate": rate / gbps.value, "kernel_over_torch": best[name + "_ms"] / best[name + "_torch_ms"]}
+    result["shadow_lights"] = dict(
+        kernels=kernels, rounds=rounds, device=torch.cuda.get_device_name(0), width=w, height=h, lights=n, reps=args.reps, warmup=args.warmup, copy_gigabytes_per_second=gbps.value,
+        planes="four LOCAL lights: distanceToOccluder / distanceToLight [4, H, W] fp32 (40 % of the texels lit), lighting [4, H, W, 4] fp32, shadows [4, H, W] uint8 (PER_LIGHT) "
+               "or [H, W, 4] uint8 (COMBINED)",
+        bytes_are="per pixel, from the formats: every input texel once (the 16-byte lighting texel whole, though 12 bytes of it are loaded) plus every output texel",
+        torch_is="the same recipe as torch elementwise operations on the same tensors, allocations included: what a host without kernels writes",
+        times_are="device events around --reps back-to-back calls, per call, the best of two alternated rounds",
+        fraction_is_not="a share of HBM bandwidth: the working set partly fits the memory-side cache, as for pack and resolve (DESIGN.md section 3.4)")
+    record = {}
+    if os.path.exists(args.out):  # the other fields of the record are another run's: kept as they are
+        with open(args.out) as fp:
+            record = json.load(fp)
+    record.update(result)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fp:
+        json.dump(record, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps({"shadow_lights": kernels, "copy_gigabytes_per_second": gbps.value}))
+    for name, k in kernels.items():
+        assert k["ms"] <= k["torch_ms"], "%s is slower than the torch chain it replaces (%.4f ms against %.4f ms): the kernel is not finished" % (name, k["ms"], k["torch_ms"])
+
+
 def synth_pack(raw, synth, torch):
     """the packing of synth.render_frame for REBLUR_DIFFUSE_SPECULAR on the raw values: its packers, elementwise torch operations with fp32 intermediates"""
     out = {"normal_roughness": synth.pack_normal_roughness(raw["normal"], raw["roughness"], raw["material"]).contiguous(), "viewz": raw["viewz"].clone(),
@@ -553,8 +704,8 @@ def rejitter_calls(args, lib, stream, pack_desc, torch, api, frontend):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=2560)
-    ap.add_argument("--height", type=int, default=1440)
+    ap.add_argument("--width", type=int, help="default: 2560, with --shadow-lights 1920 (SIGMA's baseline size)")
+    ap.add_argument("--height", type=int, help="default: 1440, with --shadow-lights 1080")
     ap.add_argument("--reps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.json"))
@@ -567,7 +718,13 @@ def main():
                     "four-channel calls; adds the `split` and `isa_split` objects to --out and leaves its other fields as they are")
     ap.add_argument("--check-inputs", action="store_true", help="a run of its own: nrdHipCheckInputsAsync on the bound REBLUR_DIFFUSE_SPECULAR planes against the copy rate and a "
                     "torch.isfinite chain; adds the `check_inputs` and `isa_check_inputs` objects to --out and leaves its other fields as they are")
+    ap.add_argument("--shadow-lights", action="store_true", help="a run of its own: nrdHipPackShadowLights / nrdHipResolveShadowLights for four local lights (1920 x 1080 unless --width / "
+                    "--height say otherwise) against the copy rate and the same recipes as torch elementwise operations; adds the `shadow_lights` and `isa_shadow_lights` objects to --out")
     args = ap.parse_args()
+    default_size = (1920, 1080) if args.shadow_lights else (2560, 1440)
+    args.width, args.height = args.width or default_size[0], args.height or default_size[1]
+    if args.shadow_lights:
+        return shadow_lights_main(args)
     if args.check_inputs:
         return check_inputs_main(args)
     if args.split:
