@@ -77,11 +77,13 @@ uint32_t nrdHipDenoise(NrdHipExecutor* executor, const uint32_t* identifiers, ui
 
 // Multi-GPU row-strip sharding: restricts this executor to PRODUCING rows [rowBegin, rowEnd) of the final outputs and of the
 // permanent (history) planes. Planes stay full-size; every pass is launched on the strip extended by the cumulative reach of the
-// passes that follow it in the dispatch list (temporal stabilization 1 row, post-blur / blur 2 x their maximum radius,
-// history fix 2 x stride, ...), so the owned rows are bit-identical to a single-GPU run provided the caller makes the other
-// ranks' owned rows of the permanent planes available before the next frame (one in-place all-gather per plane: owned strips
-// are contiguous row ranges). rowBegin = 0, rowEnd >= height restores whole-frame execution. Passes the executor cannot bound
-// (anything but the REBLUR chain in this build) always run on the whole frame.
+// passes that follow it in the dispatch list (nrdHipGetDispatchReach below: temporal stabilization 1 row, REBLUR's blur / post-blur
+// the bound of their tap rings -- 39 / 79 rows at the default radius and 1440p --, history fix its base stride + 6, ...), so the owned rows are
+// bit-identical to a single-GPU run provided the caller makes the other ranks' owned rows of the permanent planes available before
+// the next frame (one in-place all-gather per plane: owned strips are contiguous row ranges). rowBegin = 0, rowEnd >= height
+// restores whole-frame execution. REBLUR, RELAX and SIGMA lists are all bounded; a pass of unknown reach (a dynamic-resolution
+// step, a blur ring as large as its distance from the camera) and every pass in front of it run on the whole frame, as does
+// SIGMA's history Copy.
 uint32_t nrdHipSetOwnedRows(NrdHipExecutor* executor, uint32_t rowBegin, uint32_t rowEnd);
 
 // Finer-grained sharding control for a host that exchanges halos between passes (raytracingdenoiser_amd/sharding.py, HaloSharder):
@@ -96,7 +98,8 @@ uint32_t nrdHipExecuteDispatchRange(NrdHipExecutor* executor, const void* dispat
     const int32_t* rowEnd);
 
 // The halo-exchange plan of one dispatch list for rank `rank` of `world` ranks owning the row strips [stripBounds[r], stripBounds[r + 1]) (host-only,
-// no device needed; the C++ counterpart of raytracingdenoiser_amd/sharding.py plan_halo_exchange, for hosts that drive RCCL themselves):
+// no device needed). This is the planner: raytracingdenoiser_amd/sharding.py (HaloSharder), include/NRDShardedIntegrationHip.hpp and hosts that drive
+// RCCL themselves all plan with it.
 //   steps[s]   dispatches [firstDispatch, firstDispatch + dispatchCount) run between two exchanges; before them the rank sends / receives, for each of
 //              items[firstItem .. firstItem + itemCount), `widthRows` rows on either side of its strip boundaries to / from ranks rank - 1 and rank + 1
 //              (send its own top / bottom rows, receive into the rows just above / below its strip); the first `earlyCount` dispatches of the step touch

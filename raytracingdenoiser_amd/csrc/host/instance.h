@@ -2,7 +2,7 @@
 // each naming a pass (pipeline), its input/output planes and its constant block. Same data model as the reference
 // (reference Source/InstanceImpl.h:98-352, InstanceImpl.cpp:100-862): two plane pools (permanent = history,
 // transient = scratch, aliased between denoisers), ping-pong plane swapping, injected clears on CLEAR_AND_RESTART,
-// permutation selection per frame. The list is consumed by the HIP executor (csrc/hip/executor.cpp) -- or by any
+// permutation selection per frame. The list is consumed by the HIP executor (csrc/hip/executor.hip) -- or by any
 // other backend, which is how the test-suite drives the CPU oracle.
 #pragma once
 

@@ -122,89 +122,27 @@ def _is_user_input(resource_type):
     return api.ResourceType(resource_type).name.startswith("IN_")
 
 
-def plan_halo_exchange(dispatches, reach, rows, height, max_motion_rows=32, exchange_threshold=24, small_planes=(), min_strip=None):
-    """dispatches: api.Dispatch list of one frame; reach: nrdHipGetDispatchReach; rows: (row_begin, row_end) owned by this rank;
-    small_planes: keys of the down-sampled pool planes (tile maps): the passes writing them run on the whole frame on every rank (they
-    are tiny and only read user inputs), so these planes are complete everywhere and never exchanged."""
-    from . import api
-
+def plan_halo_exchange(inst, ptr, n, bounds, rank, height, max_motion_rows=32, exchange_threshold=24):
+    """The HaloPlan of dispatch list (ptr, n) of api.Instance `inst` for strip `rank` of the strips bounds[r] .. bounds[r + 1] (None: the frame cannot be cut). The planner itself
+    is nrdHipPlanHaloExchange (csrc/host/halo_plan.cpp; include/NRDHip.h describes the plan): every rule lives there, this only carries its answer over."""
     plan = HaloPlan()
-    n = len(dispatches)
-    plan.reach = list(reach)
-    if rows is None or n == 0 or any(r < 0 for r in reach):
+    plan.reach = inst.dispatch_reach(ptr, n)
+    if bounds:
+        plan.fallback, steps, row_begin, row_end = inst.plan_halo_exchange(ptr, n, bounds, rank, height, max_motion_rows, exchange_threshold)
+    else:
         plan.fallback = True
+    if plan.fallback:
         return plan
-    rb, re = rows
-    per = min_strip if min_strip is not None else re - rb  # a halo must fit into the neighbouring strip
-    starts = [0] + [i for i in range(1, n) if reach[i] > exchange_threshold]
-    bounds = starts + [n]
-    seg_of = [0] * n
-    margins = [0] * n
-    for s in range(len(starts)):
-        a, b = bounds[s], bounds[s + 1]
+    plan.steps = [(items, first, count) for items, first, count, _ in steps]
+    plan.early = [early for *_, early in steps]
+    plan.row_begin, plan.row_end = row_begin, row_end
+    # margins[i]: the rows dispatch i produces beyond the strip, by definition the reach of the passes behind it in its step
+    plan.margins = [0] * n
+    for _, first, count in plan.steps:
         m = 0
-        for i in range(b - 1, a - 1, -1):
-            seg_of[i] = s
-            margins[i] = m
-            m += reach[i]
-    plan.margins = margins
-
-    last_write = {}
-    cleared = set()  # planes a Clear_ pass of this frame wrote (every texel, on every rank)
-    whole_frame = set()
-    need = {}  # (key, writer index or -1) -> halo rows
-    for i, d in enumerate(dispatches):
-        reads = [(int(t), idx) for dt, t, idx in d.resources if dt == api.DescriptorType.TEXTURE and not _is_user_input(t) and (int(t), idx) not in small_planes]
-        writes = [(int(t), idx) for dt, t, idx in d.resources if dt == api.DescriptorType.STORAGE_TEXTURE and not _is_user_input(t)]
-        if any(key in small_planes for key in writes):
-            whole_frame.add(i)
-            if any(key not in small_planes for key in writes) or reads:
-                plan.fallback = True  # a tile-map pass that also touches full-resolution pool planes: not expected, stay safe
-                return plan
-            continue
-        for key in reads:
-            w = last_write.get(key, -1)
-            # a plane written by SIGMA's Copy IS last frame's history (previous output -> HISTORY, texel to texel): TemporalStabilization samples it at the reprojected
-            # position, so its readers need the motion bound like readers of a carried-over plane (executor.hip nrdHipPlanHaloExchange: the same rule)
-            history_copy = w >= 0 and dispatches[w].shader.startswith("SIGMA_Copy")
-            if history_copy and seg_of[w] == seg_of[i]:
-                plan.fallback = True
-                return plan
-            if w >= 0 and seg_of[w] == seg_of[i]:
-                # produced in this segment with a sufficient margin -- where it was WRITTEN. Every pass skips the sky, and a reader with a neighbourhood (reach > 0) also reads the
-                # texels next to the geometry that the writer left alone (RELAX TemporalAccumulation takes the specular hit distance of its 3x3 from the pre-pass output, sky or
-                # not: RELAX_TemporalAccumulation.hlsli:363, 433-450). On one GPU such a texel holds what the plane held at the end of the last frame; on a rank that is only true
-                # inside its strip. So the rows of the reader's neighbourhood that lie outside the strip are fetched from their owner at the frame start, BEFORE the writer runs
-                # (round 6: found by the 4-rank 4K model run, whose second strip starts just below the horizon).
-                if reach[i] > 0 and key not in cleared:  # (a plane cleared earlier in this frame holds zeros wherever nothing was written since: the same on every rank)
-                    need[(key, -1)] = max(need.get((key, -1), 0), margins[i] + reach[i])
-                continue
-            h = margins[i] + reach[i] + (max_motion_rows if w < 0 or history_copy else 0)
-            if h > 0:
-                need[(key, w)] = max(need.get((key, w), 0), h)
-        for key in writes:
-            last_write[key] = i
-            if d.shader.startswith("Clear_"):
-                cleared.add(key)
-    if any(h > per for h in need.values()):
-        plan.fallback = True  # a halo would reach past the neighbouring strip
-        return plan
-
-    exchanges = [[] for _ in starts]
-    for (key, w), h in sorted(need.items()):
-        exchanges[0 if w < 0 else seg_of[w] + 1].append((key, h))
-    for s in range(len(starts)):
-        plan.steps.append((exchanges[s], bounds[s], bounds[s + 1] - bounds[s]))
-        # leading dispatches of the segment that neither read nor write a plane of this exchange: they can run while the transfers are in flight
-        keys = {key for key, _ in exchanges[s]}
-        early = 0
-        for i in range(bounds[s], bounds[s + 1]):
-            if any((int(t), idx) in keys for dt, t, idx in dispatches[i].resources):
-                break
-            early += 1
-        plan.early.append(early if keys else 0)
-    plan.row_begin = [-1 if i in whole_frame else max(rb - margins[i], 0) for i in range(n)]
-    plan.row_end = [height if i in whole_frame else min(re + margins[i], height) for i in range(n)]
+        for i in range(first + count - 1, first - 1, -1):
+            plan.margins[i] = m
+            m += plan.reach[i]
     return plan
 
 
@@ -465,10 +403,6 @@ class HaloSharder:
     def rows(self):
         return (self.bounds[self.rank], self.bounds[self.rank + 1]) if self.bounds else None
 
-    @property
-    def min_strip(self):
-        return min(b - a for a, b in zip(self.bounds, self.bounds[1:])) if self.bounds else self.height
-
     def pixels_per_rank(self):
         if self.rows is None:
             return self.width * self.height
@@ -538,7 +472,7 @@ class HaloSharder:
                 motion, reach = host.tolist()
         else:
             motion, reach = self._words.tolist()
-        self._words[1:].zero_()  # this frame's temporal passes report into a cleared word (stream order: behind the reduction, in front of the frame's launches)
+        self._words[1:].zero_()  # this frame's temporal passes report into a zeroed word (stream order: behind the reduction, in front of the frame's launches)
         self.history_reach_rows = float(reach)
         if self._last_frame_sharded and reach + self.HISTORY_FOOTPRINT_ROWS > self.max_motion_rows:
             self.history_halo_violations += 1
@@ -593,7 +527,7 @@ class HaloSharder:
         small = self._small_planes()
 
         def make_plan():
-            return plan_halo_exchange(dispatches, reach, self.rows, self.height, self.max_motion_rows, self.exchange_threshold, small, self.min_strip)
+            return plan_halo_exchange(self.inst, ptr, n, self.bounds, self.rank, self.height, self.max_motion_rows, self.exchange_threshold)
 
         plan = make_plan()
         if recut and not plan.fallback:
@@ -836,10 +770,7 @@ def dry_plan(name, width, height, world, overrides=None, max_motion_rows=None, e
         assert r == api.Result.SUCCESS
         reach = inst.dispatch_reach(ptr, n)
         dispatches = [api.Dispatch(ptr[i], inst.pipelines) for i in range(n)]
-    small = {(int(pool), i) for pool, descs in ((api.ResourceType.PERMANENT_POOL, inst.permanent_pool), (api.ResourceType.TRANSIENT_POOL, inst.transient_pool))
-             for i, (fmt, ds) in enumerate(descs) if ds != 1}
     bounds = [r * height // world for r in range(world + 1)]
-    min_strip = min(b - a for a, b in zip(bounds, bounds[1:]))
 
     def row_bytes(key):
         t, idx = key
@@ -859,7 +790,7 @@ def dry_plan(name, width, height, world, overrides=None, max_motion_rows=None, e
     out = {"denoiser": name, "size": [width, height], "ranks": world, "strips": bounds, "history_halo_rows": max_motion_rows, "passes": [d.shader for d in dispatches], "reach_rows": list(reach),
            "per_rank": []}
     for rank in range(world):
-        plan = plan_halo_exchange(dispatches, reach, (bounds[rank], bounds[rank + 1]), height, max_motion_rows, exchange_threshold, small, min_strip)
+        plan = plan_halo_exchange(inst, ptr, n, bounds, rank, height, max_motion_rows, exchange_threshold)
         entry = {"rank": rank, "rows": [bounds[rank], bounds[rank + 1]], "fallback_unsharded": bool(plan.fallback), "steps": []}
         total = 0
         for si, (items, first, count) in enumerate(plan.steps):

@@ -195,7 +195,7 @@ int main(int argc, char** argv) {
         cs.accumulationMode = f == 0 ? nrd::AccumulationMode::CLEAR_AND_RESTART : nrd::AccumulationMode::CONTINUE;
         nrd::ReblurSettings rs = {};
         // halos that fit a 96-row strip -- except on one frame, whose blur rings are as large as their distance from the camera and therefore have no bounded reach
-        // (executor.hip ReblurBlurReachRows): that frame runs unsharded on every rank. (Until round 5 a hit-distance reconstruction pass served as the trigger; it is sharded now.)
+        // (csrc/host/halo_plan.cpp ReblurBlurReachRows): that frame runs unsharded on every rank. (Until round 5 a hit-distance reconstruction pass served as the trigger; it is sharded now.)
         rs.maxBlurRadius = f == unshardedFrame ? 400.0f : 10.0f;
         rs.diffusePrepassBlurRadius = rs.specularPrepassBlurRadius = 12.0f;
         rs.hitDistanceReconstructionMode = nrd::HitDistanceReconstructionMode::OFF;

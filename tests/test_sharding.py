@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import halo_plan_cases
 from raytracingdenoiser_amd import api, sharding
 
 
@@ -255,7 +256,7 @@ def test_halo_plan_for_reblur_and_relax():
             r, ptr, n = inst.get_compute_dispatches_raw()
             ds = [api.Dispatch(ptr[i], inst.pipelines) for i in range(n)]
             small = {(int(api.ResourceType.TRANSIENT_POOL), i) for i, (fmt, d) in enumerate(inst.transient_pool) if d != 1}
-            plans.append((sharding.plan_halo_exchange(ds, inst.dispatch_reach(ptr, n), sharding.strip_rows(h, 3, world), h, small_planes=small), ds))
+            plans.append((sharding.plan_halo_exchange(inst, ptr, n, [r * h // world for r in range(world + 1)], 3, h), ds))
         # the restart frame is sharded too since round 6: its clears are texel-local (reach 0), and a plane that is cleared before it is read is not carried over -- nothing
         # of last frame's is exchanged for it
         restart, rds = plans[0]
@@ -270,57 +271,39 @@ def test_halo_plan_for_reblur_and_relax():
             assert plan.margins[first + count - 1] == 0  # the last pass of a segment produces exactly the owned rows
             assert all(key not in small for key, _ in items) and all(0 < width <= re - rb for _, width in items)
         # frame start: the history (planes read before they are written: + the motion bound) and, since round 6, the rows of the planes a later pass of the first segment reads
-        # with a neighbourhood -- texels their writer skips (sky) hold last frame's content, which only the owner of a row has (plan_halo_exchange)
+        # with a neighbourhood -- texels their writer skips (sky) hold last frame's content, which only the owner of a row has (nrdHipPlanHaloExchange)
         carried = set(sharding.carried_over_planes(ds, small))
         assert plan.steps[0][0] and carried <= {key for key, _ in plan.steps[0][0]}
         assert all(width >= 32 for key, width in plan.steps[0][0] if key in carried) and any(key not in carried for key, _ in plan.steps[0][0])
         tiles = [i for i, d in enumerate(ds) if "ClassifyTiles" in d.shader]
         assert all(plan.row_begin[i] == -1 for i in tiles)
         others = [i for i in range(len(ds)) if i not in tiles]
+        # the planner's rows against the definition of the margins (derived from its steps and the reach alone: sharding.plan_halo_exchange)
         assert all(plan.row_begin[i] == rb - plan.margins[i] and plan.row_end[i] == re + plan.margins[i] for i in others)
 
 
-@pytest.mark.parametrize("name,size,world,overrides,cs_kw", [
-    ("REBLUR_DIFFUSE_SPECULAR", (2560, 1440), 8, None, None),
-    ("REBLUR_DIFFUSE_SPECULAR", (2560, 1440), 4, dict(enablePerformanceMode=True, maxBlurRadius=12.0), None),
-    ("REBLUR_DIFFUSE_SPECULAR", (640, 360), 8, None, None),                                   # 45-row strips: the PostBlur halo does not fit -> unsharded
-    ("REBLUR_DIFFUSE_SPECULAR_OCCLUSION", (1920, 1080), 4, None, None),                        # the user's OUT planes are the history
-    ("REBLUR_DIFFUSE_SH", (1920, 1080), 3, dict(hitDistanceReconstructionMode=1), None),       # the pre-pass gathers from the reconstruction's output: reach = its blur radius
-    ("RELAX_DIFFUSE_SPECULAR", (1920, 1080), 3, dict(hitDistanceReconstructionMode=2), None),
-    ("RELAX_DIFFUSE_SPECULAR_SH", (3840, 2160), 8, None, None),
-    ("RELAX_SPECULAR", (1920, 1080), 2, dict(atrousIterationNum=8), None),
-    ("RELAX_DIFFUSE", (1920, 1080), 2, dict(enableAntiFirefly=True), None),                    # Copy (texel to texel) + AntiFirefly (3x3)
-    ("SIGMA_SHADOW", (1920, 1080), 4, None, None),
-])
-def test_c_planner_equals_python_planner(name, size, world, overrides, cs_kw):
-    """nrdHipPlanHaloExchange (the plan a C++ host uses to drive RCCL itself) against sharding.plan_halo_exchange, for every rank, uneven strips,
-    the restart frame and two steady-state frames (ping-pong)"""
-    import parity
-
+@pytest.mark.parametrize("name,size,world,overrides,cs_kw", halo_plan_cases.CASES)
+def test_planner_reproduces_the_recorded_plans(name, size, world, overrides, cs_kw):
+    """nrdHipPlanHaloExchange and nrdHipGetDispatchReach (csrc/host/halo_plan.cpp: the planner of HaloSharder and of a C++ host that drives RCCL itself) against the plans
+    recorded in tests/golden/halo_plans.json (tools/make_halo_plan_golden.py), for every rank, uneven strips, the restart frame and two steady-state frames (ping-pong)"""
     w, h = size
-    inst = api.Instance([(0, parity.DENOISERS[name][0])])
-    seq = parity.generate_sequence(name, 32, 18, 3)
-    small = {(int(pool), i) for pool, descs in ((api.ResourceType.PERMANENT_POOL, inst.permanent_pool), (api.ResourceType.TRANSIENT_POOL, inst.transient_pool))
-             for i, (fmt, d) in enumerate(descs) if d != 1}
-    bounds = [0] + [(r * h // world) + (7 if r % 2 else -5) for r in range(1, world)] + [h]  # uneven on purpose
+    recorded = halo_plan_cases.load()[halo_plan_cases.key(name, size, world, overrides)]
+    bounds = halo_plan_cases.strip_bounds(h, world)
     sharded = 0
-    for f in range(3):
-        inst.set_denoiser_settings(0, parity.denoiser_settings(name, seq[f], overrides))
-        assert inst.set_common_settings(parity.common_settings(seq[f]["camera"], seq[max(f - 1, 0)]["camera"], w, h, f, **(cs_kw or {}))) == api.Result.SUCCESS
-        r, ptr, n = inst.get_compute_dispatches_raw()
-        ds = [api.Dispatch(ptr[i], inst.pipelines) for i in range(n)]
-        reach = inst.dispatch_reach(ptr, n)
+    for f, (inst, _, _, ptr, n) in enumerate(halo_plan_cases.frames(name, size, overrides, cs_kw)):
+        assert inst.dispatch_reach(ptr, n) == recorded[f]["reach"], f
         for rank in range(world):
-            want = sharding.plan_halo_exchange(ds, reach, (bounds[rank], bounds[rank + 1]), h, 32, 24, small, min(b - a for a, b in zip(bounds, bounds[1:])))
-            fallback, steps, row_begin, row_end = inst.plan_halo_exchange(ptr, n, bounds, rank, h, 32, 24)
-            assert fallback == want.fallback, (f, rank)
+            want = recorded[f]["ranks"][rank]
+            fallback, steps, row_begin, row_end = inst.plan_halo_exchange(ptr, n, bounds, rank, h, halo_plan_cases.MAX_MOTION_ROWS, halo_plan_cases.EXCHANGE_THRESHOLD)
+            assert fallback == want["fallback"], (f, rank)
             if fallback:
                 assert steps == [] and row_begin == [-1] * n and row_end == [h] * n
                 continue
             sharded += 1
-            assert [(items, first, count) for items, first, count, early in steps] == [([(tuple(k), wd) for k, wd in items], first, count) for items, first, count in want.steps]
-            assert [early for *_, early in steps] == want.early
-            assert row_begin == want.row_begin and row_end == want.row_end
+            assert [[[[list(k), wd] for k, wd in items], first, count] for items, first, count, early in steps] == want["steps"], (f, rank)
+            assert [early for *_, early in steps] == want["early"], (f, rank)
+            assert row_begin == want["row_begin"] and row_end == want["row_end"], (f, rank)
+    assert f == len(recorded) - 1
     # round 6: every frame of every family is sharded -- restart frames (texel-local clears), hit-distance reconstruction (the pre-pass behind it reaches its blur radius), RELAX's
     # anti-firefly pair, SIGMA (Blur / PostBlur 35 rows, TemporalStabilization 2 + the motion bound on the history Copy forwards) -- unless a halo does not fit the strips
     expect_sharded = size != (640, 360)
@@ -889,7 +872,7 @@ def test_halo_sharding_processes_over_gloo_on_emulated_kernels(name, world, W, H
     q = ctx.Queue()
     port = 29500 + (os.getpid() % 100) + world
     frames = 4
-    # the workers (fresh processes) decode their guide planes only on the rows their passes declared (executor.hip GuideReachRows) and, with this hook, write NaNs
+    # the workers (fresh processes) decode their guide planes only on the rows their passes declared (csrc/host/halo_plan.cpp GuideReachRows) and, with this hook, write NaNs
     # everywhere else: a pass that reads a guide row outside its declared reach cannot stay bit-identical
     os.environ["NRD_HIP_POISON_GUIDES"] = "1"
     try:
