@@ -501,7 +501,57 @@ typedef struct NrdHipShadowLightsResolveDesc {
 } NrdHipShadowLightsResolveDesc;
 uint32_t nrdHipResolveShadowLights(const NrdHipShadowLightsResolveDesc* desc, void* hipStream);
 
+// Guides from world positions (reference README "INPUTS": IN_VIEWZ, IN_MV and the "LESSER TIPS" on motion vectors): what a path tracer holds are world-space hit positions, what
+// the denoisers take is linear view depth and motion vectors in exactly the convention the temporal passes undo (REBLUR_TemporalAccumulation.hlsli:131-150: old = new + MV, uv
+// units after motionVectorScale, .z = viewZprev - viewZ for 2.5D). This call derives both from `position` (and, for moving geometry, `positionPrev`) and the matrices of
+// nrd::CommonSettings, and encodes the four optional UNORM slots from fp32 planes with the passes' store codec -- so that every IN_* guide can be produced by the library. The
+// contract is the one above: executor-free, one launch, asynchronous on the stream, validated before the first HIP call, nothing enqueued on an error, no allocation, no
+// synchronisation, capturable into a graph (the camera is read when the call is made: a captured call replays with the camera it was captured with), errors through
+// nrdHipGetLastFrontEndError, the 32-bit limits per plane, RGB32_SFLOAT planes by the rules of nrdHipPackInputsSplit. Every output is optional; a plane with data == NULL is absent.
+//
+// Arithmetic: correctly rounded fp32 + - * / in exactly this order, nothing fused; a sum of three products is ( a * x + b * y ) + c * z, of three products and a constant
+// ( ( a * x + b * y ) + c * z ) + d. A float32 restatement reproduces every byte.
+// Host, once per call, from the caller's matrices as given (column-major, M[ i ][ j ] = row i, column j; no handedness flip: the flip the denoisers apply cancels in
+// viewToClip . worldToView, so uv is the same for a left-handed and a right-handed pair of matrices; outViewZ has the sign of the caller's convention, which IN_VIEWZ may have --
+// the passes take abs( IN_VIEWZ * viewZScale ) and form viewZprev = viewZ + IN_MV.z * s.z from it, so mv.z is the difference of the ABSOLUTE depths, the same for either handedness):
+//   R[ i ][ j ] = worldToViewMatrix[ i ][ j ], i, j < 3      c.i = -( ( R[ 0 ][ i ] * t.x + R[ 1 ][ i ] * t.y ) + R[ 2 ][ i ] * t.z ), t = column 3 of worldToViewMatrix (the camera position)
+//   P = viewToClipMatrix      Rp, cp, Pp: the same of worldToViewMatrixPrev / viewToClipMatrixPrev      s = motionVectorScale      world = isMotionVectorInWorldSpace
+// Device, per pixel, with X = position.xyz:
+//   miss      any component of X is NaN / INF: outViewZ = missViewZ, outMv = ( 0, 0, 0, 0 )
+//   current   D = X - c ( component-wise, the subtraction first: camera-relative as the passes are )      Xv.i = ( R[ i ][ 0 ] * D.x + R[ i ][ 1 ] * D.y ) + R[ i ][ 2 ] * D.z      viewZ = Xv.z
+//             clip.k = ( ( P[ k ][ 0 ] * Xv.x + P[ k ][ 1 ] * Xv.y ) + P[ k ][ 2 ] * Xv.z ) + P[ k ][ 3 ], k = 0, 1, 3 ( x, y, w )
+//             uv = ( clip.x / clip.w * 0.5 + 0.5, clip.y / clip.w * -0.5 + 0.5 ), replaced by ( 99999, 99999 ) if clip.w < 0 ( GetScreenUv )
+//   previous  Xp = positionPrev.xyz if the plane is given and its three components are finite, else X ( a static point )
+//             Xvp, viewZp, uvp: the same of Xp with Rp, cp, Pp
+//   motion    screen space:  mv.x = ( uvp.x - uv.x ) / s.x      mv.y = ( uvp.y - uv.y ) / s.y      mv.z = s.z != 0 ? ( abs( viewZp ) - abs( viewZ ) ) / s.z : 0
+//             world space:   mv.i = s.i != 0 ? ( Xp.i - X.i ) / s.i : 0 ( absolute coordinates, no camera term )
+//   store     outMv = ( mv.xyz, 0 ): a NaN component becomes 0, then clamped to +-65504, fp16 round-to-nearest-even.      outViewZ = viewZ
+//   UNORM     floor( saturate( x ) * 255 + 0.5 ), saturate( NaN ) = 0 ( the HLSL rule );  outBaseColorMetalness = ( baseColor.rgb, metalness )
+// The projection difference is taken unscaled on purpose: a jittered sample position cancels out of uvp - uv, and for a sample at the pixel centre uv is the pixelUv the passes add
+// the vector to. The matrices are the non-jittered ones CommonSettings asks for. outMv binds as IN_MV for THESE commonSettings (their motionVectorScale and mode).
+// INVALID_ARGUMENT, naming the field: no output at all; outViewZ / outMv without position or commonSettings, a UNORM output without its input(s); an input without any output
+// that reads it (position without outViewZ / outMv, positionPrev without outMv, ...); a non-zero reserved; commonSettings.rectSize that is not the size of the planes; with
+// outViewZ a missViewZ that is NaN / INF or for which !( abs( missViewZ * commonSettings.viewZScale ) > denoisingRange ) (it must satisfy the passes' own sky predicate); with
+// outMv in screen-space mode s.x == 0 or s.y == 0; size, pitch and alignment mismatches as above. UNSUPPORTED: an orthographic projection (as everywhere else in this build);
+// another format than listed.
+typedef struct NrdHipGuidesDesc {
+    const void* commonSettings;      // const nrd::CommonSettings* of the frame: required with outViewZ or outMv
+    float missViewZ;                 // written to outViewZ where `position` is not finite (sky)
+    uint32_t reserved;               // must be 0
+    NrdHipPlaneDesc position;        // in,  RGBA32_SFLOAT or RGB32_SFLOAT (.xyz): world-space position of the primary hit (or of the PSR's virtual position)
+    NrdHipPlaneDesc positionPrev;    // in,  same formats, optional: where that surface point was in the previous frame, previous world space; absent = static scene
+    NrdHipPlaneDesc baseColor;       // in,  RGBA32_SFLOAT or RGB32_SFLOAT (.rgb)
+    NrdHipPlaneDesc metalness;       // in,  R32_SFLOAT
+    NrdHipPlaneDesc diffConfidence, specConfidence, disocclusionThresholdMix; // in, R32_SFLOAT
+    NrdHipPlaneDesc outViewZ;        // out, R32_SFLOAT: unscaled view depth = `viewZ` of nrdHipPackInputs; binds as IN_VIEWZ when viewZScale is 1
+    NrdHipPlaneDesc outMv;           // out, RGBA16_SFLOAT: binds as IN_MV for THESE commonSettings
+    NrdHipPlaneDesc outBaseColorMetalness;                                     // out, RGBA8_UNORM (needs baseColor and metalness)
+    NrdHipPlaneDesc outDiffConfidence, outSpecConfidence, outDisocclusionThresholdMix; // out, R8_UNORM (each needs its input)
+} NrdHipGuidesDesc;
+uint32_t nrdHipPackGuides(const NrdHipGuidesDesc* desc, void* hipStream);
+
 #ifdef __cplusplus
+static_assert(sizeof(NrdHipGuidesDesc) == 328, "mirrored by raytracingdenoiser_amd/api.py"); // 16 + 13 planes of 24 bytes
 static_assert(sizeof(NrdHipShadowLight) == 16 && sizeof(NrdHipShadowLightsPackDesc) == 264 && sizeof(NrdHipShadowLightsResolveDesc) == 96, "mirrored by raytracingdenoiser_amd/api.py");
 static_assert(sizeof(NrdHipFrontEndSplit) == 88 && sizeof(NrdHipBackEndSplit) == 48, "mirrored by raytracingdenoiser_amd/api.py");
 static_assert(sizeof(NrdHipInputReport) == 72, "mirrored by raytracingdenoiser_amd/api.py");

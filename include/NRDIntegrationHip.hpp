@@ -164,6 +164,8 @@ public:
     // IN_TRANSLUCENCY per light, or combined for one SIGMA_SHADOW_TRANSLUCENCY pass; then the shadowed radiance of all lights from the denoised OUT_SHADOW_TRANSLUCENCY
     inline bool PackShadowLights(const NrdHipShadowLightsPackDesc& desc) { return nrdHipPackShadowLights(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
     inline bool ResolveShadowLights(const NrdHipShadowLightsResolveDesc& desc) { return nrdHipResolveShadowLights(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
+    // IN_VIEWZ and IN_MV from world-space hit positions and the matrices of the frame's CommonSettings, and the optional UNORM guide slots from fp32 planes (nrdHipPackGuides)
+    inline bool PackGuides(const NrdHipGuidesDesc& desc) { return nrdHipPackGuides(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
     inline const char* GetLastFrontEndError() const { return nrdHipGetLastFrontEndError(); }
 
     // Assumes that no work of this integration is in flight on the stream

@@ -355,6 +355,16 @@ class HipShadowLightsResolveDesc(C.Structure):  # include/NRDHip.h NrdHipShadowL
 assert C.sizeof(HipShadowLight) == 16 and C.sizeof(HipShadowLightsPackDesc) == 264 and C.sizeof(HipShadowLightsResolveDesc) == 96
 
 
+class HipGuidesDesc(C.Structure):  # include/NRDHip.h NrdHipGuidesDesc
+    _fields_ = [("commonSettings", C.c_void_p), ("missViewZ", C.c_float), ("reserved", C.c_uint32), ("position", HipPlaneDesc), ("positionPrev", HipPlaneDesc),
+                ("baseColor", HipPlaneDesc), ("metalness", HipPlaneDesc), ("diffConfidence", HipPlaneDesc), ("specConfidence", HipPlaneDesc), ("disocclusionThresholdMix", HipPlaneDesc),
+                ("outViewZ", HipPlaneDesc), ("outMv", HipPlaneDesc), ("outBaseColorMetalness", HipPlaneDesc), ("outDiffConfidence", HipPlaneDesc), ("outSpecConfidence", HipPlaneDesc),
+                ("outDisocclusionThresholdMix", HipPlaneDesc)]
+
+
+assert C.sizeof(HipGuidesDesc) == 328
+
+
 # include/NRDHip.h NRD_HIP_INPUT_RULE_*: bit r of nrdHipCheckInputs' rulesChecked, index r of NrdHipInputReport::count / first
 INPUT_RULES = ("VIEWZ_NOT_FINITE", "MV_NOT_FINITE", "DIFF_NOT_FINITE", "SPEC_NOT_FINITE", "DIFF_HITDIST_RANGE", "SPEC_HITDIST_RANGE", "PENUMBRA_INVALID", "SIGNAL_NOT_FINITE")
 
@@ -391,7 +401,8 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipExecuteDispatchRange", "nrdHipPlanHaloExchange", "nrdHipSetGraphMode", "nrdHipGetGraphStats", "nrdHipGetTileFallbackStats", "nrdHipGetNumericsMode", "nrdHipMeasureCopyBandwidth",
                    "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError",
                    "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit",
-                   "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString", "nrdHipPackShadowLights", "nrdHipResolveShadowLights"]
+                   "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString", "nrdHipPackShadowLights", "nrdHipResolveShadowLights",
+                   "nrdHipPackGuides"]
 
 _libs = {}
 
@@ -468,6 +479,7 @@ def load_library(path=None):
     lib.nrdHipResolveOutputsSplit.argtypes, lib.nrdHipResolveOutputsSplit.restype = [P(HipBackEndDesc), P(HipBackEndOptions), P(HipBackEndSplit), C.c_void_p], C.c_uint32
     lib.nrdHipPackShadowLights.argtypes, lib.nrdHipPackShadowLights.restype = [P(HipShadowLightsPackDesc), C.c_void_p], C.c_uint32
     lib.nrdHipResolveShadowLights.argtypes, lib.nrdHipResolveShadowLights.restype = [P(HipShadowLightsResolveDesc), C.c_void_p], C.c_uint32
+    lib.nrdHipPackGuides.argtypes, lib.nrdHipPackGuides.restype = [P(HipGuidesDesc), C.c_void_p], C.c_uint32
     lib.nrdHipCheckInputs.argtypes, lib.nrdHipCheckInputs.restype = [C.c_void_p, C.c_void_p, C.c_uint32, P(HipInputReport), P(C.c_uint32)], C.c_uint32
     lib.nrdHipCheckInputsAsync.argtypes, lib.nrdHipCheckInputsAsync.restype = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, P(C.c_uint32)], C.c_uint32
     lib.nrdHipGetInputRuleString.argtypes, lib.nrdHipGetInputRuleString.restype = [C.c_uint32], C.c_char_p

@@ -1,4 +1,4 @@
-// Host side of the front-end / back-end calls (include/NRDHip.h nrdHipPackInputs* / nrdHipResolveOutputs* / nrdHipPackShadowLights / nrdHipResolveShadowLights), shared by their
+// Host side of the front-end / back-end calls (include/NRDHip.h nrdHipPackInputs* / nrdHipResolveOutputs* / nrdHipPackShadowLights / nrdHipResolveShadowLights / nrdHipPackGuides), shared by their
 // translation units: the kernels' view of a plane, the last error text and the checks every plane of a call goes through -- all of it in front of the first HIP call.
 #pragma once
 
@@ -104,6 +104,14 @@ struct Checker {
         return ownerIsRgb ? Check(p, name, required, nrd::Format::R32_SFLOAT) : FePlane{nullptr, 0};
     }
 };
+
+// a plane the chosen mode or set of outputs has no use for must be absent: a caller who passes it expects something the call will not do
+inline void Refuse(Checker& c, const NrdHipPlaneDesc& p, const char* name, const char* why) {
+    if (p.data)
+        c.Error(nrd::Result::INVALID_ARGUMENT, name, why);
+}
+
+inline bool IsRgb(const NrdHipPlaneDesc& p) { return p.format == (uint32_t)nrd::Format::RGB32_SFLOAT; }
 
 // a layer stride of a plane the kernel reads `num` > 1 layers of; dwords: an RGB32_SFLOAT stack or an R32_SFLOAT companion (nrdHipPackInputsSplit)
 inline void CheckLayerBytes(Checker& c, uint64_t layerBytes, const FePlane& plane, uint32_t num, const char* field, bool dwords = false) {

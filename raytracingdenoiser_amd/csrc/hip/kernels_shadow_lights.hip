@@ -231,14 +231,6 @@ uint32_t CheckCount(const char* entry, uint32_t mode, uint32_t lightsNum) {
     return (uint32_t)nrd::Result::SUCCESS;
 }
 
-// a plane the mode has no use for must be absent: a caller who passes it expects something the call will not do
-void Refuse(Checker& c, const NrdHipPlaneDesc& p, const char* name, const char* why) {
-    if (p.data)
-        c.Error(nrd::Result::INVALID_ARGUMENT, name, why);
-}
-
-bool IsRgb(const NrdHipPlaneDesc& p) { return p.format == (uint32_t)nrd::Format::RGB32_SFLOAT; }
-
 } // namespace
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackShadowLights(const NrdHipShadowLightsPackDesc* d, void* hipStream) {

@@ -1,4 +1,4 @@
-"""Front end / back end on the device: plumbing over nrdHipPackInputs(Ex) / nrdHipResolveOutputs(Ex) (include/NRDHip.h).
+"""Front end / back end on the device: plumbing over nrdHipPackInputs(Ex) / nrdHipResolveOutputs(Ex), nrdHipPack / ResolveShadowLights and nrdHipPackGuides (include/NRDHip.h).
 
 pack_inputs() turns an application's fp32 buffers into the packed planes HipExecutor.bind accepts, resolve_outputs() turns the denoised OUT_* planes into
 linear fp32 radiance -- one kernel launch each, asynchronous on the current stream, usable inside torch.cuda.graph. Buffers may be four-channel, or three-channel with `.w`
@@ -630,3 +630,76 @@ def resolve_shadow_lights(shadow, lighting, *args, **kw):
         lib = given.get("lib") or api.load_library()
         _check(lib, lib.nrdHipResolveShadowLights(C.byref(d), _stream(shadow, given.get("stream"))), "nrdHipResolveShadowLights")
     return t
+
+
+# ---- guides from world positions ------------------------------------------------------------------------------------------------------------------------------
+MISS_VIEWZ = 1.0e6  # above the default CommonSettings.denoisingRange (5e5): the passes take such a pixel for sky
+
+
+class PackedGuides(dict):
+    """{ResourceType: (array, Format)} as HipExecutor.bind_packed takes it, plus `viewz`: the IN_VIEWZ array once more, the unscaled view depth to hand to pack_inputs"""
+
+    viewz = None
+
+
+def _xyz_plane(t, what):
+    assert t.ndim == 3 and t.shape[2] in (3, 4), "%s: expected [H, W, 3] or [H, W, 4], got shape %s" % (what, tuple(t.shape))
+    return _fp32_plane(t, t.shape[2], what)
+
+
+def describe_pack_guides(position, common_settings=None, position_prev=None, miss_viewz=MISS_VIEWZ, base_color=None, metalness=None, diff_confidence=None, spec_confidence=None,
+                         disocclusion_threshold_mix=None, out=None, stream=None, lib=None, want=("viewz", "mv")):
+    """The descriptor of one nrdHipPackGuides launch, without launching: (PackedGuides, api.HipGuidesDesc, what the descriptor points into besides its arguments) -- for a caller
+    that launches the same frame layout repeatedly through the C-ABI itself (the camera of common_settings is read at every call). fp32 inputs, read where they lie: position
+    [H, W, 3] or [H, W, 4], the world-space position of the primary hit, NaN / INF on the sky (None: only the UNORM slots are wanted); position_prev, the same surface point one
+    frame back (None: a static scene); base_color [H, W, 3 or 4] with metalness [H, W]; diff_confidence, spec_confidence, disocclusion_threshold_mix [H, W]. With a position:
+    IN_VIEWZ [H, W] float32 (miss_viewz on the sky; binds as IN_VIEWZ when CommonSettings.viewZScale is 1) and IN_MV [H, W, 4] float16 in the convention of common_settings
+    (motionVectorScale, isMotionVectorInWorldSpace). With their inputs: IN_BASECOLOR_METALNESS [H, W, 4] uint8, IN_DIFF_CONFIDENCE, IN_SPEC_CONFIDENCE,
+    IN_DISOCCLUSION_THRESHOLD_MIX [H, W] uint8. want: which of the two position outputs, "viewz" and / or "mv" (default: both; position_prev is read by "mv" alone). `out` = a dict
+    returned earlier, whose arrays are written again instead of allocating."""
+    like = next(t for t in (position, base_color, diff_confidence, spec_confidence, disocclusion_threshold_mix) if t is not None)
+    h, w = like.shape[:2]
+    d = api.HipGuidesDesc()
+    d.commonSettings = _settings_ptr(common_settings)
+    d.missViewZ = float(miss_viewz)
+    res = PackedGuides()
+
+    def output(slot, shape, dtype, fmt):
+        t = _reuse(out, slot, like, shape, dtype)
+        res[slot] = (t, fmt)
+        return _plane(t, fmt)
+
+    if position is not None:
+        want = tuple(want)
+        assert want and set(want) <= {"viewz", "mv"}, "want: \"viewz\" and / or \"mv\""
+        d.position = _xyz_plane(position, "position")
+        if position_prev is not None:
+            d.positionPrev = _xyz_plane(position_prev, "position_prev")
+        if "viewz" in want:
+            d.outViewZ = output(R.IN_VIEWZ, (h, w), "float32", F.R32_SFLOAT)
+            res.viewz = res[R.IN_VIEWZ][0]
+        if "mv" in want:
+            d.outMv = output(R.IN_MV, (h, w, 4), "float16", F.RGBA16_SFLOAT)
+    if base_color is not None or metalness is not None:
+        assert base_color is not None and metalness is not None, "IN_BASECOLOR_METALNESS needs base_color and metalness"
+        d.baseColor, d.metalness = _xyz_plane(base_color, "base_color"), _fp32_plane(metalness, 1, "metalness")
+        d.outBaseColorMetalness = output(R.IN_BASECOLOR_METALNESS, (h, w, 4), "uint8", F.RGBA8_UNORM)
+    for t, name, field, slot in ((diff_confidence, "diff_confidence", "DiffConfidence", R.IN_DIFF_CONFIDENCE), (spec_confidence, "spec_confidence", "SpecConfidence", R.IN_SPEC_CONFIDENCE),
+                                 (disocclusion_threshold_mix, "disocclusion_threshold_mix", "DisocclusionThresholdMix", R.IN_DISOCCLUSION_THRESHOLD_MIX)):
+        if t is not None:
+            setattr(d, field[0].lower() + field[1:], _fp32_plane(t, 1, name))
+            setattr(d, "out" + field, output(slot, (h, w), "uint8", F.R8_UNORM))
+    return res, d, [common_settings]
+
+
+def pack_guides(position, *args, **kw):
+    """see describe_pack_guides; launches on `stream` (as pack_inputs) and returns the PackedGuides: IN_VIEWZ and IN_MV derived on the device from world-space positions and
+    the matrices of common_settings, and the optional UNORM guide slots encoded from fp32 planes -- one launch (NRDHip.h nrdHipPackGuides). The dict goes to
+    HipExecutor.bind_packed as it is; its `viewz` is the `viewz` argument of pack_inputs."""
+    given = inspect.signature(describe_pack_guides).bind(position, *args, **kw).arguments
+    like = next(t for t in (position, given.get("base_color"), given.get("diff_confidence"), given.get("spec_confidence"), given.get("disocclusion_threshold_mix")) if t is not None)
+    with _stream_scope(like, given.get("stream")):
+        res, d, keep = describe_pack_guides(position, *args, **kw)
+        lib = given.get("lib") or api.load_library()
+        _check(lib, lib.nrdHipPackGuides(C.byref(d), _stream(like, given.get("stream"))), "nrdHipPackGuides")
+    return res

@@ -213,7 +213,7 @@ def _pack_relax(out, name, radiance, hit_dist, direction):
 def render_frame(width, height, frame, device="cpu", static_camera=False, noise=True, seed=7, want=("reblur",), camera_frame=None):
     """Returns a dict with the packed planes and the camera (for CommonSettings). camera_frame: the frame index the camera pose is taken from
     (default: frame) -- a camera that stops moving while the noise keeps changing. want "raw": additionally out["raw"], the fp32 values in front of the packers (what an
-    application holds: the input of frontend.pack_inputs) -- normal, roughness, material_id, albedo, diff / spec _radiance, _hit_dist (world units, 0 on the sky), _direction,
+    application holds: the input of frontend.pack_inputs / pack_guides) -- position (world space, NaN on the sky), normal, roughness, material_id, albedo, diff / spec _radiance, _hit_dist (world units, 0 on the sky), _direction,
     distance_to_occluder (0 where NoL <= 0, FP16_MAX on a miss)."""
     dev = torch.device(device)
     cam = Camera(width, height, frame if camera_frame is None else camera_frame, static=static_camera)
@@ -249,6 +249,7 @@ def render_frame(width, height, frame, device="cpu", static_camera=False, noise=
     raw = None
     if "raw" in want:
         raw = out["raw"] = {"normal": n, "roughness": rough, "material_id": material_id, "albedo": alb}
+        raw["position"] = torch.where(is_sky.unsqueeze(-1), torch.full_like(p, float("nan")), p)  # world-space hit position, NaN on the sky: the input of frontend.pack_guides
     out["mv"] = torch.zeros((height, width, 4), dtype=torch.float16, device=dev)  # static scene, world-space MVs scaled by 0
     if "basecolor" in want:
         # IN_BASECOLOR_METALNESS (RGBA8_UNORM): the surface albedo as base colour, metalness in bands {0, 0.5, 1} of the world position

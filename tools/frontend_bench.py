@@ -15,8 +15,11 @@ planes), pack_split_ms (nrdHipPackInputsSplit in place), and the same three for 
 --check-inputs is a run of its own that adds the `check_inputs` and `isa_check_inputs` objects to the output file: nrdHipCheckInputsAsync on the bound REBLUR_DIFFUSE_SPECULAR planes
 of raytracingdenoiser_amd/synth.py (28 B per pixel: viewZ 4, IN_MV 8, two signals 8 + 8) against (a) the copy rate of the same run and (b) what a tensor host does today for the same
 answer: torch.isfinite over the four planes, masked with the range test, .all(). The run fails if the kernel is slower than (b).
+--guides is a run of its own that adds the `guides` and `isa_guides` objects to the output file: nrdHipPackGuides on RGB32_SFLOAT position and positionPrev planes (36 B per pixel
+with IN_VIEWZ and IN_MV) against the copy rate of the same run, next to the four shadow-light calls of --shadow-lights on planes of the same size -- streaming kernels of the same
+shape, its yardstick; the whole set three times with the rows alternating, each row's spread over the rounds next to its number.
 usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]] [--split]
-       [--check-inputs]"""
+       [--check-inputs] [--shadow-lights] [--guides]"""
 import argparse
 import ctypes as C
 import json
@@ -510,6 +513,30 @@ def shadow_lights_isa():
     return out
 
 
+def _shadow_light_planes(torch, api, frontend, w, h):
+    """the planes and descriptors of the four timed shadow-light calls (four LOCAL lights, 40 % of the texels lit), and the bytes each moves per pixel, from the formats"""
+    n = 4
+    g = torch.Generator(device="cuda").manual_seed(17)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    sizes = [0.5, 1.0, 2.0, 4.0]
+    lights = [(api.LightType.LOCAL, v) for v in sizes]
+    d = 0.05 + 20.0 * rand(n, h, w)
+    d[rand(n, h, w) < 0.4] = 1e5  # lit
+    dl = d + 1.0 + 30.0 * rand(n, h, w)
+    lighting = (4.0 * rand(n, h, w, 4)).contiguous()
+    PL, CO = api.ShadowsMode.PER_LIGHT, api.ShadowsMode.COMBINED
+    per_res, per_desc, keep0 = frontend.describe_pack_shadow_lights(lights, d, distance_to_light=dl, mode=PL)
+    com_res, com_desc, keep1 = frontend.describe_pack_shadow_lights(lights, d, distance_to_light=dl, lighting=lighting, mode=CO)
+    shadows = torch.randint(0, 256, (n, h, w), dtype=torch.uint8, device="cuda", generator=g)
+    shadow4 = torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda", generator=g)
+    lsum = com_res["lighting_sum"][0]
+    out_a, rdesc_a, _ = frontend.describe_resolve_shadow_lights(shadows, lighting, mode=PL)
+    out_b, rdesc_b, _ = frontend.describe_resolve_shadow_lights(shadow4, lsum, mode=CO, lights_num=n)
+    bytes_per_px = {"pack_per_light": n * (4 + 4) + n * 2, "pack_combined": n * (4 + 4 + 16) + 2 + 4 + 16, "resolve_per_light": n * (1 + 16) + 16, "resolve_combined": 4 + 16 + 16}
+    return dict(n=n, sizes=sizes, d=d, dl=dl, lighting=lighting, shadows=shadows, shadow4=shadow4, lsum=lsum, per_res=per_res, per_desc=per_desc, com_res=com_res, com_desc=com_desc,
+                out_a=out_a, rdesc_a=rdesc_a, out_b=out_b, rdesc_b=rdesc_b, keep=[keep0, keep1], bytes_per_px=bytes_per_px)
+
+
 def shadow_lights_main(args):
     """--shadow-lights: nrdHipPackShadowLights (PER_LIGHT and COMBINED) and nrdHipResolveShadowLights (both modes) for four local lights at SIGMA's baseline size against the
     copy rate of the same process and against the same recipes written as torch elementwise operations -- all the parent commit offers a host without kernels"""
@@ -524,24 +551,11 @@ def shadow_lights_main(args):
     if not torch.cuda.is_available():
         raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
     w, h = args.width, args.height
-    px, n = w * h, 4
-    g = torch.Generator(device="cuda").manual_seed(17)
-    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
-    sizes = [0.5, 1.0, 2.0, 4.0]
-    lights = [(api.LightType.LOCAL, v) for v in sizes]
-    d = 0.05 + 20.0 * rand(n, h, w)
-    d[rand(n, h, w) < 0.4] = 1e5  # lit
-    dl = d + 1.0 + 30.0 * rand(n, h, w)
-    lighting = (4.0 * rand(n, h, w, 4)).contiguous()
+    px = w * h
     lib, stream = api.load_library(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    PL, CO = api.ShadowsMode.PER_LIGHT, api.ShadowsMode.COMBINED
-    per_res, per_desc, keep0 = frontend.describe_pack_shadow_lights(lights, d, distance_to_light=dl, mode=PL)
-    com_res, com_desc, keep1 = frontend.describe_pack_shadow_lights(lights, d, distance_to_light=dl, lighting=lighting, mode=CO)
-    shadows = torch.randint(0, 256, (n, h, w), dtype=torch.uint8, device="cuda", generator=g)
-    shadow4 = torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda", generator=g)
-    lsum = com_res["lighting_sum"][0]
-    out_a, rdesc_a, _ = frontend.describe_resolve_shadow_lights(shadows, lighting, mode=PL)
-    out_b, rdesc_b, _ = frontend.describe_resolve_shadow_lights(shadow4, lsum, mode=CO, lights_num=n)
+    t = _shadow_light_planes(torch, api, frontend, w, h)
+    n, sizes, d, dl, lighting, shadows, shadow4, lsum = t["n"], t["sizes"], t["d"], t["dl"], t["lighting"], t["shadows"], t["shadow4"], t["lsum"]
+    per_res, per_desc, com_desc, out_a, rdesc_a, out_b, rdesc_b = t["per_res"], t["per_desc"], t["com_desc"], t["out_a"], t["rdesc_a"], t["out_b"], t["rdesc_b"]
 
     def call(fn, desc):
         def f():
@@ -610,7 +624,7 @@ def shadow_lights_main(args):
     best = {k: min(r[k] for r in rounds) for k in rounds[0]}
     gbps = C.c_double()
     assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
-    bytes_per_px = {"pack_per_light": n * (4 + 4) + n * 2, "pack_combined": n * (4 + 4 + 16) + 2 + 4 + 16, "resolve_per_light": n * (1 + 16) + 16, "resolve_combined": 4 + 16 + 16}
+    bytes_per_px = t["bytes_per_px"]
     kernels = {}
     for name in calls:
         rate = bytes_per_px[name] * px / (best[name + "_ms"] * 1e-3) / 1e9
@@ -636,6 +650,118 @@ def shadow_lights_main(args):
     print(json.dumps({"shadow_lights": kernels, "copy_gigabytes_per_second": gbps.value}))
     for name, k in kernels.items():
         assert k["ms"] <= k["torch_ms"], "%s is slower than the torch chain it replaces (%.4f ms against %.4f ms): the kernel is not finished" % (name, k["ms"], k["torch_ms"])
+
+
+GUIDES_SRC = os.path.join(B.CSRC, "hip", "kernels_guides.hip")
+
+
+def guides_isa():
+    """static facts about every instantiation of the kernel behind nrdHipPackGuides (the `isa_guides` object of profiles/frontend_bench.json), as isa(): named
+    pack_guides_<bytes of a position texel>_<bytes of a positionPrev texel> (0 = the plane is absent)"""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_guides.s")
+        flags = [f for f in B._flags(GUIDES_SRC) if f not in ("-x", "hip")]
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", GUIDES_SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+    out = {}
+    for mangled, s in stats.items():
+        m = re.search(r"PackGuidesKernelILj(\d+)ELj(\d+)E", mangled)
+        if m:
+            c = s["counter"]
+            out["pack_guides_%s_%s" % m.groups()] = {
+                "vgprs": s["vgpr"], "waves_per_simd": s["occ"], "scratch_bytes": s["scratch"], "lds_bytes": s["ldsb"], "valu": s["valu"], "salu": s["salu"], "vmem": s["vmem"],
+                "global_load_dwordx4": c.get("global_load_dwordx4", 0), "global_load_dwordx3": c.get("global_load_dwordx3", 0), "global_store_dwordx2": c.get("global_store_dwordx2", 0),
+                "v_div_scale_f32": c.get("v_div_scale_f32", 0), "transcendental": s["trans"]}
+    assert set(out) == {"pack_guides_%d_%d" % k for k in ((0, 0), (12, 0), (12, 12), (12, 16), (16, 0), (16, 12), (16, 16))}, list(stats)
+    return out
+
+
+def guides_main(args):
+    """--guides: nrdHipPackGuides at 2560 x 1440 -- IN_VIEWZ and IN_MV from RGB32_SFLOAT position and positionPrev planes, 36 bytes per pixel -- against the copy rate of the same
+    process, next to the four shadow-light calls on planes of the same size: streaming kernels of the same shape, its yardstick. The whole set is timed three times, the rows
+    alternating; the spread of a row over the three rounds stands next to its number."""
+    result = {"isa_guides": guides_isa()}
+    if args.isa_only:
+        print(json.dumps(result))
+        return
+    import torch
+
+    from raytracingdenoiser_amd import api, frontend, scene, synth
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    w, h = args.width, args.height
+    px = w * h
+    lib, stream = api.load_library(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g = torch.Generator(device="cuda").manual_seed(23)
+    cam, cam_prev = synth.Camera(w, h, 1), synth.Camera(w, h, 0)
+    cs = scene.common_settings(cam, cam_prev, w, h, 1, isMotionVectorInWorldSpace=False, motionVectorScale=(1.0 / w, 1.0 / h, 1.0))
+    # points in front of both cameras, a tenth of them sky; the surface moved by a few centimetres
+    depth = 2.0 + 30.0 * torch.rand(h, w, 1, device="cuda", generator=g)
+    lateral = (torch.rand(h, w, 2, device="cuda", generator=g) - 0.5) * depth
+    rot = torch.tensor([cam.right, cam.up, cam.fwd], device="cuda", dtype=torch.float32)
+    position = (torch.cat([lateral, depth], -1) @ rot + torch.tensor(cam.pos, device="cuda")).contiguous()
+    position[torch.rand(h, w, device="cuda", generator=g) < 0.1] = float("nan")
+    position_prev = (position + 0.02 * (torch.rand(h, w, 3, device="cuda", generator=g) - 0.5)).contiguous()
+    res, desc, keep = frontend.describe_pack_guides(position, cs, position_prev)
+    t = _shadow_light_planes(torch, api, frontend, w, h)
+
+    def call(fn, d):
+        def f():
+            assert fn(C.byref(d), stream) == 0, lib.nrdHipGetLastFrontEndError()
+        return f
+
+    calls = {"guides": call(lib.nrdHipPackGuides, desc), "pack_per_light": call(lib.nrdHipPackShadowLights, t["per_desc"]), "pack_combined": call(lib.nrdHipPackShadowLights, t["com_desc"]),
+             "resolve_per_light": call(lib.nrdHipResolveShadowLights, t["rdesc_a"]), "resolve_combined": call(lib.nrdHipResolveShadowLights, t["rdesc_b"])}
+    bytes_per_px = dict(t["bytes_per_px"], guides=12 + 12 + 4 + 8)
+    for f in calls.values():
+        f()
+    torch.cuda.synchronize()
+    viewz = res.viewz
+    sky = torch.isnan(position[..., 0])
+    assert bool((viewz[sky] == frontend.MISS_VIEWZ).all()) and bool(torch.isfinite(viewz).all()) and bool(torch.isfinite(res[api.ResourceType.IN_MV][0].float()).all())
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(args.reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / args.reps
+
+    rounds = [{name: timed(fn) for name, fn in calls.items()} for _ in range(3)]
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
+    rows = {}
+    for name in calls:
+        ms = [r[name] for r in rounds]
+        fraction = lambda v: bytes_per_px[name] * px / (v * 1e-3) / 1e9 / gbps.value
+        rows[name] = {"ms": min(ms), "bytes_per_pixel": bytes_per_px[name], "fraction_of_copy_rate": fraction(min(ms)), "fraction_of_copy_rate_worst_round": fraction(max(ms)),
+                      "spread": (max(ms) - min(ms)) / min(ms)}
+    yardstick = min(rows[name]["fraction_of_copy_rate"] for name in rows if name != "guides")
+    spread = max(rows[name]["spread"] for name in rows if name != "guides")  # of the yardstick rows: the guides row's own outliers must not widen what it is allowed
+    result["guides"] = dict(
+        rows=rows, rounds=rounds, device=torch.cuda.get_device_name(0), width=w, height=h, reps=args.reps, warmup=args.warmup, copy_gigabytes_per_second=gbps.value,
+        lowest_shadow_light_fraction=yardstick, run_to_run_spread=spread, guides_meets_yardstick=rows["guides"]["fraction_of_copy_rate"] >= yardstick * (1.0 - spread),
+        planes="position and positionPrev [H, W, 3] fp32 (RGB32_SFLOAT, a tenth of the texels NaN), IN_VIEWZ [H, W] fp32 and IN_MV [H, W, 4] fp16 out, screen-space 2.5D vectors; "
+               "the four shadow-light calls of --shadow-lights on planes of the same size",
+        bytes_are="per pixel, from the formats: every input texel once plus every output texel",
+        times_are="device events around --reps back-to-back calls, per call; the whole set three times, the rows alternating; ms is the best round, spread = ( worst - best ) / best; run_to_run_spread is the largest spread among the four shadow-light rows",
+        fraction_is_not="a share of HBM bandwidth: the working set partly fits the memory-side cache, as for pack and resolve (DESIGN.md section 3.4)")
+    record = {}
+    if os.path.exists(args.out):  # the other fields of the record are another run's: kept as they are
+        with open(args.out) as fp:
+            record = json.load(fp)
+    record.update(result)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fp:
+        json.dump(record, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps({"guides": rows, "copy_gigabytes_per_second": gbps.value, "lowest_shadow_light_fraction": yardstick, "run_to_run_spread": spread}))
 
 
 def synth_pack(raw, synth, torch):
@@ -720,9 +846,13 @@ def main():
                     "torch.isfinite chain; adds the `check_inputs` and `isa_check_inputs` objects to --out and leaves its other fields as they are")
     ap.add_argument("--shadow-lights", action="store_true", help="a run of its own: nrdHipPackShadowLights / nrdHipResolveShadowLights for four local lights (1920 x 1080 unless --width / "
                     "--height say otherwise) against the copy rate and the same recipes as torch elementwise operations; adds the `shadow_lights` and `isa_shadow_lights` objects to --out")
+    ap.add_argument("--guides", action="store_true", help="a run of its own: nrdHipPackGuides on RGB32_SFLOAT position planes against the copy rate, next to the four shadow-light "
+                    "calls on planes of the same size, the whole set three times; adds the `guides` and `isa_guides` objects to --out and leaves its other fields as they are")
     args = ap.parse_args()
     default_size = (1920, 1080) if args.shadow_lights else (2560, 1440)
     args.width, args.height = args.width or default_size[0], args.height or default_size[1]
+    if args.guides:
+        return guides_main(args)
     if args.shadow_lights:
         return shadow_lights_main(args)
     if args.check_inputs:
