@@ -5,7 +5,7 @@
 
 #include "NRDHip.h"
 
-#include "../common/pass_constants.h"
+#include "dispatch_list.h" // FamilyOf, ConstantsAs: the family tests and the typed views of the constant blocks
 
 #include <algorithm>
 #include <climits>
@@ -15,6 +15,10 @@
 #include <map>
 #include <set>
 #include <vector>
+
+using nrdhip::ConstantsAs;
+using nrdhip::Family;
+using nrdhip::ShaderOf;
 
 // Rows a tap of REBLUR's Blur / PostBlur can lie from its pixel (kernels_reblur_spatial.hip; reference REBLUR_Common_SpatialFilter.hlsli):
 //   diffuse taps: screen space, |offset| <= blurRadius * skew with skew <= 1 and blurRadius = max( scale * maxBlurRadius * sqrt( areaFactor <= 1 ), minBlurRadius );
@@ -41,16 +45,17 @@ static int ReblurBlurReachRows(float scaledMaxRadius, float minRadius, float unp
 static int PassReachRows(const char* shader, const void* constants, uint32_t constantsSize) {
     if (!strncmp(shader, "Clear_", 6))
         return 0; // the clears of a restart frame: texel-local (the launch covers the whole plane on every rank, which is what a single GPU's plane holds afterwards)
-    if (!strncmp(shader, "RELAX_", 6) && constants && constantsSize >= sizeof(nrdc::RelaxConstants)) {
-        const nrdc::RelaxConstants& c = *(const nrdc::RelaxConstants*)constants;
+    if (const nrdc::RelaxConstants* relax = ConstantsAs<nrdc::RelaxConstants>(Family::RELAX, shader, constants, constantsSize)) {
+        const nrdc::RelaxConstants& c = *relax;
         if (c.gRectSizePrev.x != float(c.gRectSize.x) || c.gRectSizePrev.y != float(c.gRectSize.y))
             return -1; // dynamic resolution step: history rows map to different rows of this frame, no bounded halo -> whole frame
         if (strstr(shader, "_AtrousSmem") || strstr(shader, "_HistoryClamping"))
             return 2; // 5x5 windows
         if (strstr(shader, "_Atrous")) {
-            if (constantsSize < sizeof(nrdc::RelaxAtrousConstants))
+            const nrdc::RelaxAtrousConstants* atrous = ConstantsAs<nrdc::RelaxAtrousConstants>(Family::RELAX, shader, constants, constantsSize);
+            if (!atrous)
                 return -1;
-            const uint32_t step = ((const nrdc::RelaxAtrousConstants*)constants)->gStepSize;
+            const uint32_t step = atrous->gStepSize;
             return (int)(step + (step > 4 ? (step + 3) / 4 : 0)); // +-step taps, shifted by up to step / 4 at the large steps
         }
         if (strstr(shader, "_HistoryFix"))
@@ -61,11 +66,11 @@ static int PassReachRows(const char* shader, const void* constants, uint32_t con
             return 0; // read user inputs only (the pre-pass behind a reconstruction pass: DispatchReachRows) / copy texel to texel (the copy's launch covers the whole plane: a superset)
         return -1;
     }
-    if (!strncmp(shader, "SIGMA_", 6) && constants && constantsSize >= sizeof(nrdc::SigmaConstants)) {
+    if (const nrdc::SigmaConstants* sigma = ConstantsAs<nrdc::SigmaConstants>(Family::SIGMA, shader, constants, constantsSize)) {
         // round 6. Blur / PostBlur: screen-space taps at <= SIGMA_MAX_PIXEL_RADIUS = 32 pixels (skew <= 1; reference SIGMA_Common.hlsli:21-33, SIGMA_Config.hlsli:34),
         // snapped to a texel centre (+ 1), around the 5x5 radius-estimation window (2); TemporalStabilization: 5x5 moments. The tile passes write down-sampled planes (every rank
         // runs them on the whole frame: nrdHipPlanHaloExchange); Copy and SplitScreen work texel to texel.
-        const nrdc::SigmaConstants& c = *(const nrdc::SigmaConstants*)constants;
+        const nrdc::SigmaConstants& c = *sigma;
         if (c.gRectSizePrev.x != c.gRectSize.x || c.gRectSizePrev.y != c.gRectSize.y)
             return -1;
         if (strstr(shader, "_PostBlur") || strstr(shader, "_Blur"))
@@ -76,9 +81,10 @@ static int PassReachRows(const char* shader, const void* constants, uint32_t con
             return 0;
         return -1;
     }
-    if (strncmp(shader, "REBLUR_", 7) != 0 || !constants || constantsSize < sizeof(nrdc::ReblurConstants))
+    const nrdc::ReblurConstants* reblur = ConstantsAs<nrdc::ReblurConstants>(Family::REBLUR, shader, constants, constantsSize);
+    if (!reblur)
         return -1;
-    const nrdc::ReblurConstants& c = *(const nrdc::ReblurConstants*)constants;
+    const nrdc::ReblurConstants& c = *reblur;
     if (c.gRectSizePrev.x != c.gRectSize.x || c.gRectSizePrev.y != c.gRectSize.y)
         return -1; // dynamic resolution step: history rows map to different rows of this frame, no bounded halo -> whole frame
     if (strstr(shader, "_TemporalStabilization"))
@@ -98,7 +104,7 @@ static int PassReachRows(const char* shader, const void* constants, uint32_t con
 
 // Rows above / below a produced pixel at which dispatch i reads the per-frame GUIDE planes (decoded normals, view / world positions): PassReachRows, except for the
 // pre-passes, whose taps read nothing written earlier in the frame (reach 0 for the halo plan) but do read the guides at blur-radius distance. -1 = unknown.
-static int PrePassTapRows(const char* shader, const void* constants);
+static int PrePassTapRows(const char* shader, const void* constants, uint32_t constantsSize);
 int nrdhip::GuideReachRows(const char* shader, const void* constants, uint32_t constantsSize) {
     const int reach = PassReachRows(shader, constants, constantsSize);
     // TemporalAccumulation with a specular signal (REBLUR and RELAX): the curvature estimate's high-parallax tap reads the decoded normals smbParallaxInPixelsMin * (1 + gFramerateScale *
@@ -110,22 +116,21 @@ int nrdhip::GuideReachRows(const char* shader, const void* constants, uint32_t c
         return -1;
     if (reach < 0 || !strstr(shader, "_PrePass"))
         return reach;
-    return PrePassTapRows(shader, constants);
+    return PrePassTapRows(shader, constants, constantsSize);
 }
 
 // Rows a tap of a pre-pass (REBLUR or RELAX) can lie from its pixel. Where they land on planes written earlier in the frame -- the output of a hit-distance reconstruction pass --
 // this is the pass's reach for the halo plan (DispatchReachRows); it always is its reach on the per-frame guide planes (GuideReachRows).
-static int PrePassTapRows(const char* shader, const void* constants) {
+static int PrePassTapRows(const char* shader, const void* constants, uint32_t constantsSize) {
     // the pre-pass taps of both families are SCREEN-space (REBLUR: skew 1 for diffuse, REBLUR_USE_SCREEN_SPACE_SAMPLING_FOR_SPECULAR in the pre-pass; RELAX: pixelUv + rotator *
     // blurRadius): the radius itself bounds them (rounds 2-5 doubled it)
     float radius;
-    if (!strncmp(shader, "RELAX_", 6)) {
-        const nrdc::RelaxConstants& c = *(const nrdc::RelaxConstants*)constants;
-        radius = std::fmax(c.gDiffBlurRadius, c.gSpecBlurRadius);
-    } else {
-        const nrdc::ReblurConstants& c = *(const nrdc::ReblurConstants*)constants;
-        radius = std::fmax(std::fmax(c.gDiffPrepassBlurRadius, c.gSpecPrepassBlurRadius), c.gMinBlurRadius);
-    }
+    if (const nrdc::RelaxConstants* c = ConstantsAs<nrdc::RelaxConstants>(Family::RELAX, shader, constants, constantsSize))
+        radius = std::fmax(c->gDiffBlurRadius, c->gSpecBlurRadius);
+    else if (const nrdc::ReblurConstants* c = ConstantsAs<nrdc::ReblurConstants>(Family::REBLUR, shader, constants, constantsSize))
+        radius = std::fmax(std::fmax(c->gDiffPrepassBlurRadius, c->gSpecPrepassBlurRadius), c->gMinBlurRadius);
+    else
+        return -1; // (not reached: both callers come here with a reach PassReachRows took from the same block)
     return (int)std::ceil(std::fmax(radius, 1.0f)) + 2; // (RELAX: a zero hit distance widens the radius to at least one pixel)
 }
 
@@ -133,9 +138,9 @@ static int PrePassTapRows(const char* shader, const void* constants) {
 // gather from that pass's output, a full-resolution plane written earlier in the frame, at blur-radius distance (rounds 2-5 ran such frames unsharded).
 static int DispatchReachRows(const nrd::InstanceDesc& idesc, const nrd::DispatchDesc* descs, uint32_t i) {
     const nrd::DispatchDesc& d = descs[i];
-    if (d.pipelineIndex >= idesc.pipelinesNum)
-        return -1;
-    const char* shader = idesc.pipelines[d.pipelineIndex].shaderFileName;
+    const char* shader = ShaderOf(idesc, d);
+    if (!*shader)
+        return -1; // a pipeline the instance does not have
     const int reach = PassReachRows(shader, d.constantBufferData, d.constantBufferDataSize);
     if (reach != 0 || !strstr(shader, "_PrePass"))
         return reach;
@@ -146,9 +151,8 @@ static int DispatchReachRows(const nrd::InstanceDesc& idesc, const nrd::Dispatch
         for (uint32_t j = 0; j < i; j++)
             for (uint32_t w = 0; w < descs[j].resourcesNum; w++) {
                 const nrd::ResourceDesc& out = descs[j].resources[w];
-                if (out.descriptorType == nrd::DescriptorType::STORAGE_TEXTURE && out.type == in.type && out.indexInPool == in.indexInPool && descs[j].pipelineIndex < idesc.pipelinesNum &&
-                    strstr(idesc.pipelines[descs[j].pipelineIndex].shaderFileName, "_HitDistReconstruction"))
-                    return PrePassTapRows(shader, d.constantBufferData);
+                if (out.descriptorType == nrd::DescriptorType::STORAGE_TEXTURE && out.type == in.type && out.indexInPool == in.indexInPool && strstr(ShaderOf(idesc, descs[j]), "_HitDistReconstruction"))
+                    return PrePassTapRows(shader, d.constantBufferData, d.constantBufferDataSize);
             }
     }
     return reach;
@@ -167,7 +171,7 @@ void nrdhip::OwnedRowRanges(const nrd::Instance& instance, const nrd::DispatchDe
             margin = -1; // whole frame from here backwards
             continue;
         }
-        if (d.pipelineIndex < idesc.pipelinesNum && !strncmp(idesc.pipelines[d.pipelineIndex].shaderFileName, "SIGMA_Copy", 10))
+        if (!strncmp(ShaderOf(idesc, d), "SIGMA_Copy", 10))
             continue; // its output is last frame's history, which TemporalStabilization samples at the REPROJECTED position: the texel-to-texel copy (10 B/px) covers the whole frame, the margin walks on
         rowBegin[i] = std::max(ownedRowBegin - margin, 0);
         rowEnd[i] = ownedRowEnd == INT_MAX ? INT_MAX : ownedRowEnd + margin;
@@ -276,7 +280,7 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPlanHaloExchang
             const int w = it == lastWrite.end() ? -1 : it->second;
             // a plane written by SIGMA's Copy IS last frame's history (SIGMA_Copy.hlsli: previous output -> HISTORY, texel to texel): TemporalStabilization samples it at
             // the reprojected position, so its readers need the motion bound like readers of a carried-over plane
-            const bool historyCopy = w >= 0 && descs[w].pipelineIndex < idesc.pipelinesNum && !strncmp(idesc.pipelines[descs[w].pipelineIndex].shaderFileName, "SIGMA_Copy", 10);
+            const bool historyCopy = w >= 0 && !strncmp(ShaderOf(idesc, descs[w]), "SIGMA_Copy", 10);
             if (historyCopy && segOf[w] == segOf[i])
                 return fallback(); // (never with the default threshold: Blur's reach starts a segment between the two)
             if (w >= 0 && segOf[w] == segOf[i]) {
@@ -296,7 +300,7 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPlanHaloExchang
                 slot = std::max(slot, h);
             }
         }
-        const bool isClear = d.pipelineIndex < idesc.pipelinesNum && !strncmp(idesc.pipelines[d.pipelineIndex].shaderFileName, "Clear_", 6);
+        const bool isClear = !strncmp(ShaderOf(idesc, d), "Clear_", 6);
         for (const Key& key : writes) {
             lastWrite[key] = (int)i;
             if (isClear)

@@ -1,5 +1,6 @@
-// What the HIP executor (csrc/hip/executor.hip) calls of the host-only sharding planner (halo_plan.cpp); the planner's public entry points --
-// nrdHipGetDispatchReach, nrdHipPlanHaloExchange -- are declared in include/NRDHip.h.
+// What the HIP executor calls of the host-only sharding planner (halo_plan.cpp): csrc/hip/executor.hip asks GuideReachRows when it plans the guide rows of a range and
+// OwnedRowRanges for nrdHipSetOwnedRows. The planner's public entry points -- nrdHipGetDispatchReach, nrdHipPlanHaloExchange -- are declared in include/NRDHip.h; what a
+// dispatch list says (family of a pass, its typed constant block) both read through dispatch_list.h.
 #pragma once
 
 #include "NRD.h"
