@@ -17,6 +17,7 @@
 // wave-wide vote -- no LDS, no atomics.
 #include "passes.h"
 #include "reblur_device.h"
+#include "../host/tap_index.h"
 
 namespace nrdhip {
 
@@ -78,6 +79,7 @@ struct SpatialCtx {
     // checkerboard resolve of the pre-pass (reference REBLUR_PrePass.hlsli:43-56): neighbour columns in the half-width input + their weights
     int cbX0, cbX1;
     float2 wc;
+    float tapPitch; // FR == 3: texels per row of every plane a tap reads
 };
 
 // ---- one tap of the Poisson kernels: position -> texel, guides of that texel ------------------------------------------------------------------
@@ -92,6 +94,7 @@ struct TapGuides {
     float NvXvs;      // dot(centre view-space normal, Xvs) (the argument of the plane-distance weight)
     float roughnessS, materialIDs, zs;
     int2 ts;          // texel of the signal planes
+    uint32_t ti;      // FR == 3: its linear index, the same in every plane of the pass
     float2 uv;        // generic path only
 };
 
@@ -104,7 +107,16 @@ NRD_D TapGuides FetchTapGuidesFullRect(const ReblurCB& c, const SpatialCtx& s, f
     // clamp in the float domain (one v_med3_f32 per axis; the snapped coordinate is an integer-valued float): inside <=> the clamp changed nothing
     const float cxf = __builtin_amdgcn_fmed3f(k.x, 0.0f, rectSize.x - 1.0f), cyf = __builtin_amdgcn_fmed3f(k.y, 0.0f, rectSize.y - 1.0f);
     t.w = (cxf == k.x && cyf == k.y) ? 1.0f : 0.0f;
-    t.ts = make_int2((int)cxf, (int)cyf);
+    // FR == 3 (NRD_SPATIAL_TAP_INDEX): every plane the tap reads has the same pitch IN TEXELS and fewer than 2^24 of them (the launcher checks: csrc/host/tap_index.h), so
+    // the texel's linear index is one exact fma of the clamped floats and one conversion, and each plane's byte offset is that index times its texel size -- instead of two
+    // conversions and one 24-bit multiply-add PER PLANE (guide, signal, PostBlur's viewZ). Same texels, same values.
+    constexpr bool INDEXED = FR == 3;
+    t.ti = 0u;
+    t.ts = make_int2(0, 0);
+    if (INDEXED)
+        t.ti = (uint32_t)__builtin_fmaf(cyf, s.tapPitch, cxf);
+    else
+        t.ts = make_int2((int)cxf, (int)cyf);
     // Guides of the texel: the per-frame (normal, viewZ) guide plane (passes.h viewPos) makes a diffuse tap ONE 16-byte guide load; a specular tap adds the
     // 4 bytes that hold the roughness / material bits of the decoded-normal texel (from their compact copy, passes.h roughnessWord). The view position is re-derived from viewZ. Fetching it as a second
     // 16-byte guide texel instead (r02_b / r02_c A/B) saved 19 % of the instructions and bought nothing: the extra 12 bytes per tap through the L1 /
@@ -117,7 +129,7 @@ NRD_D TapGuides FetchTapGuidesFullRect(const ReblurCB& c, const SpatialCtx& s, f
     const bool materials = FR == 1 && compareMaterials;
     uint32_t bits = 0u;
     {
-        const uint32_t offset = TexelOffset(gIn_ViewPos, t.ts.x, t.ts.y, 16u, true); // same layout as the decoded normals (launcher check)
+        const uint32_t offset = INDEXED ? t.ti * 16u : TexelOffset(gIn_ViewPos, t.ts.x, t.ts.y, 16u, true); // same layout as the decoded normals (launcher check)
         const float4 g = *(const float4*)(gIn_ViewPos.ptr + offset);
         t.Ns = Xyz(g);
         t.zs = g.w;
@@ -129,7 +141,7 @@ NRD_D TapGuides FetchTapGuidesFullRect(const ReblurCB& c, const SpatialCtx& s, f
     // reference weighs the tap by. Within the range the two planes agree (Blur wrote the texel this frame). 4 bytes more per tap; re-reading only where the guide says "beyond
     // the range" is the same value for fewer bytes but a divergent branch per tap: 78 -> 95 VGPRs in the benchmarked kernel against 78 -> 79 (profiles/HISTORY.md).
     if (MODE == POST_BLUR)
-        t.zs = UnpackViewZ(c, LoadR32F(gIn_ViewZ, t.ts.x, t.ts.y));
+        t.zs = UnpackViewZ(c, INDEXED ? *(const float*)(gIn_ViewZ.ptr + t.ti * 4u) : LoadR32F(gIn_ViewZ, t.ts.x, t.ts.y));
     const float2 uvc = (k + 0.5f) * rectSizeInv; // centre of the snapped pixel; equals the clamped texel's centre whenever the tap counts (t.w != 0)
     t.Xvs = ReconstructViewPosition(uvc, ToF4(c.gFrustum), t.zs, 0.0f); // perspective only (CheckSupported); dead code unless the caller needs the position
     t.NvXvs = t.zs * (k.x * s.geo.x + (k.y * s.geo.y + s.geo.z));
@@ -171,6 +183,20 @@ NRD_D TapGuides FetchTapGuides(const ReblurCB& c, const SpatialCtx& s, float2 uv
     t.w = IsInScreenNearest(uv);
     t.uv = uv;
     return t;
+}
+
+// the signal texels of a tap
+template <int KIND, int FR>
+NRD_D typename ReblurSignal<KIND>::type LoadTapSignalOrZero(const Plane& p, const TapGuides& t, bool zero) {
+    if (FR == 3)
+        return ReblurSignal<KIND>::LoadOrZeroAt(p, t.ti, zero);
+    return ReblurSignal<KIND>::LoadOrZero(p, t.ts.x, t.ts.y, zero);
+}
+template <int FR>
+NRD_D float4 LoadTapSh(const Plane& p, const TapGuides& t) {
+    if (FR == 3)
+        return DecodeRGBA16Float(*(const uint2*)(p.ptr + t.ti * 8u));
+    return LoadRGBA16F(p, t.ts.x, t.ts.y);
 }
 
 // PERF = REBLUR_PERFORMANCE_MODE (reference REBLUR_Config.hlsli:196-238): 6 taps of g_Special6 instead of 8 of g_Special8, and
@@ -241,14 +267,13 @@ NRD_D typename ReblurSignal<KIND>::type DiffuseSpatialFilterTaps(const ReblurCB&
     skew = skew * (rectSizeInv * blurRadius);
     float4 scaledRotator = ScaleRotator(s.rotator, skew);
     // material IDs are 0..3: with a minimum material >= 3 every comparison holds (the library default is 4 = "off")
-    const bool compareMaterials = FR != 2 && c.gDiffMinMaterial < 3.0f;
+    const bool compareMaterials = FR < 2 && c.gDiffMinMaterial < 3.0f;
 
 #pragma unroll
     for (int n = 0; n < (PERF ? 6 : 8); n++) {
         float3 offset = PERF ? F3(g_Special6[n][0], g_Special6[n][1], g_Special6[n][2]) : F3(g_Special8[n][0], g_Special8[n][1], g_Special8[n][2]);
         const float2 uvTap = s.pixelUv + RotateVector(scaledRotator, F2(offset.x, offset.y));
         TapGuides t = FetchTapGuides<MODE, CB, FR, false>(c, s, uvTap, gIn_Diff, gIn_ViewZ, gIn_Normal_Roughness, gIn_ViewPos, c.gDiffCheckerboard, (uint32_t)n, compareMaterials);
-        const int2 ts = t.ts;
 
         float angle = AcosApprox(Dot(s.N, t.Ns));
 
@@ -258,7 +283,7 @@ NRD_D typename ReblurSignal<KIND>::type DiffuseSpatialFilterTaps(const ReblurCB&
             w *= CompareMaterials(s.materialID, t.materialIDs, c.gDiffMinMaterial) ? 1.0f : 0.0f;
         w *= ComputeWeight(angle, normalWeightParam, 0.0f);
 
-        S smp = Sig::LoadOrZero(gIn_Diff, ts.x, ts.y, w == 0.0f);
+        S smp = LoadTapSignalOrZero<KIND, FR>(gIn_Diff, t, w == 0.0f);
 
         w *= Lerp(minHitDistWeight, 1.0f, ComputeExponentialWeight(ExtractHitDist(smp), hitDistanceWeightParams.x, hitDistanceWeightParams.y));
         w *= PoissonGaussianWeight<PERF>(n);
@@ -266,7 +291,7 @@ NRD_D typename ReblurSignal<KIND>::type DiffuseSpatialFilterTaps(const ReblurCB&
         sum += w;
         diff = Mad(smp, w, diff);
         if (SH) {
-            float4 sh = LoadRGBA16F(gIn_DiffSh, ts.x, ts.y);
+            float4 sh = LoadTapSh<FR>(gIn_DiffSh, t);
             sh = Select(w == 0.0f, F4(0.0f), sh);
             diffSh = Mad(sh, w, diffSh);
         }
@@ -363,7 +388,7 @@ NRD_D typename ReblurSignal<KIND>::type SpecularSpatialFilterTaps(const ReblurCB
         minHitDistWeight *= Sqrt(specNonLinearAccumSpeed);
 
     const float2 rectSizeInv = ToF2(c.gRectSizeInv);
-    const bool compareMaterials = FR != 2 && c.gSpecMinMaterial < 3.0f; // see the diffuse filter
+    const bool compareMaterials = FR < 2 && c.gSpecMinMaterial < 3.0f; // see the diffuse filter
 
     constexpr bool SCREEN_SPACE = MODE == PRE_BLUR || PERF; // REBLUR_USE_SCREEN_SPACE_SAMPLING_FOR_SPECULAR
     float4 scaledRotator = F4(0.0f);
@@ -395,7 +420,6 @@ NRD_D typename ReblurSignal<KIND>::type SpecularSpatialFilterTaps(const ReblurCB
         else
             uv = KernelSampleUv(kernelProjection, offset.x, offset.y);
         TapGuides t = FetchTapGuides<MODE, CB, FR, true>(c, s, uv, gIn_Spec, gIn_ViewZ, gIn_Normal_Roughness, gIn_ViewPos, c.gSpecCheckerboard, (uint32_t)n, compareMaterials);
-        const int2 ts = t.ts;
         const float zs = t.zs;
         const float3 Xvs = t.Xvs;
         const float4 Ns = F4(t.Ns, t.roughnessS);
@@ -409,7 +433,7 @@ NRD_D typename ReblurSignal<KIND>::type SpecularSpatialFilterTaps(const ReblurCB
         w *= ComputeWeight(angle, normalWeightParam, 0.0f);
         w *= ComputeWeight(Ns.w, roughnessWeightParams.x, roughnessWeightParams.y);
 
-        S smp = Sig::LoadOrZero(gIn_Spec, ts.x, ts.y, w == 0.0f);
+        S smp = LoadTapSignalOrZero<KIND, FR>(gIn_Spec, t, w == 0.0f);
 
         if (MODE == PRE_BLUR) {
             float hs = ExtractHitDist(smp) * GetHitDistanceNormalization(zs, hitDistParams, Ns.w);
@@ -429,7 +453,7 @@ NRD_D typename ReblurSignal<KIND>::type SpecularSpatialFilterTaps(const ReblurCB
         sum += w;
         spec = Mad(smp, w, spec);
         if (SH) {
-            float4 sh = LoadRGBA16F(gIn_SpecSh, ts.x, ts.y);
+            float4 sh = LoadTapSh<FR>(gIn_SpecSh, t);
             sh = Select(w == 0.0f, F4(0.0f), sh);
             specSh.x += sh.x * w, specSh.y += sh.y * w, specSh.z += sh.z * w;
         }
@@ -505,7 +529,8 @@ struct SpatialPlanes {
     Plane inDiffSh, inSpecSh, outDiffSh, outSpecSh, outDiffShCopy, outSpecShCopy; // SH family
 };
 
-// FR: 0 = generic taps; 1 = rect == resource, no checkerboard, (normal, viewZ) guide plane present; 2 = 1 without material tests (FetchTapGuides)
+// FR: 0 = generic taps; 1 = rect == resource, no checkerboard, (normal, viewZ) guide plane present; 2 = 1 without material tests (FetchTapGuides);
+// 3 = 2 with one linear texel index per tap for all planes (FetchTapGuidesFullRect)
 template <SpatialMode MODE, bool DIFF, bool SPEC, bool NO_TS, bool PERF, int KIND, bool SH, bool CB, int FR>
 __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_SPATIAL) void ReblurSpatialKernel(ReblurCB c, SpatialPlanes P, RowRange rr) {
     typedef ReblurSignal<KIND> Sig;
@@ -536,6 +561,7 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_SPATIAL) void Rebl
     if (!MakeSpatialCtx(c, px, py, UnpackViewZ(c, viewZpacked), P.decodedNR, ToF4(rot), s))
         return;
 
+    s.tapPitch = FR == 3 ? float(P.viewPos.pitch >> 4) : 0.0f; // (uniform; FR == 3: the launcher has checked that this is every tap plane's pitch in texels)
     if (MODE != PRE_BLUR)
         s.data1 = LoadData1<DIFF, SPEC>(P.data1, px, py);
 
@@ -607,6 +633,30 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_SPATIAL) void Rebl
 static bool ForceGenericTaps() {
     const char* v = getenv("NRD_HIP_GENERIC_TAPS");
     return v && atoi(v) != 0;
+}
+
+// NRD_SPATIAL_TAP_INDEX (A/B switch, tools/build_variant.py; 0 = the FR == 3 variants are neither launched nor compiled): the planes a "full rect" tap reads -- the (normal, viewZ)
+// guide at 16 bytes per texel, the signals, their SH planes, PostBlur's own viewZ (the roughness word is a quarter of the guide by construction: MakeNormalRoughnessGuide) --
+// can be addressed by one texel index (csrc/host/tap_index.h). Not in the L1-resident experiment builds, which redirect loads inside TexelOffset.
+#ifndef NRD_SPATIAL_TAP_INDEX
+#define NRD_SPATIAL_TAP_INDEX (!NRD_EXPERIMENT_L1_RESIDENT)
+#endif
+// NRD_HIP_TAP_INDEX=0: never take the FR == 3 variants (tests/test_reblur_tap_index.py holds the two forms of the offset against each other byte for byte in child processes)
+static bool TapIndexAllowed() {
+    const char* v = getenv("NRD_HIP_TAP_INDEX");
+    return !v || atoi(v) != 0;
+}
+template <SpatialMode MODE, bool DIFF, bool SPEC, int KIND, bool SH>
+static bool TapPlanesShareTexelPitch(const SpatialPlanes& P) {
+    const uint32_t signalBytes = KIND == SIGNAL_OCCLUSION ? 2u : 8u; // R16_UNORM; RGBA16_SFLOAT / RGBA16_SNORM
+    uint32_t pitch[6], bytes[6], n = 0;
+    pitch[n] = P.viewPos.pitch, bytes[n++] = 16u;
+    if (DIFF) pitch[n] = P.inDiff.pitch, bytes[n++] = signalBytes;
+    if (SPEC) pitch[n] = P.inSpec.pitch, bytes[n++] = signalBytes;
+    if (DIFF && SH) pitch[n] = P.inDiffSh.pitch, bytes[n++] = 8u;
+    if (SPEC && SH) pitch[n] = P.inSpecSh.pitch, bytes[n++] = 8u;
+    if (MODE == POST_BLUR) pitch[n] = P.viewZ.pitch, bytes[n++] = 4u;
+    return TapIndexAddressesAllPlanes(P.viewPos.w, P.viewPos.h, pitch, bytes, n);
 }
 
 static const char* CheckSupported(const ReblurCB& c) {
@@ -686,6 +736,10 @@ static const char* LaunchSpatial(const PassArgs& a) {
     const bool fullRect = c.gResolutionScale.x == 1.0f && c.gResolutionScale.y == 1.0f && c.gRectSizeMinusOne.x + 1 == P.decodedNR.nz.w &&
                           c.gRectSizeMinusOne.y + 1 == P.decodedNR.nz.h && P.viewZ.w == P.decodedNR.nz.w && P.viewZ.h == P.decodedNR.nz.h && !ForceGenericTaps();
     const bool materials = (DIFF && c.gDiffMinMaterial < 3.0f) || (SPEC && c.gSpecMinMaterial < 3.0f);
+    if (NRD_SPATIAL_TAP_INDEX && fullRect && !materials && TapIndexAllowed() && TapPlanesShareTexelPitch<MODE, DIFF, SPEC, KIND, SH>(P)) {
+        LaunchPass(a, (ReblurSpatialKernel<MODE, DIFF, SPEC, NO_TS, PERF, KIND, SH, false, NRD_SPATIAL_TAP_INDEX ? 3 : 2>), g.grid, dim3(TILE_X * TILE_Y), c, P, rows);
+        return nullptr;
+    }
     if (fullRect && !materials)
         LaunchPass(a, (ReblurSpatialKernel<MODE, DIFF, SPEC, NO_TS, PERF, KIND, SH, false, 2>), g.grid, dim3(TILE_X * TILE_Y), c, P, rows);
     else if (fullRect)

@@ -181,6 +181,8 @@ NRD_D KernelProjection MakeKernelProjection(const float* m, float3 X, float3 T, 
     k.v = F3(m[0] * Br.x + m[4] * Br.y + m[8] * Br.z, m[1] * Br.x + m[5] * Br.y + m[9] * Br.z, m[3] * Br.x + m[7] * Br.y + m[11] * Br.z);
     return k;
 }
+// (the two Div are ONE v_rcp_f32 in the listing: the empty asm in front of Rcp is not volatile, so the compiler merges the two reciprocals of the same value --
+// writing the shared reciprocal out by hand leaves the instruction stream as it is, profiles/HISTORY.md)
 NRD_D float2 KernelSampleUv(const KernelProjection& k, float ox, float oy) {
     float3 clip = Mad(k.v, oy, Mad(k.u, ox, k.c0));
     clip.x = Div(clip.x, clip.z);
@@ -897,11 +899,15 @@ struct ReblurSignal<SIGNAL_RADIANCE> {
 #if NRD_EXPERIMENT_LEGACY_DENANIFY // A/B builds only (tools/build_variant.py): the selection after the conversions, as up to round 3
         return Select(zero, F4(0.0f), LoadRGBA16F(p, x, y));
 #endif
-        uint2 raw = *TexelPtr<const uint2>(p, x, y);
+        return RawOrZero(*TexelPtr<const uint2>(p, x, y), zero);
+    }
+    static NRD_D float4 RawOrZero(uint2 raw, bool zero) {
         raw.x = zero ? 0u : raw.x;
         raw.y = zero ? 0u : raw.y;
         return F4(HalfBitsToFloat((uint16_t)(raw.x & 0xFFFFu)), HalfBitsToFloat((uint16_t)(raw.x >> 16)), HalfBitsToFloat((uint16_t)(raw.y & 0xFFFFu)), HalfBitsToFloat((uint16_t)(raw.y >> 16)));
     }
+    // the same by linear texel index (a plane whose pitch is a whole number of texels: kernels_reblur_spatial.hip, FR == 3)
+    static NRD_D float4 LoadOrZeroAt(const Plane& p, uint32_t texel, bool zero) { return RawOrZero(*(const uint2*)(p.ptr + texel * 8u), zero); }
     static NRD_D void Store(const Plane& p, int x, int y, float4 v) { StoreRGBA16F(p, x, y, v); }
     static NRD_D float4 WithHitDist(float4 s, float hitDist) { return F4(s.x, s.y, s.z, hitDist); }
     static NRD_D float4 FetchHistory(const HistoryFilter& h, const Plane& tex) { return FetchHistoryRGBA16F(h, tex); }
@@ -936,6 +942,7 @@ struct ReblurSignal<SIGNAL_OCCLUSION> {
     static NRD_D float Zero() { return 0.0f; }
     static NRD_D float Load(const Plane& p, int x, int y) { return LoadR16Unorm(p, x, y); }
     static NRD_D float LoadOrZero(const Plane& p, int x, int y, bool zero) { return zero ? 0.0f : LoadR16Unorm(p, x, y); }
+    static NRD_D float LoadOrZeroAt(const Plane& p, uint32_t texel, bool zero) { return zero ? 0.0f : NRD_DIV_65535(float(*(const uint16_t*)(p.ptr + texel * 2u))); }
     static NRD_D void Store(const Plane& p, int x, int y, float v) { StoreR16Unorm(p, x, y, v); }
     static NRD_D float WithHitDist(float, float hitDist) { return hitDist; }
     static NRD_D float FetchHistory(const HistoryFilter& h, const Plane& tex) {
@@ -958,6 +965,7 @@ struct ReblurSignal<SIGNAL_DIRECTIONAL_OCCLUSION> {
     static NRD_D DirOcc Zero() { return MakeDirOcc(F4(0.0f)); }
     static NRD_D DirOcc Load(const Plane& p, int x, int y) { return MakeDirOcc(LoadRGBA16Snorm(p, x, y)); }
     static NRD_D DirOcc LoadOrZero(const Plane& p, int x, int y, bool zero) { return Select(zero, Zero(), Load(p, x, y)); }
+    static NRD_D DirOcc LoadOrZeroAt(const Plane& p, uint32_t texel, bool zero) { return Select(zero, Zero(), MakeDirOcc(DecodeRGBA16Snorm(*(const uint2*)(p.ptr + texel * 8u)))); }
     static NRD_D void Store(const Plane& p, int x, int y, DirOcc s) { StoreRGBA16Snorm(p, x, y, s.v); }
     static NRD_D DirOcc WithHitDist(DirOcc s, float hitDist) { return MakeDirOcc(F4(s.v.x, s.v.y, s.v.z, hitDist)); }
     static NRD_D DirOcc FetchHistory(const HistoryFilter& h, const Plane& tex) {
