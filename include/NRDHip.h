@@ -65,6 +65,33 @@ uint32_t nrdHipBindResource(NrdHipExecutor* executor, uint32_t resourceType, con
 // For tooling and parity tests (history inspection); the memory stays owned by the executor.
 uint32_t nrdHipGetPoolPlane(NrdHipExecutor* executor, uint32_t resourceType, uint32_t indexInPool, NrdHipPlaneDesc* plane);
 
+// ---- Layered executor: SIGMA for many lights, N shadow layers in one pass chain ------------------------------------------------------------------------------
+// One executor over ONE instance of SIGMA_SHADOW and / or SIGMA_SHADOW_TRANSLUCENCY denoises layersNum (1 .. NRD_HIP_MAX_SHADOW_LIGHTS) shadow layers -- one per light -- per
+// nrdHipDenoise: every dispatch of the list is still ONE launch, whose grid's z extent is layersNum (Clear_* dispatches included). This is possible because the layers differ in
+// nothing but the planes they touch: every constant of a SIGMA pass comes from CommonSettings and SigmaSettings, and the one per-light field, lightDirection
+// (gLightDirectionView), is filled by the host and read by no pass in this version (the reference uses it only with SIGMA_USE_SCREEN_SPACE_SAMPLING == 0; its config sets 1).
+// So there are no per-layer constants. layersNum == 1 is exactly nrdHipCreateExecutor: the same pool, the same kernels, the same bytes. With layersNum > 1 an instance that
+// holds any pass other than SIGMA_* / Clear_* returns UNSUPPORTED (message on stderr); layersNum of 0 or above the maximum returns INVALID_ARGUMENT.
+//   Pool: every permanent and transient pool plane exists once per layer, layer l starting l x (the plane's 256-byte aligned size) behind layer 0; the whole arena is zero-filled
+// once; nrdHipGetPoolMemoryUsage reports the totals; nrdHipGetPoolPlane describes layer 0 and nrdHipGetPoolPlaneLayer any layer (layer >= layersNum: INVALID_ARGUMENT). A
+// caller-provided arena (nrdHipCreateExecutorWithArena) stays unlayered.
+//   Slots: IN_PENUMBRA, IN_TRANSLUCENCY and OUT_SHADOW_TRANSLUCENCY are per layer. On an executor with layersNum > 1 they are bound with nrdHipBindResourceLayers only (a plain
+// nrdHipBindResource of one of them returns INVALID_ARGUMENT and names the slot): `plane` describes layer 0 under the formats and limits of nrdHipBindResource, layer l is
+// data + l x layerBytes (64-bit: the stack may exceed 4 GiB, a layer may not), layerBytes >= rowPitchBytes x height and a multiple of 4 -- the light-layer rule of
+// nrdHipPackShadowLights, whose stacks bind as they are. IN_VIEWZ, IN_NORMAL_ROUGHNESS and IN_MV are shared: bound with nrdHipBindResource, one plane read by all layers.
+// nrdHipBindResourceLayers on a shared slot, on an executor without layers or with a bad stride returns INVALID_ARGUMENT. Nothing is bound or enqueued on any error.
+//   Execution: nrdHipDenoise, nrdHipExecuteDispatches and nrdHipExecuteDispatchRange (NULL row arrays) work as on any executor -- all-or-nothing pre-flight, graph mode, profiling
+// (one launch per pass), dynamic resolution (only the shared guide planes get rect-at-origin twins); the word of nrdHipSetHistoryReachWord receives the maximum over the layers.
+// Refused with UNSUPPORTED + nrdHipGetLastError, nothing enqueued: a row restriction (nrdHipSetOwnedRows with less than the whole frame, non-NULL row arrays), nrdHipCheckInputs
+// and nrdHipCheckInputsAsync (audit a layer through an unlayered executor), any pass in a list that is neither SIGMA_* nor Clear_*.
+//   Contract: after any sequence of frames, layer l of OUT_SHADOW_TRANSLUCENCY and of every pool plane holds byte for byte what a separate unlayered executor over its own instance
+// holds that was fed the same settings and shared guides with layer l's penumbra, translucency and output planes bound -- temporal stabilisation per light included, which the
+// one-instance loop over the lights cannot have. Layers never read each other; the bytes between the layers of a user stack are never written.
+uint32_t nrdHipCreateExecutorLayered(void* instance, uint16_t resourceWidth, uint16_t resourceHeight, uint32_t layersNum, void* hipStream, NrdHipExecutor** executor);
+uint32_t nrdHipBindResourceLayers(NrdHipExecutor* executor, uint32_t resourceType, const NrdHipPlaneDesc* plane, uint64_t layerBytes);
+uint32_t nrdHipGetPoolPlaneLayer(NrdHipExecutor* executor, uint32_t resourceType, uint32_t indexInPool, uint32_t layer, NrdHipPlaneDesc* plane);
+uint32_t nrdHipGetLayersNum(const NrdHipExecutor* executor, uint32_t* layersNum);
+
 // Executes a dispatch list obtained from nrd::GetComputeDispatches on the executor's stream, in order.
 // "dispatchDescs" is a const nrd::DispatchDesc*. All-or-nothing: the whole list is checked first (a HIP kernel exists for every pass, all
 // resources are bound, every pass accepts its constants) and an error (UNSUPPORTED / INVALID_ARGUMENT + nrdHipGetLastError) is returned

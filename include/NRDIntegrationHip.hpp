@@ -29,11 +29,22 @@ namespace nrd {
 
 // One entry per ResourceType slot (the two pool pseudo-slots excluded, as in the reference). Zero-initialise; fill the slots the
 // requested denoisers need (NRDDescs.h lists them per denoiser).
-typedef std::array<NrdHipPlaneDesc, (size_t)ResourceType::MAX_NUM - 2> UserPoolHip;
+// With an executor of several layers (IntegrationHipCreationDesc::layersNum > 1) a per-layer slot -- IN_PENUMBRA, IN_TRANSLUCENCY, OUT_SHADOW_TRANSLUCENCY -- holds a stack of
+// planes: its entry describes layer 0 and layerBytes[ slot ] is the distance in bytes from one layer to the next (NRDHip.h nrdHipBindResourceLayers); 0 = a plain plane.
+struct UserPoolHip : std::array<NrdHipPlaneDesc, (size_t)ResourceType::MAX_NUM - 2> {
+    std::array<uint64_t, (size_t)ResourceType::MAX_NUM - 2> layerBytes = {};
+};
 
 inline void IntegrationHip_SetResource(UserPoolHip& pool, ResourceType slot, const NrdHipPlaneDesc& plane) {
     NRD_INTEGRATION_ASSERT(plane.data != nullptr, "Invalid plane!");
     pool[(size_t)slot] = plane;
+    pool.layerBytes[(size_t)slot] = 0;
+}
+
+inline void IntegrationHip_SetResourceLayers(UserPoolHip& pool, ResourceType slot, const NrdHipPlaneDesc& layer0, uint64_t layerBytes) {
+    NRD_INTEGRATION_ASSERT(layer0.data != nullptr && layerBytes != 0, "Invalid stack of planes!");
+    pool[(size_t)slot] = layer0;
+    pool.layerBytes[(size_t)slot] = layerBytes;
 }
 
 struct IntegrationHipCreationDesc {
@@ -44,6 +55,9 @@ struct IntegrationHipCreationDesc {
     // Optional caller-owned pool memory ("NRD allocates no GPU memory"): at least nrdHipGetArenaSize() bytes, 256-byte aligned.
     void* arena = nullptr;
     uint64_t arenaSize = 0;
+    // SIGMA for many lights (NRDHip.h "layered executor"): > 1 = that many shadow layers, one per light, denoised by one pass chain of an instance of SIGMA denoisers only.
+    // The pool then belongs to the library (not with "arena"), and the per-layer slots of the user pool are stacks (IntegrationHip_SetResourceLayers).
+    uint32_t layersNum = 1;
 };
 
 class IntegrationHip {
@@ -56,8 +70,9 @@ public:
         NRD_INTEGRATION_ASSERT(m_Instance == nullptr, "Already initialized! Did you forget to call 'Destroy'?");
         if (CreateInstance(instanceCreationDesc, m_Instance) != Result::SUCCESS)
             return false;
-        uint32_t r = desc.arena ? nrdHipCreateExecutorWithArena(m_Instance, desc.resourceWidth, desc.resourceHeight, desc.hipStream, desc.arena, desc.arenaSize, &m_Executor)
-                                : nrdHipCreateExecutor(m_Instance, desc.resourceWidth, desc.resourceHeight, desc.hipStream, &m_Executor);
+        uint32_t r = desc.arena && desc.layersNum != 1 ? (uint32_t)Result::UNSUPPORTED // (a caller-provided arena stays unlayered)
+                     : desc.arena ? nrdHipCreateExecutorWithArena(m_Instance, desc.resourceWidth, desc.resourceHeight, desc.hipStream, desc.arena, desc.arenaSize, &m_Executor)
+                                  : nrdHipCreateExecutorLayered(m_Instance, desc.resourceWidth, desc.resourceHeight, desc.layersNum, desc.hipStream, &m_Executor);
         if (r != (uint32_t)Result::SUCCESS) {
             DestroyInstance(*m_Instance);
             m_Instance = nullptr;
@@ -95,10 +110,8 @@ public:
     // supported by this build or a required slot is not bound -- nothing is launched in that case.
     inline bool Denoise(const Identifier* denoisers, uint32_t denoisersNum, const UserPoolHip& userPool) {
         NRD_INTEGRATION_ASSERT(m_Executor != nullptr, "Uninitialized! Did you forget to call 'Initialize'?");
-        for (size_t slot = 0; slot < userPool.size(); slot++) {
-            if (userPool[slot].data && nrdHipBindResource(m_Executor, (uint32_t)slot, &userPool[slot]) != (uint32_t)Result::SUCCESS)
-                return false;
-        }
+        if (!BindPool(userPool))
+            return false;
         if (m_CheckedDispatches && m_CheckedIdentifiers == std::vector<Identifier>(denoisers, denoisers + denoisersNum)) {
             // CheckInputs fetched this frame's list already (GetComputeDispatches advances the instance's ping-pong state: once per frame): execute that very list
             const DispatchDesc* descs = m_CheckedDispatches;
@@ -190,13 +203,24 @@ public:
 private:
     IntegrationHip(const IntegrationHip&) = delete;
 
+    // every non-null entry of the pool: a stack of per-layer planes where the pool gives a layer stride, a plain plane otherwise
+    inline bool BindPool(const UserPoolHip& userPool) {
+        for (size_t slot = 0; slot < userPool.size(); slot++) {
+            if (!userPool[slot].data)
+                continue;
+            const uint32_t r = userPool.layerBytes[slot] ? nrdHipBindResourceLayers(m_Executor, (uint32_t)slot, &userPool[slot], userPool.layerBytes[slot])
+                                                         : nrdHipBindResource(m_Executor, (uint32_t)slot, &userPool[slot]);
+            if (r != (uint32_t)Result::SUCCESS)
+                return false;
+        }
+        return true;
+    }
+
     inline bool FetchForCheck(const Identifier* denoisers, uint32_t denoisersNum, const UserPoolHip& userPool) {
         NRD_INTEGRATION_ASSERT(m_Executor != nullptr, "Uninitialized! Did you forget to call 'Initialize'?");
         m_CheckedDispatches = nullptr;
-        for (size_t slot = 0; slot < userPool.size(); slot++) {
-            if (userPool[slot].data && nrdHipBindResource(m_Executor, (uint32_t)slot, &userPool[slot]) != (uint32_t)Result::SUCCESS)
-                return false;
-        }
+        if (!BindPool(userPool))
+            return false;
         const DispatchDesc* descs = nullptr;
         if (GetComputeDispatches(*m_Instance, denoisers, denoisersNum, descs, m_CheckedDispatchesNum) != Result::SUCCESS)
             return false;

@@ -402,7 +402,7 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError",
                    "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit",
                    "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString", "nrdHipPackShadowLights", "nrdHipResolveShadowLights",
-                   "nrdHipPackGuides"]
+                   "nrdHipPackGuides", "nrdHipCreateExecutorLayered", "nrdHipBindResourceLayers", "nrdHipGetPoolPlaneLayer", "nrdHipGetLayersNum"]
 
 _libs = {}
 
@@ -448,6 +448,10 @@ def load_library(path=None):
     lib.nrdHipGetArenaSize.argtypes, lib.nrdHipGetArenaSize.restype = [C.c_void_p, C.c_uint16, C.c_uint16], C.c_uint64
     lib.nrdHipCreateExecutorWithArena.argtypes = [C.c_void_p, C.c_uint16, C.c_uint16, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_void_p)]
     lib.nrdHipCreateExecutorWithArena.restype = C.c_uint32
+    lib.nrdHipCreateExecutorLayered.argtypes, lib.nrdHipCreateExecutorLayered.restype = [C.c_void_p, C.c_uint16, C.c_uint16, C.c_uint32, C.c_void_p, P(C.c_void_p)], C.c_uint32
+    lib.nrdHipBindResourceLayers.argtypes, lib.nrdHipBindResourceLayers.restype = [C.c_void_p, C.c_uint32, P(HipPlaneDesc), C.c_uint64], C.c_uint32
+    lib.nrdHipGetPoolPlaneLayer.argtypes, lib.nrdHipGetPoolPlaneLayer.restype = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(HipPlaneDesc)], C.c_uint32
+    lib.nrdHipGetLayersNum.argtypes, lib.nrdHipGetLayersNum.restype = [C.c_void_p, P(C.c_uint32)], C.c_uint32
     lib.nrdHipSetOwnedRows.argtypes, lib.nrdHipSetOwnedRows.restype = [C.c_void_p, C.c_uint32, C.c_uint32], C.c_uint32
     lib.nrdHipGetDispatchReach.argtypes, lib.nrdHipGetDispatchReach.restype = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)], C.c_uint32
     lib.nrdHipExecuteDispatchRange.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -39,6 +39,12 @@ struct NrdHipExecutor {
     uint32_t* motionBits = nullptr;    // nrdHipMeasureMotionRows: the reduction's result (float bits), own 4-byte allocation made on first use
     uint32_t* inputReport = nullptr;   // nrdHipCheckInputs: the device copy of the NrdHipInputReport, own allocation made on first use
     std::vector<nrd::Format> permanentFormat, transientFormat;
+    // nrdHipCreateExecutorLayered: every pool plane exists layersNum times, layer l of plane i at permanent[i].ptr + l * permanentStride[i] (its 256-byte aligned size);
+    // the per-layer user slots are stacks of planes userLayerBytes apart (nrdHipBindResourceLayers; 0 = a plain plane shared by all layers)
+    uint32_t layersNum = 1;
+    std::vector<uint64_t> permanentStride, transientStride;
+    uint64_t userLayerBytes[nrdhip::kUserSlots] = {};
+    std::vector<uint64_t> scratchLayerStrides;
 
     nrdhip::Plane user[nrdhip::kUserSlots] = {};
     bool userBound[nrdhip::kUserSlots] = {};

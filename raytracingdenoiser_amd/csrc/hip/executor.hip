@@ -83,9 +83,12 @@ Ensured nrdhip::EnsurePlane(Plane& plane, const Plane& geometry) {
     return Ensured::FAILED;
 }
 
-static bool PlanPool(const nrd::TextureDesc* descs, uint32_t num, uint16_t w, uint16_t h, std::vector<Plane>& planes, std::vector<nrd::Format>& formats, uint64_t& offset) {
+// layers > 1 (nrdHipCreateExecutorLayered): every plane is followed by its layers 1 .. layers - 1, each `strides[i]` -- the plane's 256-byte aligned size -- behind the last
+static bool PlanPool(const nrd::TextureDesc* descs, uint32_t num, uint16_t w, uint16_t h, uint32_t layers, std::vector<Plane>& planes, std::vector<nrd::Format>& formats,
+    std::vector<uint64_t>& strides, uint64_t& offset) {
     planes.resize(num);
     formats.resize(num);
+    strides.resize(num);
     for (uint32_t i = 0; i < num; i++) {
         uint32_t bpt = BytesPerTexel(descs[i].format);
         if (!bpt)
@@ -95,24 +98,34 @@ static bool PlanPool(const nrd::TextureDesc* descs, uint32_t num, uint16_t w, ui
         uint32_t pitch = ((uint32_t)pw * bpt + 255u) & ~255u;
         planes[i] = Plane{(uint8_t*)(uintptr_t)offset, pitch, pw, ph}; // (ptr: patched to a real pointer once the arena exists)
         formats[i] = descs[i].format;
-        offset += ((uint64_t)pitch * (uint64_t)ph + 255u) & ~(uint64_t)255u;
+        strides[i] = ((uint64_t)pitch * (uint64_t)ph + 255u) & ~(uint64_t)255u;
+        offset += strides[i] * layers;
     }
     return true;
 }
 
 static bool PlanPools(const nrd::InstanceDesc& desc, uint16_t w, uint16_t h, NrdHipExecutor& e) {
     uint64_t offset = 0;
-    bool ok = PlanPool(desc.permanentPool, desc.permanentPoolSize, w, h, e.permanent, e.permanentFormat, offset);
+    bool ok = PlanPool(desc.permanentPool, desc.permanentPoolSize, w, h, e.layersNum, e.permanent, e.permanentFormat, e.permanentStride, offset);
     e.permanentBytes = offset;
-    ok = ok && PlanPool(desc.transientPool, desc.transientPoolSize, w, h, e.transient, e.transientFormat, offset);
+    ok = ok && PlanPool(desc.transientPool, desc.transientPoolSize, w, h, e.layersNum, e.transient, e.transientFormat, e.transientStride, offset);
     e.transientBytes = offset - e.permanentBytes;
     return ok;
 }
 
-static uint32_t CreateExecutorImpl(void* instance, uint16_t resourceWidth, uint16_t resourceHeight, void* hipStream, void* userArena, uint64_t userArenaSize, NrdHipExecutor** executor) {
-    if (!instance || !executor || !resourceWidth || !resourceHeight)
+static uint32_t CreateExecutorImpl(void* instance, uint16_t resourceWidth, uint16_t resourceHeight, uint32_t layersNum, void* hipStream, void* userArena, uint64_t userArenaSize,
+    NrdHipExecutor** executor) {
+    if (!instance || !executor || !resourceWidth || !resourceHeight || !layersNum || layersNum > NRD_HIP_MAX_SHADOW_LIGHTS)
         return (uint32_t)nrd::Result::INVALID_ARGUMENT;
     *executor = nullptr;
+    if (layersNum > 1) { // the layers share every constant, which only SIGMA's passes allow (include/NRDHip.h "layered executor")
+        const nrd::InstanceDesc& desc = nrd::GetInstanceDesc(*(nrd::Instance*)instance);
+        for (uint32_t p = 0; p < desc.pipelinesNum; p++)
+            if (strncmp(desc.pipelines[p].shaderFileName, "SIGMA_", 6) != 0 && strncmp(desc.pipelines[p].shaderFileName, "Clear_", 6) != 0) {
+                fprintf(stderr, "nrdHipCreateExecutorLayered: %u layers need an instance of SIGMA denoisers only; this one holds the pass %s\n", layersNum, desc.pipelines[p].shaderFileName);
+                return (uint32_t)nrd::Result::UNSUPPORTED;
+            }
+    }
     if (!PlaneAddressable(((uint64_t)resourceWidth * 16u + 255u) & ~255ull, resourceHeight)) {
         fprintf(stderr, "nrdHipCreateExecutor: %u x %u is beyond the 4 GiB a plane of 16-byte texels may span (32-bit byte offsets)\n", resourceWidth, resourceHeight);
         return (uint32_t)nrd::Result::UNSUPPORTED;
@@ -129,6 +142,7 @@ static uint32_t CreateExecutorImpl(void* instance, uint16_t resourceWidth, uint1
     e->stream = (hipStream_t)hipStream;
     e->width = resourceWidth;
     e->height = resourceHeight;
+    e->layersNum = layersNum;
 
     const nrd::InstanceDesc& desc = nrd::GetInstanceDesc(*e->instance);
 
@@ -182,14 +196,19 @@ static uint32_t CreateExecutorImpl(void* instance, uint16_t resourceWidth, uint1
 }
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipCreateExecutor(void* instance, uint16_t resourceWidth, uint16_t resourceHeight, void* hipStream, NrdHipExecutor** executor) {
-    return CreateExecutorImpl(instance, resourceWidth, resourceHeight, hipStream, nullptr, 0, executor);
+    return CreateExecutorImpl(instance, resourceWidth, resourceHeight, 1, hipStream, nullptr, 0, executor);
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipCreateExecutorLayered(void* instance, uint16_t resourceWidth, uint16_t resourceHeight, uint32_t layersNum, void* hipStream,
+    NrdHipExecutor** executor) {
+    return CreateExecutorImpl(instance, resourceWidth, resourceHeight, layersNum, hipStream, nullptr, 0, executor);
 }
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipCreateExecutorWithArena(void* instance, uint16_t resourceWidth, uint16_t resourceHeight, void* hipStream, void* arena, uint64_t arenaSize,
     NrdHipExecutor** executor) {
     if (!arena)
         return (uint32_t)nrd::Result::INVALID_ARGUMENT;
-    return CreateExecutorImpl(instance, resourceWidth, resourceHeight, hipStream, arena, arenaSize, executor);
+    return CreateExecutorImpl(instance, resourceWidth, resourceHeight, 1, hipStream, arena, arenaSize, executor);
 }
 
 extern "C" __attribute__((visibility("default"))) uint64_t nrdHipGetArenaSize(void* instance, uint16_t resourceWidth, uint16_t resourceHeight) {
@@ -223,11 +242,14 @@ extern "C" __attribute__((visibility("default"))) void nrdHipDestroyExecutor(Nrd
     delete e;
 }
 
-extern "C" __attribute__((visibility("default"))) uint32_t nrdHipBindResource(NrdHipExecutor* e, uint32_t resourceType, const NrdHipPlaneDesc* plane) {
-    if (!e || !plane)
-        return (uint32_t)nrd::Result::INVALID_ARGUMENT;
-    if (resourceType >= (uint32_t)nrd::ResourceType::TRANSIENT_POOL)
-        return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipBindResource: not a user slot");
+// the slots of which every layer of a layered executor has its own plane (SIGMA's noisy inputs and its output); every other slot is one plane read by all layers
+static bool IsPerLayerSlot(uint32_t t) {
+    using R = nrd::ResourceType;
+    return t == (uint32_t)R::IN_PENUMBRA || t == (uint32_t)R::IN_TRANSLUCENCY || t == (uint32_t)R::OUT_SHADOW_TRANSLUCENCY;
+}
+
+// nrdHipBindResource (layerBytes = 0) and nrdHipBindResourceLayers: the same rules for the plane, which describes layer 0
+static uint32_t BindPlane(NrdHipExecutor* e, uint32_t resourceType, const NrdHipPlaneDesc* plane, uint64_t layerBytes) {
 
     nrd::Format expected = ExpectedUserFormat((nrd::ResourceType)resourceType, e->translucentShadow);
     if (expected == nrd::Format::MAX_NUM)
@@ -248,9 +270,33 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipBindResource(Nr
     p.w = plane->width;
     p.h = plane->height;
     e->userBound[resourceType] = true;
+    e->userLayerBytes[resourceType] = layerBytes;
     if (resourceType == (uint32_t)nrd::ResourceType::IN_NORMAL_ROUGHNESS || resourceType == (uint32_t)nrd::ResourceType::IN_VIEWZ)
         e->decodedFresh = false;
     return (uint32_t)nrd::Result::SUCCESS;
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipBindResource(NrdHipExecutor* e, uint32_t resourceType, const NrdHipPlaneDesc* plane) {
+    if (!e || !plane)
+        return (uint32_t)nrd::Result::INVALID_ARGUMENT;
+    if (resourceType >= (uint32_t)nrd::ResourceType::TRANSIENT_POOL)
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipBindResource: not a user slot");
+    if (e->layersNum > 1 && IsPerLayerSlot(resourceType))
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, std::string("nrdHipBindResource: on a layered executor every layer has its own ") + nrd::GetResourceTypeString((nrd::ResourceType)resourceType) +
+                                                          "; bind the stack with nrdHipBindResourceLayers");
+    return BindPlane(e, resourceType, plane, 0);
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipBindResourceLayers(NrdHipExecutor* e, uint32_t resourceType, const NrdHipPlaneDesc* plane, uint64_t layerBytes) {
+    if (!e || !plane)
+        return (uint32_t)nrd::Result::INVALID_ARGUMENT;
+    if (e->layersNum <= 1)
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipBindResourceLayers: the executor has no layers (nrdHipCreateExecutorLayered with layersNum > 1); use nrdHipBindResource");
+    if (resourceType >= (uint32_t)nrd::ResourceType::TRANSIENT_POOL || !IsPerLayerSlot(resourceType))
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipBindResourceLayers: not a per-layer slot (IN_PENUMBRA, IN_TRANSLUCENCY, OUT_SHADOW_TRANSLUCENCY); the other slots are shared: nrdHipBindResource");
+    if (layerBytes < (uint64_t)plane->rowPitchBytes * plane->height || (layerBytes & 3u) != 0)
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipBindResourceLayers: layerBytes must be >= rowPitchBytes x height and a multiple of 4");
+    return BindPlane(e, resourceType, plane, layerBytes);
 }
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipGetPoolPlane(NrdHipExecutor* e, uint32_t resourceType, uint32_t indexInPool, NrdHipPlaneDesc* plane) {
@@ -272,6 +318,8 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipGetPoolPlane(Nr
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipSetOwnedRows(NrdHipExecutor* e, uint32_t rowBegin, uint32_t rowEnd) {
     if (!e || rowBegin > rowEnd)
         return (uint32_t)nrd::Result::INVALID_ARGUMENT;
+    if (e->layersNum > 1 && (rowBegin != 0 || rowEnd < e->height))
+        return e->Fail(nrd::Result::UNSUPPORTED, "nrdHipSetOwnedRows: a layered executor runs whole frames only (no row strips)");
     e->ownedRowBegin = (int)rowBegin;
     e->ownedRowEnd = rowEnd >= e->height ? INT_MAX : (int)rowEnd;
     return (uint32_t)nrd::Result::SUCCESS;
@@ -478,8 +526,10 @@ static const char* FillPassArgs(NrdHipExecutor* e, const Range& range, const Gui
     e->scratchPlanes.resize(d.resourcesNum);
     e->scratchBytesPerTexel.resize(d.resourcesNum);
     e->scratchFormats.resize(d.resourcesNum);
-    auto use = [&](uint32_t r, const Plane& plane, nrd::Format format) {
+    e->scratchLayerStrides.resize(d.resourcesNum);
+    auto use = [&](uint32_t r, const Plane& plane, nrd::Format format, uint64_t layerStride) {
         e->scratchPlanes[r] = plane;
+        e->scratchLayerStrides[r] = e->layersNum > 1 ? layerStride : 0;
         e->scratchBytesPerTexel[r] = (uint8_t)BytesPerTexel(format);
         e->scratchFormats[r] = (uint8_t)format;
     };
@@ -488,7 +538,7 @@ static const char* FillPassArgs(NrdHipExecutor* e, const Range& range, const Gui
         if (res.type == nrd::ResourceType::PERMANENT_POOL) {
             if (res.indexInPool >= e->permanent.size())
                 return "permanent pool index out of range";
-            use(r, e->permanent[res.indexInPool], e->permanentFormat[res.indexInPool]);
+            use(r, e->permanent[res.indexInPool], e->permanentFormat[res.indexInPool], e->permanentStride[res.indexInPool]);
         } else if (res.type == nrd::ResourceType::TRANSIENT_POOL) {
             if (res.indexInPool >= e->transient.size())
                 return "transient pool index out of range";
@@ -496,20 +546,26 @@ static const char* FillPassArgs(NrdHipExecutor* e, const Range& range, const Gui
             const uint16_t index = nrd::TransientAliasOf(*e->instance, d.identifier, res.indexInPool);
             if (index >= e->transient.size())
                 return "transient pool index out of range";
-            use(r, e->transient[index], e->transientFormat[index]);
+            use(r, e->transient[index], e->transientFormat[index], e->transientStride[index]);
         } else {
             uint32_t t = (uint32_t)res.type;
             if (t >= (uint32_t)nrd::ResourceType::MAX_NUM || !e->userBound[t]) {
                 msg = std::string("resource not bound: ") + (nrd::GetResourceTypeString(res.type) ? nrd::GetResourceTypeString(res.type) : "?");
                 return msg.c_str();
             }
-            use(r, (e->originX || e->originY) && IsGuideInput(res.type) && e->shifted[t].ptr ? e->shifted[t] : e->user[t], ExpectedUserFormat(res.type, e->translucentShadow));
+            if (e->layersNum > 1 && IsPerLayerSlot(t) && !e->userLayerBytes[t]) { // (unreachable through the entry points: nrdHipBindResource refuses these slots)
+                msg = std::string("not bound as a stack of layers: ") + nrd::GetResourceTypeString(res.type);
+                return msg.c_str();
+            }
+            use(r, (e->originX || e->originY) && IsGuideInput(res.type) && e->shifted[t].ptr ? e->shifted[t] : e->user[t], ExpectedUserFormat(res.type, e->translucentShadow), e->userLayerBytes[t]);
         }
     }
     args.planes = e->scratchPlanes.data();
     args.planesNum = d.resourcesNum;
     args.bytesPerTexel = e->scratchBytesPerTexel.data();
     args.formats = e->scratchFormats.data();
+    args.layersNum = e->layersNum;
+    args.layerStrides = e->layersNum > 1 ? e->scratchLayerStrides.data() : nullptr;
     args.constants = d.constantBufferData;
     args.constantsSize = d.constantBufferDataSize;
     args.gridWidth = d.gridWidth;
@@ -560,6 +616,8 @@ static uint32_t RecordRange(NrdHipExecutor* e, const Range& range, const GuidePl
         PassLauncher launch = e->launchers[d.pipelineIndex];
         if (!launch)
             return e->Fail(nrd::Result::UNSUPPORTED, "nrdHipExecuteDispatches: no HIP kernel for pass " + PassName(range, d) + "; nothing was launched");
+        if (e->layersNum > 1 && strncmp(ShaderOf(range.idesc, d), "SIGMA_", 6) != 0 && strncmp(ShaderOf(range.idesc, d), "Clear_", 6) != 0)
+            return e->Fail(nrd::Result::UNSUPPORTED, "nrdHipExecuteDispatches: a layered executor runs SIGMA and Clear passes only, not " + PassName(range, d) + "; nothing was launched");
         if (d.constantBufferDataSize && !d.constantBufferData)
             return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipExecuteDispatches: pass " + PassName(range, d) + " has no constant data (constant arena overflow?); nothing was launched");
         PassArgs args = {};
@@ -643,6 +701,8 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipExecuteDispatch
     const int32_t* rowBegin, const int32_t* rowEnd) {
     if (!e || (!dispatchDescs && dispatchDescsNum) || first > dispatchDescsNum || count > dispatchDescsNum - first || (rowBegin == nullptr) != (rowEnd == nullptr))
         return (uint32_t)nrd::Result::INVALID_ARGUMENT;
+    if (e->layersNum > 1 && rowBegin)
+        return e->Fail(nrd::Result::UNSUPPORTED, "nrdHipExecuteDispatchRange: a layered executor runs whole frames only (pass NULL row arrays); nothing was launched");
     return ExecuteRange(e, (const nrd::DispatchDesc*)dispatchDescs, dispatchDescsNum, first, count, rowBegin, rowEnd);
 }
 

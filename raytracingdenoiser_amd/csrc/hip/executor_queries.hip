@@ -5,6 +5,25 @@
 
 using namespace nrdhip;
 
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipGetLayersNum(const NrdHipExecutor* e, uint32_t* layersNum) {
+    if (!e || !layersNum)
+        return (uint32_t)nrd::Result::INVALID_ARGUMENT;
+    *layersNum = e->layersNum;
+    return (uint32_t)nrd::Result::SUCCESS;
+}
+
+// nrdHipGetPoolPlane describes layer 0; layer l of the same plane lies l x (its 256-byte aligned size) behind it
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipGetPoolPlaneLayer(NrdHipExecutor* e, uint32_t resourceType, uint32_t indexInPool, uint32_t layer, NrdHipPlaneDesc* plane) {
+    if (!e || !plane)
+        return (uint32_t)nrd::Result::INVALID_ARGUMENT;
+    if (layer >= e->layersNum)
+        return e->Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipGetPoolPlaneLayer: the executor has " + std::to_string(e->layersNum) + " layer(s)");
+    const uint32_t r = nrdHipGetPoolPlane(e, resourceType, indexInPool, plane);
+    if (r == (uint32_t)nrd::Result::SUCCESS)
+        plane->data = (uint8_t*)plane->data + (uint64_t)layer * (resourceType == (uint32_t)nrd::ResourceType::PERMANENT_POOL ? e->permanentStride : e->transientStride)[indexInPool];
+    return r;
+}
+
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipSetProfiling(NrdHipExecutor* e, uint32_t enable) {
     if (!e)
         return (uint32_t)nrd::Result::INVALID_ARGUMENT;
@@ -167,6 +186,8 @@ static bool IsFloatFormat(nrd::Format f) {
 static uint32_t EnqueueCheckInputs(NrdHipExecutor* e, const void* dispatchDescs, uint32_t dispatchDescsNum, uint32_t* deviceReport, uint32_t& mask) {
     using R = nrd::ResourceType;
     mask = 0;
+    if (e->layersNum > 1) // (the audit kernel reads one plane per slot: audit a layer through an unlayered executor with that layer's planes bound)
+        return e->Fail(nrd::Result::UNSUPPORTED, "nrdHipCheckInputs: not on a layered executor; audit one layer through an unlayered executor");
     // the frame's rect, range and checkerboard: the first constant block of a pass family (every block of a list carries the same CommonSettings)
     const ListScan s = ScanDispatchList(nrd::GetInstanceDesc(*e->instance), (const nrd::DispatchDesc*)dispatchDescs, dispatchDescsNum);
     CheckInputsParams p = {};

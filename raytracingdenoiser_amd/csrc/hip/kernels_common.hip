@@ -179,7 +179,12 @@ void LaunchShiftPlane(const PassArgs& a, const Plane& user, const Plane& shifted
 
 // ---- Clear: zero every texel of the plane (row padding is never read). User planes may have any pitch / alignment, so a 16-byte
 // chunk is written with one store only when it is whole and aligned, bytewise otherwise (ragged row ends, 1-pixel-wide frames)
-__global__ __launch_bounds__(256) void ClearPlaneKernel(Plane out, uint32_t rowBytes, uint32_t firstRow) {
+// LAYERS (passes.h "LAYERED twins"): empty, or the LayerStrides<1> of the twin a layered executor launches with grid.z = layers -- one launch clears the plane of every
+// layer, never the bytes between two layers
+template <typename... LAYERS>
+__global__ __launch_bounds__(256) void ClearPlaneKernel(Plane out, uint32_t rowBytes, uint32_t firstRow, LAYERS... layers) {
+    if constexpr (sizeof...(LAYERS) != 0)
+        AdvanceToLayers(layers..., out);
     const uint32_t begin = (blockIdx.x * 256u + threadIdx.x) * 16u;
     if (begin >= rowBytes)
         return;
@@ -201,7 +206,11 @@ static const char* LaunchClear(const PassArgs& a) {
     // always the whole plane: clears belong to restart frames, which the sharding planners run unsharded (reach unknown), and the plane may be a
     // down-sampled one whose rows are not the frame's rows
     dim3 grid((rowBytes + 4095) / 4096, (unsigned)out.h, 1);
-    LaunchPass(a, ClearPlaneKernel, grid, dim3(256), out, rowBytes, 0u);
+    if (IsLayered(a)) {
+        grid.z = a.layersNum;
+        LaunchPass(a, ClearPlaneKernel<LayerStrides<1>>, grid, dim3(256), out, rowBytes, 0u, LayerStrides<1>{{a.layerStrides[0]}});
+    } else
+        LaunchPass(a, ClearPlaneKernel<>, grid, dim3(256), out, rowBytes, 0u);
     return nullptr;
 }
 

@@ -13,6 +13,8 @@
 // wave-wide reductions (__all / shuffle-max) instead of the reference's LDS atomics. Blur / PostBlur / TS stage a 36x12
 // (halo 2) LDS tile of {penumbra, viewZ, shadow} decoded once per workgroup for the dense 5x5 part; the sparse 8-tap part
 // gathers from global (L2). LDS rows are padded to 37 dwords.
+// Many lights: a layered executor (include/NRDHip.h nrdHipCreateExecutorLayered) launches the LAYERED twin of each kernel once per pass for all its shadow layers, the layer in
+// blockIdx.z (passes.h "LAYERED twins"): 5-25 us kernels too small to fill 256 CUs become one grid N times the size, and N - 1 launches per pass are saved.
 #include "../common/pass_constants.h"
 #include "passes.h"
 #include "reblur_device.h" // shared Common.hlsli helpers (weights, history fetch, clamp-addressed fetches)
@@ -122,8 +124,11 @@ NRD_D float LoadTileX(const Plane& tiles, int tx, int ty) { // .x of the RG8 smo
 }
 
 // ================================================================================================ ClassifyTiles
-template <bool TRANSLUCENT>
-__global__ __launch_bounds__(256) void SigmaClassifyTilesKernel(SigmaCB c, Plane viewZ, Plane penumbra, Plane translucency, Plane tiles) {
+// Every kernel of this file ends in `LAYERS... layers` (passes.h "LAYERED twins"): empty for an unlayered executor, one LayerStrides<N> for nrdHipCreateExecutorLayered
+template <bool TRANSLUCENT, typename... LAYERS>
+__global__ __launch_bounds__(256) void SigmaClassifyTilesKernel(SigmaCB c, Plane viewZ, Plane penumbra, Plane translucency, Plane tiles, LAYERS... layers) {
+    if constexpr (sizeof...(LAYERS) != 0)
+        AdvanceToLayers(layers..., viewZ, penumbra, translucency, tiles);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // the tiles of the RECT (the reference's dispatch grid, ceil( rectSize / 16 ) groups): tiles of the plane beyond it are left alone
     const int tilesW = min(tiles.w, ((int)c.gRectSize.x + 15) >> 4), tilesH = min(tiles.h, ((int)c.gRectSize.y + 15) >> 4);
@@ -185,12 +190,19 @@ static const char* LaunchClassifyTiles(const PassArgs& a) {
         return "SIGMA classify tiles: unexpected resource count";
     const Plane& tiles = a.planes[a.planesNum - 1];
     int numTiles = tiles.w * tiles.h;
-    LaunchPass(a, (SigmaClassifyTilesKernel<TRANSLUCENT>), dim3((numTiles + 3) / 4), dim3(256), c, a.planes[0], a.planes[1], TRANSLUCENT ? a.planes[2] : Plane{}, tiles);
+    if (IsLayered(a))
+        LaunchPass(a, (SigmaClassifyTilesKernel<TRANSLUCENT, LayerStrides<4>>), dim3((numTiles + 3) / 4, 1, a.layersNum), dim3(256), c, a.planes[0], a.planes[1],
+            TRANSLUCENT ? a.planes[2] : Plane{}, tiles, LayerStrides<4>{{a.layerStrides[0], a.layerStrides[1], TRANSLUCENT ? a.layerStrides[2] : 0u, a.layerStrides[a.planesNum - 1]}});
+    else
+        LaunchPass(a, (SigmaClassifyTilesKernel<TRANSLUCENT>), dim3((numTiles + 3) / 4), dim3(256), c, a.planes[0], a.planes[1], TRANSLUCENT ? a.planes[2] : Plane{}, tiles);
     return nullptr;
 }
 
 // ================================================================================================ SmoothTiles
-__global__ __launch_bounds__(256) void SigmaSmoothTilesKernel(SigmaCB c, Plane inTiles, Plane outTiles) {
+template <typename... LAYERS>
+__global__ __launch_bounds__(256) void SigmaSmoothTilesKernel(SigmaCB c, Plane inTiles, Plane outTiles, LAYERS... layers) {
+    if constexpr (sizeof...(LAYERS) != 0)
+        AdvanceToLayers(layers..., inTiles, outTiles);
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (!InBounds(outTiles, x, y))
         return;
@@ -217,7 +229,12 @@ __global__ __launch_bounds__(256) void SigmaSmoothTilesKernel(SigmaCB c, Plane i
 static const char* LaunchSmoothTiles(const PassArgs& a) {
     const SigmaCB& c = *(const SigmaCB*)a.constants;
     const Plane& out = a.planes[1];
-    LaunchPass(a, SigmaSmoothTilesKernel, GridFor(out.w, out.h, 16, 16), dim3(256), c, a.planes[0], out);
+    dim3 grid = GridFor(out.w, out.h, 16, 16);
+    if (IsLayered(a)) {
+        grid.z = a.layersNum;
+        LaunchPass(a, SigmaSmoothTilesKernel<LayerStrides<2>>, grid, dim3(256), c, a.planes[0], out, LayerStrides<2>{{a.layerStrides[0], a.layerStrides[1]}});
+    } else
+        LaunchPass(a, SigmaSmoothTilesKernel<>, grid, dim3(256), c, a.planes[0], out);
     return nullptr;
 }
 
@@ -237,8 +254,11 @@ static RowBand MakeRowBand(const PassArgs& a, int h, int tileH) {
 }
 
 // ================================================================================================ Copy
-template <typename TEXEL> // uint8_t (R8 shadow) or uint32_t (RGBA8 shadow + translucency)
-__global__ __launch_bounds__(256) void SigmaCopyKernel(SigmaCB c, Plane tiles, Plane inHistory, Plane inHistoryLength, Plane outHistory, Plane outHistoryLength, int blockY0) {
+template <typename TEXEL, typename... LAYERS> // uint8_t (R8 shadow) or uint32_t (RGBA8 shadow + translucency)
+__global__ __launch_bounds__(256) void SigmaCopyKernel(SigmaCB c, Plane tiles, Plane inHistory, Plane inHistoryLength, Plane outHistory, Plane outHistoryLength, int blockY0,
+    LAYERS... layers) {
+    if constexpr (sizeof...(LAYERS) != 0)
+        AdvanceToLayers(layers..., tiles, inHistory, inHistoryLength, outHistory, outHistoryLength);
     // 4 pixels per thread: 4 (or 16) bytes of shadow history and 16 bytes of R32_UINT history length
     struct alignas(sizeof(TEXEL) * 4) Texel4 {
         TEXEL v[4];
@@ -268,7 +288,15 @@ static const char* LaunchCopy(const PassArgs& a) {
     dim3 grid((unsigned)((out.w + 255) / 256), band.blocksY, 1);
     if (a.planesNum != 5 || a.bytesPerTexel[1] != a.bytesPerTexel[3])
         return "SIGMA copy: unexpected resources";
-    if (a.bytesPerTexel[3] == 4)
+    if (IsLayered(a) && (a.bytesPerTexel[3] == 4 || a.bytesPerTexel[3] == 1)) {
+        typedef LayerStrides<5> L;
+        const L layers = {{a.layerStrides[0], a.layerStrides[1], a.layerStrides[2], a.layerStrides[3], a.layerStrides[4]}};
+        grid.z = a.layersNum;
+        if (a.bytesPerTexel[3] == 4)
+            LaunchPass(a, (SigmaCopyKernel<uint32_t, L>), grid, dim3(256), c, a.planes[0], a.planes[1], a.planes[2], out, a.planes[4], band.blockY0, layers);
+        else
+            LaunchPass(a, (SigmaCopyKernel<uint8_t, L>), grid, dim3(256), c, a.planes[0], a.planes[1], a.planes[2], out, a.planes[4], band.blockY0, layers);
+    } else if (a.bytesPerTexel[3] == 4)
         LaunchPass(a, SigmaCopyKernel<uint32_t>, grid, dim3(256), c, a.planes[0], a.planes[1], a.planes[2], out, a.planes[4], band.blockY0);
     else if (a.bytesPerTexel[3] == 1)
         LaunchPass(a, SigmaCopyKernel<uint8_t>, grid, dim3(256), c, a.planes[0], a.planes[1], a.planes[2], out, a.planes[4], band.blockY0);
@@ -282,8 +310,10 @@ struct BlurPlanes {
     Plane viewZ, normalRoughness, penumbra, tiles, shadow, outPenumbra, outShadow;
 };
 
-template <bool FIRST_PASS, bool TRANSLUCENT>
-__global__ __launch_bounds__(TILE_X* TILE_Y) void SigmaBlurKernel(SigmaCB c, BlurPlanes P, int blockY0) {
+template <bool FIRST_PASS, bool TRANSLUCENT, typename... LAYERS>
+__global__ __launch_bounds__(TILE_X* TILE_Y) void SigmaBlurKernel(SigmaCB c, BlurPlanes P, int blockY0, LAYERS... layers) {
+    if constexpr (sizeof...(LAYERS) != 0) // (in the order of BlurPlanes)
+        AdvanceToLayers(layers..., P.viewZ, P.normalRoughness, P.penumbra, P.tiles, P.shadow, P.outPenumbra, P.outShadow);
     typedef SigmaType<TRANSLUCENT> ST;
     typedef typename ST::type S;
     constexpr bool READS_SHADOW = !FIRST_PASS || TRANSLUCENT; // the translucent first pass reads IN_TRANSLUCENCY (not unpacked)
@@ -458,22 +488,33 @@ static const char* LaunchBlur(const PassArgs& a) {
     const SigmaCB& c = *(const SigmaCB*)a.constants;
     if (const char* err = CheckSupportedSigma(c))
         return err;
-    BlurPlanes P = {};
-    uint32_t k = 0;
-    P.viewZ = a.planes[k++];
-    P.normalRoughness = a.planes[k++];
-    P.penumbra = a.planes[k++];
-    P.tiles = a.planes[k++];
-    if (!FIRST_PASS || TRANSLUCENT)
-        P.shadow = a.planes[k++];
-    P.outPenumbra = a.planes[k++];
-    P.outShadow = a.planes[k++];
-    if (k != a.planesNum)
+    if (a.planesNum != ((!FIRST_PASS || TRANSLUCENT) ? 7u : 6u))
         return "SIGMA blur: unexpected resource count";
+    BlurPlanes P = {};
+    LayerStrides<7> layers = {}; // (in the order of BlurPlanes; 0 for the plane a pass does not bind)
+    const bool layered = IsLayered(a);
+    uint32_t k = 0;
+    auto take = [&](Plane& plane, int member) {
+        plane = a.planes[k];
+        layers.s[member] = layered ? a.layerStrides[k] : 0u;
+        k++;
+    };
+    take(P.viewZ, 0);
+    take(P.normalRoughness, 1);
+    take(P.penumbra, 2);
+    take(P.tiles, 3);
+    if (!FIRST_PASS || TRANSLUCENT)
+        take(P.shadow, 4);
+    take(P.outPenumbra, 5);
+    take(P.outShadow, 6);
     dim3 grid = GridFor(c.gRectSizeMinusOne.x + 1, c.gRectSizeMinusOne.y + 1, TILE_X, TILE_Y);
     const RowBand band = MakeRowBand(a, c.gRectSizeMinusOne.y + 1, TILE_Y);
     grid.y = band.blocksY;
-    LaunchPass(a, (SigmaBlurKernel<FIRST_PASS, TRANSLUCENT>), grid, dim3(TILE_X * TILE_Y), c, P, band.blockY0);
+    if (layered) {
+        grid.z = a.layersNum;
+        LaunchPass(a, (SigmaBlurKernel<FIRST_PASS, TRANSLUCENT, LayerStrides<7>>), grid, dim3(TILE_X * TILE_Y), c, P, band.blockY0, layers);
+    } else
+        LaunchPass(a, (SigmaBlurKernel<FIRST_PASS, TRANSLUCENT>), grid, dim3(TILE_X * TILE_Y), c, P, band.blockY0);
     return nullptr;
 }
 
@@ -495,8 +536,10 @@ NRD_D typename SigmaType<TRANSLUCENT>::type FetchShadowHistory(const HistoryFilt
     return FetchHistoryGeneric<typename ST::type>(h, tex, [](const Plane& p, int x, int y) { return ST::Load(p, x, y); }, ST::Splat(0.0f));
 }
 
-template <bool TRANSLUCENT>
-__global__ __launch_bounds__(TILE_X* TILE_Y) void SigmaTemporalStabilizationKernel(SigmaCB c, TsPlanes P, int blockY0, uint32_t* historyReach) {
+template <bool TRANSLUCENT, typename... LAYERS> // (every layer reports into the one history-reach word with atomicMax: the word receives the maximum over the layers)
+__global__ __launch_bounds__(TILE_X* TILE_Y) void SigmaTemporalStabilizationKernel(SigmaCB c, TsPlanes P, int blockY0, uint32_t* historyReach, LAYERS... layers) {
+    if constexpr (sizeof...(LAYERS) != 0) // (in the order of TsPlanes = of the pass's resources)
+        AdvanceToLayers(layers..., P.viewZ, P.mv, P.penumbra, P.shadow, P.history, P.historyLength, P.tiles, P.outShadow, P.outHistoryLength);
     typedef SigmaType<TRANSLUCENT> ST;
     typedef typename ST::type S;
     __shared__ float s_Penumbra[BUF_Y * BUF_STRIDE];
@@ -642,13 +685,22 @@ static const char* LaunchTemporalStabilization(const PassArgs& a) {
     dim3 grid = GridFor(c.gRectSizeMinusOne.x + 1, c.gRectSizeMinusOne.y + 1, TILE_X, TILE_Y);
     const RowBand band = MakeRowBand(a, c.gRectSizeMinusOne.y + 1, TILE_Y);
     grid.y = band.blocksY;
-    LaunchPass(a, SigmaTemporalStabilizationKernel<TRANSLUCENT>, grid, dim3(TILE_X * TILE_Y), c, P, band.blockY0, a.historyReachWord);
+    if (IsLayered(a)) {
+        LayerStrides<9> layers;
+        for (int k = 0; k < 9; k++)
+            layers.s[k] = a.layerStrides[k];
+        grid.z = a.layersNum;
+        LaunchPass(a, (SigmaTemporalStabilizationKernel<TRANSLUCENT, LayerStrides<9>>), grid, dim3(TILE_X * TILE_Y), c, P, band.blockY0, a.historyReachWord, layers);
+    } else
+        LaunchPass(a, SigmaTemporalStabilizationKernel<TRANSLUCENT>, grid, dim3(TILE_X * TILE_Y), c, P, band.blockY0, a.historyReachWord);
     return nullptr;
 }
 
 // ================================================================================================ SplitScreen
-template <bool TRANSLUCENT>
-__global__ __launch_bounds__(256) void SigmaSplitScreenKernel(SigmaCB c, Plane viewZ, Plane penumbra, Plane translucency, Plane outShadow, int blockY0) {
+template <bool TRANSLUCENT, typename... LAYERS>
+__global__ __launch_bounds__(256) void SigmaSplitScreenKernel(SigmaCB c, Plane viewZ, Plane penumbra, Plane translucency, Plane outShadow, int blockY0, LAYERS... layers) {
+    if constexpr (sizeof...(LAYERS) != 0)
+        AdvanceToLayers(layers..., viewZ, penumbra, translucency, outShadow);
     typedef SigmaType<TRANSLUCENT> ST;
     const int px = blockIdx.x * TILE_X + (threadIdx.x % TILE_X), py = ((int)blockIdx.y + blockY0) * TILE_Y + (threadIdx.x / TILE_X);
     if (px > c.gRectSizeMinusOne.x || py > c.gRectSizeMinusOne.y)
@@ -673,7 +725,12 @@ static const char* LaunchSplitScreen(const PassArgs& a) {
     dim3 grid = GridFor(c.gRectSizeMinusOne.x + 1, c.gRectSizeMinusOne.y + 1, TILE_X, TILE_Y);
     const RowBand band = MakeRowBand(a, c.gRectSizeMinusOne.y + 1, TILE_Y);
     grid.y = band.blocksY;
-    LaunchPass(a, SigmaSplitScreenKernel<TRANSLUCENT>, grid, dim3(256), c, a.planes[0], a.planes[1], TRANSLUCENT ? a.planes[2] : Plane{}, a.planes[a.planesNum - 1], band.blockY0);
+    if (IsLayered(a)) {
+        grid.z = a.layersNum;
+        LaunchPass(a, (SigmaSplitScreenKernel<TRANSLUCENT, LayerStrides<4>>), grid, dim3(256), c, a.planes[0], a.planes[1], TRANSLUCENT ? a.planes[2] : Plane{}, a.planes[a.planesNum - 1], band.blockY0,
+            LayerStrides<4>{{a.layerStrides[0], a.layerStrides[1], TRANSLUCENT ? a.layerStrides[2] : 0u, a.layerStrides[a.planesNum - 1]}});
+    } else
+        LaunchPass(a, SigmaSplitScreenKernel<TRANSLUCENT>, grid, dim3(256), c, a.planes[0], a.planes[1], TRANSLUCENT ? a.planes[2] : Plane{}, a.planes[a.planesNum - 1], band.blockY0);
     return nullptr;
 }
 

@@ -140,7 +140,30 @@ struct PassArgs {
     uint32_t* historyReachWord = nullptr;
     // non-null: the launcher performs all its checks and hands its launch(es) to the recorder instead of enqueueing them
     LaunchRecorder* recorder = nullptr;
+    // layered executor (include/NRDHip.h nrdHipCreateExecutorLayered, SIGMA and Clear passes only): the number of layers -- the z extent of the pass's grid -- and, per
+    // resolved plane, the bytes from layer l to layer l + 1 (0: one plane shared by all layers). <= 1 / nullptr on an unlayered executor, whose launchers then launch
+    // exactly the kernels they always did.
+    uint32_t layersNum = 0;
+    const uint64_t* layerStrides = nullptr;
 };
+
+// LAYERED twins. A kernel that serves a layered executor is a template whose last parameter is a pack, `typename... LAYERS`, and whose last argument is `LAYERS... layers`:
+//   LAYERS empty              the kernel an unlayered executor launches -- argument for argument, statement for statement the kernel it was before layers existed
+//   LAYERS = LayerStrides<N>  its LAYERED twin, launched with grid.z = layers: the layer strides of its N planes by value as one more argument. Its first statement,
+//                             AdvanceToLayers( layers..., planes... ), moves every plane to the layer of its workgroup; nothing else in the body differs.
+// blockIdx.z arrives in a scalar register and the strides are kernel arguments, so the 64-bit products are scalar arithmetic and every plane's base stays in SGPRs
+// (no per-lane multiply; the uniform tile-map loads of planes.h stay uniform).
+template <int N>
+struct LayerStrides {
+    uint64_t s[N];
+};
+inline bool IsLayered(const PassArgs& a) { return a.layersNum > 1 && a.layerStrides; }
+template <int N, typename... PLANES>
+__device__ __forceinline__ void AdvanceToLayers(const LayerStrides<N>& strides, PLANES&... planes) {
+    static_assert(sizeof...(PLANES) == N, "one stride per plane");
+    int k = 0;
+    ((planes.ptr += (uint64_t)blockIdx.z * strides.s[k++]), ...);
+}
 
 namespace detail {
 template <typename T>

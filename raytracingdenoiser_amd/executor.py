@@ -24,10 +24,22 @@ def texel_bytes(fmt):
     return api.FORMAT_BYTES[api.Format(fmt)]
 
 
-class HipExecutor:
-    """One nrd::Instance bound to pool planes in HBM; launches the pass chain on `stream` (a torch.cuda.Stream or None)."""
+class _DeviceBytes:
+    """device memory the library owns, as torch.as_tensor takes it (the CUDA array interface): the pool arena of a layered executor"""
 
-    def __init__(self, instance, width, height, stream=None):
+    def __init__(self, ptr, nbytes):
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+PER_LAYER_SLOTS = (api.ResourceType.IN_PENUMBRA, api.ResourceType.IN_TRANSLUCENCY, api.ResourceType.OUT_SHADOW_TRANSLUCENCY)
+
+
+class HipExecutor:
+    """One nrd::Instance bound to pool planes in HBM; launches the pass chain on `stream` (a torch.cuda.Stream or None).
+    layers > 1 (an instance of SIGMA denoisers only): `layers` shadow layers, one per light, denoised by one pass chain -- include/NRDHip.h nrdHipCreateExecutorLayered.
+    The per-layer slots (PER_LAYER_SLOTS) are then bound as [N, H, W(, C)] stacks with bind_layers, the guides with bind as ever; the pool belongs to the library."""
+
+    def __init__(self, instance, width, height, stream=None, layers=1):
         import torch
 
         if not torch.cuda.is_available():
@@ -36,8 +48,18 @@ class HipExecutor:
         self.lib = instance.lib
         self.width, self.height = width, height
         self.stream = stream
+        self.layers = layers
         handle = C.c_void_p()
         stream_ptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self._bound = {}  # keeps tensors alive
+        self._checked_list = None  # (identifiers, pointer, count, instance.list_generation): the list check_inputs fetched for the denoise() that follows
+        if layers != 1:  # (a caller-provided arena stays unlayered: the library allocates the layered pool)
+            self.arena = None
+            r = api.Result(self.lib.nrdHipCreateExecutorLayered(instance.handle, width, height, layers, stream_ptr, C.byref(handle)))
+            if r != api.Result.SUCCESS:
+                raise RuntimeError("nrdHipCreateExecutorLayered(%d layers) failed: %s" % (layers, r.name))
+            self.handle = handle
+            return
         # the pool arena is a torch allocation, so pool planes can be aliased as tensors (needed for the RCCL all-gather)
         size = self.lib.nrdHipGetArenaSize(instance.handle, width, height)
         self.arena = torch.zeros(max(size, 256), dtype=torch.uint8, device="cuda")
@@ -46,8 +68,6 @@ class HipExecutor:
         if r != api.Result.SUCCESS:
             raise RuntimeError("nrdHipCreateExecutorWithArena failed: %s" % r.name)
         self.handle = handle
-        self._bound = {}  # keeps tensors alive
-        self._checked_list = None  # (identifiers, pointer, count, instance.list_generation): the list check_inputs fetched for the denoise() that follows
 
     def _check(self, code, what):
         r = api.Result(code)
@@ -63,10 +83,23 @@ class HipExecutor:
         self._check(self.lib.nrdHipBindResource(self.handle, int(resource_type), C.byref(desc)), "nrdHipBindResource(%s)" % api.ResourceType(resource_type).name)
         self._bound[int(resource_type)] = tensor
 
+    def bind_layers(self, resource_type, tensor, fmt):
+        """a per-layer slot of a layered executor: tensor [N, H, W(, C)] with N == layers, layer l = tensor[l]; the layers may lie further apart than their size (stride(0)
+        is the layerBytes of nrdHipBindResourceLayers), e.g. frontend.shadow_stack or a [:, :H] view of a taller stack"""
+        assert tensor.is_cuda and tensor.shape[0] == self.layers and tensor[0][0].is_contiguous()
+        pitch = tensor.stride(1) * tensor.element_size()
+        desc = api.HipPlaneDesc(tensor.data_ptr(), pitch, int(fmt), self.width, self.height)
+        self._check(self.lib.nrdHipBindResourceLayers(self.handle, int(resource_type), C.byref(desc), tensor.stride(0) * tensor.element_size()),
+                    "nrdHipBindResourceLayers(%s)" % api.ResourceType(resource_type).name)
+        self._bound[int(resource_type)] = tensor
+
     def bind_packed(self, packed):
-        """binds what frontend.pack_inputs returned: {ResourceType: (tensor, Format)}"""
+        """binds what frontend.pack_inputs returned: {ResourceType: (tensor, Format)}; on a layered executor the per-layer slots are taken as stacks (bind_layers)"""
         for resource_type, (tensor, fmt) in packed.items():
-            self.bind(resource_type, tensor, fmt)
+            if self.layers > 1 and int(resource_type) in [int(t) for t in PER_LAYER_SLOTS]:
+                self.bind_layers(resource_type, tensor, fmt)
+            else:
+                self.bind(resource_type, tensor, fmt)
 
     def resolve(self, diffuse_mode=None, specular_mode=None, resolve=0, shadow=False, **kw):
         """frontend.resolve_outputs on the planes bound to this executor: the OUT_* planes of the given signal modes (frontend.SignalMode; `resolve` = frontend.ResolveMode for the
@@ -133,26 +166,38 @@ class HipExecutor:
     def execute_raw(self, dispatch_ptr, num):
         self._check(self.lib.nrdHipExecuteDispatches(self.handle, C.cast(dispatch_ptr, C.c_void_p), num), "nrdHipExecuteDispatches")
 
-    def pool_plane_desc(self, pool, index):
+    def pool_plane_desc(self, pool, index, layer=0):
         desc = api.HipPlaneDesc()
-        self._check(self.lib.nrdHipGetPoolPlane(self.handle, int(pool), index, C.byref(desc)), "nrdHipGetPoolPlane")
+        if layer == 0:
+            self._check(self.lib.nrdHipGetPoolPlane(self.handle, int(pool), index, C.byref(desc)), "nrdHipGetPoolPlane")
+        else:
+            self._check(self.lib.nrdHipGetPoolPlaneLayer(self.handle, int(pool), index, layer, C.byref(desc)), "nrdHipGetPoolPlaneLayer")
         return desc
 
-    def read_pool_plane(self, pool, index):
-        """Synchronous device->host copy of a pool plane: returns (uint8 ndarray [h, pitch], Format, width)."""
+    def layers_num(self):
+        n = C.c_uint32()
+        self._check(self.lib.nrdHipGetLayersNum(self.handle, C.byref(n)), "nrdHipGetLayersNum")
+        return n.value
+
+    def read_pool_plane(self, pool, index, layer=0):
+        """Synchronous device->host copy of a pool plane (of one layer): returns (uint8 ndarray [h, pitch], Format, width)."""
         import torch
 
         torch.cuda.synchronize()
-        d = self.pool_plane_desc(pool, index)
+        d = self.pool_plane_desc(pool, index, layer)
         host = np.empty((d.height, d.rowPitchBytes), dtype=np.uint8)
         err = _hip_runtime().hipMemcpy(host.ctypes.data_as(C.c_void_p), C.c_void_p(d.data), host.nbytes, 2)
         if err != 0:
             raise RuntimeError("hipMemcpy D2H failed: %d" % err)
         return host, api.Format(d.format), d.width
 
-    def pool_plane_tensor(self, pool, index):
-        """uint8 tensor view [h, pitch] aliasing a pool plane inside the arena (no copy)."""
-        d = self.pool_plane_desc(pool, index)
+    def pool_plane_tensor(self, pool, index, layer=0):
+        """uint8 tensor view [h, pitch] aliasing a pool plane (of one layer) inside the arena (no copy)."""
+        d = self.pool_plane_desc(pool, index, layer)
+        if self.arena is None:  # a layered executor: the arena belongs to the library (valid until destroy())
+            import torch
+
+            return torch.as_tensor(_DeviceBytes(d.data, d.height * d.rowPitchBytes), device="cuda").view(d.height, d.rowPitchBytes)
         off = d.data - self.arena.data_ptr()
         return self.arena[off : off + d.height * d.rowPitchBytes].view(d.height, d.rowPitchBytes)
 
