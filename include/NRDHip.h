@@ -457,6 +457,62 @@ typedef struct NrdHipBackEndSplit {
 } NrdHipBackEndSplit;
 uint32_t nrdHipResolveOutputsSplit(const NrdHipBackEndDesc* desc, const NrdHipBackEndOptions* options, const NrdHipBackEndSplit* split, void* hipStream);
 
+// Quarter-resolution tracing and denoising (reference README "RECOMMENDATIONS AND BEST PRACTICES: LESSER TIPS": "In case of quarter resolution tracing and denoising use
+// pixelPos / 2 as texture coordinates ... 'Nearest Z' upsampling works best for upscaling of the denoised output"). The full size is W x H, the low size w = ( W + 1 ) >> 1,
+// h = ( H + 1 ) >> 1; low pixel ( i, j ) stands for full pixel ( 2i, 2j ) -- not a rotated grid. The denoisers run at any size; the two calls below are the front end and
+// the back end of such a frame: a decimated pack, the denoise at w x h, and a resolve that brings the low OUT_* planes back to the full-size frame, where albedo, Rf0 and the
+// normals have their detail. Both follow the contract above: validated before the first HIP call, nothing enqueued on an error, no allocation, no synchronisation, capturable
+// into a graph, errors through nrdHipGetLastFrontEndError, the 32-bit limits for each plane at its own size, RGB32_SFLOAT planes by the rules of the *Split calls.
+// Out of scope: checkerboarding combined with decimation, re-jittering combined with upsampling, decimation inside nrdHipPackGuides (pack the guides at full size and hand
+// them to the calls below), any filter other than nearest Z.
+//
+// nrdHipPackInputsDecimated. guideShift == 0 is exactly nrdHipPackInputsSplit( desc, options, samples, split, stream ): the same kernels, the same bytes. guideShift == 1:
+//   full size (W x H), read at ( 2x, 2y ) for low pixel ( x, y ):  normalRoughness, viewZ, materialID, motion, albedo, rf0 and split->roughness -- the G-buffer
+//   low size (w x h):  everything traced -- both signals' radianceHitDist / direction and their sample layers, split->{ diffuse, specular }HitDist, distanceToOccluder,
+//                      translucency -- and every output
+// Every output byte equals what nrdHipPackInputsSplit writes when it is fed contiguous copies of the G-buffer planes decimated [ ::2, ::2 ]: the arithmetic is the same code,
+// only the load coordinate of the G-buffer planes differs. commonSettings (demodulation) is the struct of the LOW-size frame: rectSize = ( w, h ), and the view vector is that
+// of pixel ( x, y ) of a w x h frame. guideShift > 1 -> INVALID_ARGUMENT. With guideShift 1: G-buffer planes that are not all one size W x H, low planes that are not all one
+// size w x h, or sizes that break the relation above -> INVALID_ARGUMENT naming the plane; a checkerboardMode other than OFF -> UNSUPPORTED (out of scope).
+uint32_t nrdHipPackInputsDecimated(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, const NrdHipFrontEndSplit* split,
+                                   uint32_t guideShift, void* hipStream);
+
+// nrdHipResolveOutputsUpsampled. upsample == NULL is exactly nrdHipResolveOutputsSplit( desc, options, split, stream ). With upsample given:
+//   low size:   diffuse.in0 / in1, specular.in0 / in1, shadow and upsample->lowViewZ -- the denoiser's OUT_* planes and its IN_VIEWZ
+//   full size:  normalRoughness (the IN_NORMAL_ROUGHNESS format, packed at full size by a plain pack call), viewZ, albedo, rf0, every output of the descriptor, the split
+//               hit-distance outputs and upsample->outSource
+// commonSettings, viewZ and lowViewZ are required. commonSettings is the denoiser's own struct of the frame -- it supplies viewZScale, denoisingRange and the camera -- so its
+// rectSize must be the LOW size; the view vector of the contract above is evaluated with w = W, h = H. One launch. Per full pixel ( X, Y ), in correctly rounded fp32:
+//   s  = viewZScale          R = denoisingRange
+//   Zf = abs( viewZ[ X, Y ] * s )
+//   out of range      if Zf is NaN or Zf > R                                   -> source = none
+//   candidate k = a + 2b, for a, b in { 0, 1 }:
+//       texel ( i, j ) = ( ( X >> 1 ) + a, ( Y >> 1 ) + b )
+//       exists         iff ( a == 0 or X is odd ) and ( b == 0 or Y is odd ) and i < w and j < h
+//       Zk             = abs( lowViewZ[ i, j ] * s )
+//       valid          iff Zk is not NaN and !( Zk > R )
+//       dk             = abs( Zk - Zf )
+//   source            = the valid candidate of smallest dk; a tie goes to the lowest k
+//                       none if there is no valid candidate
+//                       none if depthThreshold > 0 and dk > depthThreshold * Zf
+// N, the roughness, V, the material factors, and the viewZ and roughness denormalizeHitDist uses are those of the FULL pixel, computed exactly as the plain call does. Only the
+// signal texels -- in0, in1 and shadow -- are read at the source texel; they then go through the code of the plain call: unpack, SH / SG / extract resolve, remodulation, store.
+// (A hit distance denormalised with the full pixel's depth and roughness is exact where those equal the source texel's and an approximation elsewhere.) Where the source is none,
+// every signal output, its split hit-distance plane, outShadow and outComposed get zeros and outSource 255; outViewVector, outDiffFactor and outSpecFactor do not depend on the
+// source and are written for every pixel, as the plain call does. No byte of a signal plane is loaded at a candidate that is not the chosen source: the denoisers leave texels
+// beyond the denoising range unwritten, so those may hold anything, NaN included.
+// UNSUPPORTED: options->reJitter != 0 together with upsample (it needs full-size SG neighbours: out of scope); an outSource in a format other than R8_UINT. INVALID_ARGUMENT,
+// naming the field: a missing commonSettings, viewZ or lowViewZ; a non-zero reserved; a NaN, negative or infinite depthThreshold; a rectSize that is not the low size; low or
+// full planes that differ in size within their class or break the size relation.
+typedef struct NrdHipBackEndUpsample {
+    NrdHipPlaneDesc lowViewZ;  // in,  R32_SFLOAT, low size: the IN_VIEWZ plane the denoiser ran with
+    NrdHipPlaneDesc outSource; // out, R8_UINT, full size, optional: which low texel a pixel took (0..3), 255 = none
+    float depthThreshold;      // 0 = off; > 0: reject a source whose depth differs by more than depthThreshold * depth
+    uint32_t reserved;         // must be 0
+} NrdHipBackEndUpsample;
+uint32_t nrdHipResolveOutputsUpsampled(const NrdHipBackEndDesc* desc, const NrdHipBackEndOptions* options, const NrdHipBackEndSplit* split, const NrdHipBackEndUpsample* upsample,
+                                       void* hipStream);
+
 // SIGMA shadows for local and many lights (reference README "RECOMMENDATIONS ... LESSER TIPS", [SIGMA]): the front end and the back end of up to NRD_HIP_MAX_SHADOW_LIGHTS lights
 // per pixel, one launch each, every input byte read once. The contract is the one above: validated before the first HIP call, nothing enqueued on an error, no allocation, no
 // synchronisation, capturable into a graph, errors through nrdHipGetLastFrontEndError, the 32-bit limits per plane. The arithmetic is NRD.hip.h in unfused fp32 with correctly
@@ -582,6 +638,7 @@ static_assert(sizeof(NrdHipGuidesDesc) == 328, "mirrored by raytracingdenoiser_a
 static_assert(sizeof(NrdHipShadowLight) == 16 && sizeof(NrdHipShadowLightsPackDesc) == 264 && sizeof(NrdHipShadowLightsResolveDesc) == 96, "mirrored by raytracingdenoiser_amd/api.py");
 static_assert(sizeof(NrdHipFrontEndSplit) == 88 && sizeof(NrdHipBackEndSplit) == 48, "mirrored by raytracingdenoiser_amd/api.py");
 static_assert(sizeof(NrdHipInputReport) == 72, "mirrored by raytracingdenoiser_amd/api.py");
+static_assert(sizeof(NrdHipBackEndUpsample) == 56, "mirrored by raytracingdenoiser_amd/api.py"); // 2 planes of 24 bytes + 8
 #endif
 
 #ifdef __cplusplus

@@ -179,6 +179,16 @@ public:
     inline bool ResolveShadowLights(const NrdHipShadowLightsResolveDesc& desc) { return nrdHipResolveShadowLights(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
     // IN_VIEWZ and IN_MV from world-space hit positions and the matrices of the frame's CommonSettings, and the optional UNORM guide slots from fp32 planes (nrdHipPackGuides)
     inline bool PackGuides(const NrdHipGuidesDesc& desc) { return nrdHipPackGuides(&desc, m_Stream) == (uint32_t)Result::SUCCESS; }
+    // Quarter-resolution tracing and denoising (nrdHipPackInputsDecimated / nrdHipResolveOutputsUpsampled): the G-buffer planes of the pack are full-size and read at every second
+    // texel, everything traced and every packed plane has the low size ( ( W + 1 ) >> 1 ) x ( ( H + 1 ) >> 1 ), for an instance recreated at that size; the resolve brings the low
+    // OUT_* planes back to the full-size frame by nearest-Z upsampling. options / samples / split may be NULL
+    inline bool PackInputsDecimated(const NrdHipFrontEndDesc& desc, const NrdHipFrontEndOptions* options = nullptr, const NrdHipFrontEndSamples* samples = nullptr,
+        const NrdHipFrontEndSplit* split = nullptr, uint32_t guideShift = 1) {
+        return nrdHipPackInputsDecimated(&desc, options, samples, split, guideShift, m_Stream) == (uint32_t)Result::SUCCESS;
+    }
+    inline bool ResolveOutputsUpsampled(const NrdHipBackEndDesc& desc, const NrdHipBackEndUpsample& upsample, const NrdHipBackEndOptions* options = nullptr, const NrdHipBackEndSplit* split = nullptr) {
+        return nrdHipResolveOutputsUpsampled(&desc, options, split, &upsample, m_Stream) == (uint32_t)Result::SUCCESS;
+    }
     inline const char* GetLastFrontEndError() const { return nrdHipGetLastFrontEndError(); }
 
     // Assumes that no work of this integration is in flight on the stream

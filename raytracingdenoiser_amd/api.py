@@ -322,6 +322,13 @@ class HipBackEndSplit(C.Structure):  # include/NRDHip.h NrdHipBackEndSplit
     _fields_ = [("diffuseHitDist", HipPlaneDesc), ("specularHitDist", HipPlaneDesc)]
 
 
+class HipBackEndUpsample(C.Structure):  # include/NRDHip.h NrdHipBackEndUpsample
+    _fields_ = [("lowViewZ", HipPlaneDesc), ("outSource", HipPlaneDesc), ("depthThreshold", C.c_float), ("reserved", C.c_uint32)]
+
+
+NO_SOURCE = 255  # NrdHipBackEndUpsample::outSource of a pixel that took no low texel
+
+
 class LightType(enum.IntEnum):  # include/NRDHip.h NRD_HIP_LIGHT_*
     DIRECTIONAL = 0
     LOCAL = 1
@@ -374,7 +381,7 @@ class HipInputReport(C.Structure):  # include/NRDHip.h NrdHipInputReport
 
 
 assert C.sizeof(HipInputReport) == 72
-assert C.sizeof(HipFrontEndSplit) == 88 and C.sizeof(HipBackEndSplit) == 48
+assert C.sizeof(HipFrontEndSplit) == 88 and C.sizeof(HipBackEndSplit) == 48 and C.sizeof(HipBackEndUpsample) == 56
 assert C.sizeof(HipPlaneDesc) == 24 and C.sizeof(HipFrontEndSignal) == 104 and C.sizeof(HipFrontEndDesc) == 552 and C.sizeof(HipBackEndSignal) == 80 and C.sizeof(HipBackEndDesc) == 432
 assert C.sizeof(HipFrontEndOptions) == 8 and C.sizeof(HipBackEndOptions) == 32 and C.sizeof(HipSignalSamples) == 24 and C.sizeof(HipFrontEndSamples) == 56
 
@@ -402,7 +409,8 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipMeasureMotionRows", "nrdHipMeasureMotionRowsAsync", "nrdHipSetHistoryReachWord", "nrdHipPackInputs", "nrdHipResolveOutputs", "nrdHipGetLastFrontEndError",
                    "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit",
                    "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString", "nrdHipPackShadowLights", "nrdHipResolveShadowLights",
-                   "nrdHipPackGuides", "nrdHipCreateExecutorLayered", "nrdHipBindResourceLayers", "nrdHipGetPoolPlaneLayer", "nrdHipGetLayersNum"]
+                   "nrdHipPackGuides", "nrdHipCreateExecutorLayered", "nrdHipBindResourceLayers", "nrdHipGetPoolPlaneLayer", "nrdHipGetLayersNum",
+                   "nrdHipPackInputsDecimated", "nrdHipResolveOutputsUpsampled"]
 
 _libs = {}
 
@@ -481,6 +489,10 @@ def load_library(path=None):
     lib.nrdHipResolveOutputsEx.argtypes, lib.nrdHipResolveOutputsEx.restype = [P(HipBackEndDesc), P(HipBackEndOptions), C.c_void_p], C.c_uint32
     lib.nrdHipPackInputsSplit.argtypes, lib.nrdHipPackInputsSplit.restype = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSamples), P(HipFrontEndSplit), C.c_void_p], C.c_uint32
     lib.nrdHipResolveOutputsSplit.argtypes, lib.nrdHipResolveOutputsSplit.restype = [P(HipBackEndDesc), P(HipBackEndOptions), P(HipBackEndSplit), C.c_void_p], C.c_uint32
+    lib.nrdHipPackInputsDecimated.argtypes = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSamples), P(HipFrontEndSplit), C.c_uint32, C.c_void_p]
+    lib.nrdHipPackInputsDecimated.restype = C.c_uint32
+    lib.nrdHipResolveOutputsUpsampled.argtypes = [P(HipBackEndDesc), P(HipBackEndOptions), P(HipBackEndSplit), P(HipBackEndUpsample), C.c_void_p]
+    lib.nrdHipResolveOutputsUpsampled.restype = C.c_uint32
     lib.nrdHipPackShadowLights.argtypes, lib.nrdHipPackShadowLights.restype = [P(HipShadowLightsPackDesc), C.c_void_p], C.c_uint32
     lib.nrdHipResolveShadowLights.argtypes, lib.nrdHipResolveShadowLights.restype = [P(HipShadowLightsResolveDesc), C.c_void_p], C.c_uint32
     lib.nrdHipPackGuides.argtypes, lib.nrdHipPackGuides.restype = [P(HipGuidesDesc), C.c_void_p], C.c_uint32

@@ -25,7 +25,7 @@ inline uint32_t Fail(nrd::Result r, const std::string& text) {
 inline uint32_t TexelBytes(nrd::Format f) {
     using F = nrd::Format;
     switch (f) {
-        case F::R8_UNORM: return 1;
+        case F::R8_UNORM: case F::R8_UINT: return 1;
         case F::R16_UNORM: case F::R16_SFLOAT: return 2;
         case F::RGBA8_UNORM: case F::RGBA8_SNORM: case F::R10_G10_B10_A2_UNORM: case F::R32_SFLOAT: return 4;
         case F::RGBA16_UNORM: case F::RGBA16_SNORM: case F::RGBA16_SFLOAT: case F::RG32_SFLOAT: return 8;
@@ -40,6 +40,10 @@ struct Checker {
     const char* entry;
     uint32_t result = (uint32_t)nrd::Result::SUCCESS;
     uint16_t w = 0, h = 0;
+    // quarter-resolution calls (nrdHipPackInputsDecimated / nrdHipResolveOutputsUpsampled): a second size class. While `full` is set a plane is held against fw x fh, the
+    // full-size planes of the call, instead of w x h, its low-size ones; once both are known, w x h must be ( ( fw + 1 ) >> 1 ) x ( ( fh + 1 ) >> 1 ). Never set by the other calls.
+    uint16_t fw = 0, fh = 0;
+    bool full = false;
     bool split = false;   // nrdHipPackInputsSplit / nrdHipResolveOutputsSplit: CheckColour accepts RGB32_SFLOAT
     uint32_t rgb = 0;     // kSplit* bits of the planes that hold it
 
@@ -63,10 +67,11 @@ struct Checker {
             return out;
         }
         const uint32_t bpt = TexelBytes((nrd::Format)p.format);
+        uint16_t &cw = full ? fw : w, &ch = full ? fh : h;
         if (!p.width || !p.height)
             Error(nrd::Result::INVALID_ARGUMENT, name, "empty plane");
-        else if (w && (p.width != w || p.height != h))
-            Error(nrd::Result::INVALID_ARGUMENT, name, "size differs from the other planes of the call");
+        else if (cw && (p.width != cw || p.height != ch))
+            Error(nrd::Result::INVALID_ARGUMENT, name, fw || full ? "size differs from the other planes of its size class (full-size / low-size) of the call" : "size differs from the other planes of the call");
         else if (bpt == 12u && ((p.rowPitchBytes % 4u) != 0 || ((uintptr_t)p.data % 4u) != 0)) // three packed dwords: dword alignment, rows need not start on a texel multiple
             Error(nrd::Result::INVALID_ARGUMENT, name, "row pitch or pointer of an RGB32_SFLOAT plane is not a multiple of 4");
         else if (bpt != 12u && ((p.rowPitchBytes % bpt) != 0 || ((uintptr_t)p.data % bpt) != 0))
@@ -77,8 +82,12 @@ struct Checker {
             Error(nrd::Result::UNSUPPORTED, name, "row pitch >= 16 MiB or plane >= 4 GiB (planes are addressed with 32-bit byte offsets)");
         if (Failed())
             return out;
-        w = p.width;
-        h = p.height;
+        cw = p.width;
+        ch = p.height;
+        if (w && fw && (w != ((fw + 1u) >> 1) || h != ((fh + 1u) >> 1))) {
+            Error(nrd::Result::INVALID_ARGUMENT, name, "the low-size planes must be ( ( W + 1 ) >> 1 ) x ( ( H + 1 ) >> 1 ) of the W x H full-size planes");
+            return out;
+        }
         out.ptr = (uint8_t*)p.data;
         out.pitch = p.rowPitchBytes;
         return out;
@@ -103,6 +112,13 @@ struct Checker {
         }
         return ownerIsRgb ? Check(p, name, required, nrd::Format::R32_SFLOAT) : FePlane{nullptr, 0};
     }
+};
+
+// the planes checked while one of these lives belong to the full-size class (on = false: an ordinary call, nothing changes)
+struct FullSize {
+    Checker& c;
+    FullSize(Checker& c_, bool on) : c(c_) { c.full = on; }
+    ~FullSize() { c.full = false; }
 };
 
 // a plane the chosen mode or set of outputs has no use for must be absent: a caller who passes it expects something the call will not do

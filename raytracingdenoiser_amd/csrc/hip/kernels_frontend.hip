@@ -6,6 +6,8 @@
 // nrdHipPackInputsSplit / nrdHipResolveOutputsSplit launch the kernels of those calls when every plane is RGBA32_SFLOAT, else the split twin of the kernel the call would have
 // taken: the same body instantiated with SPLIT = true, in which a colour / vector plane may hold 12-byte RGB32_SFLOAT texels (global_load_dwordx3 / global_store_dwordx3,
 // never a 16-byte access) and `.w` lives in an R32_SFLOAT plane of its own.
+// nrdHipPackInputsDecimated / nrdHipResolveOutputsUpsampled (quarter-resolution tracing) launch the kernels of the split calls when nothing is decimated / upsampled, else a
+// DECIMATED instantiation of the pack body (the G-buffer planes read at every second texel) and the two upsampling resolve kernels (nearest Z among the low texels around a pixel).
 //
 // Arithmetic: include/NRD.hip.h and nothing else -- its contract, and the reference text it is pinned to, is unfused IEEE fp32 with correctly rounded
 // division and square root. The product builds its device sources with -ffp-contract=on, hence the pragma below, in front of every include: no statement
@@ -339,19 +341,24 @@ __device__ __forceinline__ float ClampToHalf(float v) { return isnan(v) ? v : fm
 // SAMPLES (nrdHipPackInputsSamples): each signal is reduced over its sample layers (PackSignalSamples); the other kernels never look at `sa`.
 // SPLIT (nrdHipPackInputsSplit): the fp32 colour / vector planes may hold 12-byte RGB32_SFLOAT texels, `.w` in a plane of its own (`sp`, which the other kernels never look at).
 // The same body: only the loads differ.
-template <bool CHECKERBOARD, bool SAMPLES, bool SPLIT>
+// DECIMATED (nrdHipPackInputsDecimated with guideShift = 1, quarter-resolution tracing): w x h is the LOW size, that of everything traced and of every output; the G-buffer planes
+// (normalRoughness and its roughness companion, viewZ, materialID, motion, albedo, rf0) are full-size planes of which pixel ( x, y ) reads texel ( gx, gy ) = ( 2x, 2y ) -- inside
+// them because w = ( W + 1 ) >> 1, h = ( H + 1 ) >> 1 (held by the host). Only that load coordinate differs: the view vector of the demodulation is that of ( x, y ) in w x h.
+template <bool CHECKERBOARD, bool SAMPLES, bool SPLIT, bool DECIMATED = false>
 __device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& sa, const SplitArgs& sp, uint32_t diffCell, uint32_t frameIndex) {
+    static_assert(!(DECIMATED && CHECKERBOARD), "checkerboarding and decimation are not combined");
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
     const int w = a.w, h = a.h;
     if (x >= w || y >= h)
         return;
-    const float4 nr = LoadTexel<SPLIT>(a.normalRoughness, sp.roughness, sp.rgb, kSplitNormalRoughness, true, x, y, w, h);
-    const float viewZ = LoadR32F(AsPlane(a.viewZ, w, h), x, y) * a.viewZScale;
+    const int gx = DECIMATED ? x << 1 : x, gy = DECIMATED ? y << 1 : y;
+    const float4 nr = LoadTexel<SPLIT>(a.normalRoughness, sp.roughness, sp.rgb, kSplitNormalRoughness, true, gx, gy, w, h);
+    const float viewZ = LoadR32F(AsPlane(a.viewZ, w, h), gx, gy) * a.viewZScale;
     const float3 N = Xyz(nr);
     const float roughness = nr.w;
 
     if (a.outNormalRoughness.ptr) {
-        const float materialID = a.materialID.ptr ? LoadR32F(AsPlane(a.materialID, w, h), x, y) : 0.0f;
+        const float materialID = a.materialID.ptr ? LoadR32F(AsPlane(a.materialID, w, h), gx, gy) : 0.0f;
         *TexelPtr<NRD_NormalRoughnessTexel>(AsPlane(a.outNormalRoughness, w, h), x, y) = NRD_StoreNormalRoughnessTexel(NRD_FrontEnd_PackNormalAndRoughness(N, roughness, materialID));
     }
     if (a.outViewZ.ptr)
@@ -359,20 +366,20 @@ __device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& s
     if (a.outMv.ptr) {
         float4 mv;
         if (a.motionIsRG) {
-            const float2 m = *TexelPtr<const float2>(AsPlane(a.motion, w, h), x, y);
+            const float2 m = *TexelPtr<const float2>(AsPlane(a.motion, w, h), gx, gy);
             mv = make_float4(m.x, m.y, 0.0f, 0.0f);
         } else if (SPLIT && (sp.rgb & kSplitMotion)) {
-            const float3 m = LoadRGB32F(AsPlane(a.motion, w, h), x, y);
+            const float3 m = LoadRGB32F(AsPlane(a.motion, w, h), gx, gy);
             mv = make_float4(m.x, m.y, m.z, 0.0f);
         } else
-            mv = LoadRGBA32F(AsPlane(a.motion, w, h), x, y);
+            mv = LoadRGBA32F(AsPlane(a.motion, w, h), gx, gy);
         StoreRGBA16F(AsPlane(a.outMv, w, h), x, y, make_float4(ClampToHalf(mv.x), ClampToHalf(mv.y), ClampToHalf(mv.z), ClampToHalf(mv.w)));
     }
 
     float3 diffFactor = make_float3(1.0f, 1.0f, 1.0f), specFactor = diffFactor;
     if (a.demodulate) {
         const float3 V = ViewVector(a.camera, x, y, w, h, viewZ);
-        NRD_MaterialFactors(N, V, LoadColour<SPLIT>(a.albedo, sp.rgb, kSplitAlbedo, x, y, w, h), LoadColour<SPLIT>(a.rf0, sp.rgb, kSplitRf0, x, y, w, h), roughness, diffFactor, specFactor);
+        NRD_MaterialFactors(N, V, LoadColour<SPLIT>(a.albedo, sp.rgb, kSplitAlbedo, gx, gy, w, h), LoadColour<SPLIT>(a.rf0, sp.rgb, kSplitRf0, gx, gy, w, h), roughness, diffFactor, specFactor);
     }
     const bool diffHere = !CHECKERBOARD || ((((uint32_t)x ^ (uint32_t)y) ^ frameIndex) & 1u) == diffCell;
     const int xo = CHECKERBOARD ? x >> 1 : x;
@@ -426,18 +433,28 @@ __global__ void __launch_bounds__(256) PackSamplesSplitKernel(const PackArgs a, 
     PackPixel<CHECKERBOARD, true, true>(a, sa, sp, diffCell, frameIndex);
 }
 
+// the decimated twins of the four kernels without checkerboarding (nrdHipPackInputsDecimated with guideShift = 1): the same body once more, the G-buffer planes read at ( 2x, 2y )
+__global__ void __launch_bounds__(256) PackDecimatedKernel(const PackArgs a) { PackPixel<false, false, false, true>(a, SampleArgs{}, SplitArgs{}, 0u, 0u); }
+
+__global__ void __launch_bounds__(256) PackDecimatedSamplesKernel(const PackArgs a, const SampleArgs sa) { PackPixel<false, true, false, true>(a, sa, SplitArgs{}, 0u, 0u); }
+
+__global__ void __launch_bounds__(256) PackDecimatedSplitKernel(const PackArgs a, const SplitArgs sp) { PackPixel<false, false, true, true>(a, SampleArgs{}, sp, 0u, 0u); }
+
+__global__ void __launch_bounds__(256) PackDecimatedSamplesSplitKernel(const PackArgs a, const SampleArgs sa, const SplitArgs sp) { PackPixel<false, true, true, true>(a, sa, sp, 0u, 0u); }
+
 __device__ __forceinline__ float4 LoadSignalTexel(const FePlane& p, bool wide, int x, int y, int w, int h) {
     return wide ? LoadRGBA32F(AsPlane(p, w, h), x, y) : LoadRGBA16F(AsPlane(p, w, h), x, y);
 }
 
-// one signal of the back end: returns the colour written to `out` (for the composition)
+// one signal of the back end: returns the colour written to `out` (for the composition). ( sx, sy ) in sw x sh: the texel of in0 / in1 the pixel takes its signal from -- the
+// pixel itself in the plain kernels, the nearest-Z texel of the low-size planes in the upsampling ones; everything else (viewZ, N, V, roughness, factor, the store) is the pixel's
 template <bool SPEC, bool SPLIT>
 __device__ __forceinline__ float3 ResolveSignal(uint32_t mode, uint32_t resolve, bool wide, const FePlane& in0, const FePlane& in1, const FePlane& out, const FePlane& outHitDist, uint32_t splitBits,
-    int x, int y, int w, int h, float viewZ, float3 N, float3 V, float roughness, float4 hitDistParams, bool denormalize, bool remodulate, float3 factor) {
+    int x, int y, int w, int h, int sx, int sy, int sw, int sh, float viewZ, float3 N, float3 V, float roughness, float4 hitDistParams, bool denormalize, bool remodulate, float3 factor) {
     const float r = SPEC ? roughness : 1.0f;
     const Plane o = AsPlane(out, w, h);
     if (mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION) {
-        float normHitDist = LoadR16Unorm(AsPlane(in0, w, h), x, y);
+        float normHitDist = LoadR16Unorm(AsPlane(in0, sw, sh), sx, sy);
         if (denormalize)
             normHitDist = REBLUR_GetHitDist(normHitDist, viewZ, hitDistParams, r);
         StoreR32F(o, x, y, normHitDist);
@@ -446,17 +463,17 @@ __device__ __forceinline__ float3 ResolveSignal(uint32_t mode, uint32_t resolve,
     float4 c;
     const bool reblur = mode != NRD_HIP_SIGNAL_RELAX_RADIANCE && mode != NRD_HIP_SIGNAL_RELAX_SH;
     if (mode == NRD_HIP_SIGNAL_REBLUR_RADIANCE)
-        c = REBLUR_BackEnd_UnpackRadianceAndNormHitDist(LoadSignalTexel(in0, wide, x, y, w, h));
+        c = REBLUR_BackEnd_UnpackRadianceAndNormHitDist(LoadSignalTexel(in0, wide, sx, sy, sw, sh));
     else if (mode == NRD_HIP_SIGNAL_RELAX_RADIANCE)
-        c = RELAX_BackEnd_UnpackRadiance(LoadSignalTexel(in0, wide, x, y, w, h));
+        c = RELAX_BackEnd_UnpackRadiance(LoadSignalTexel(in0, wide, sx, sy, sw, sh));
     else {
         NRD_SG sg;
         if (mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
-            sg = REBLUR_BackEnd_UnpackDirectionalOcclusion(LoadRGBA16Snorm(AsPlane(in0, w, h), x, y));
+            sg = REBLUR_BackEnd_UnpackDirectionalOcclusion(LoadRGBA16Snorm(AsPlane(in0, sw, sh), sx, sy));
         else if (mode == NRD_HIP_SIGNAL_REBLUR_SH)
-            sg = REBLUR_BackEnd_UnpackSh(LoadSignalTexel(in0, wide, x, y, w, h), LoadSignalTexel(in1, wide, x, y, w, h));
+            sg = REBLUR_BackEnd_UnpackSh(LoadSignalTexel(in0, wide, sx, sy, sw, sh), LoadSignalTexel(in1, wide, sx, sy, sw, sh));
         else
-            sg = RELAX_BackEnd_UnpackSh(LoadSignalTexel(in0, wide, x, y, w, h), LoadSignalTexel(in1, wide, x, y, w, h));
+            sg = RELAX_BackEnd_UnpackSh(LoadSignalTexel(in0, wide, sx, sy, sw, sh), LoadSignalTexel(in1, wide, sx, sy, sw, sh));
         float3 rgb;
         if (resolve == NRD_HIP_RESOLVE_SH)
             rgb = SPEC ? NRD_SH_ResolveSpecular(sg, N, V, roughness) : NRD_SH_ResolveDiffuse(sg, N);
@@ -507,10 +524,10 @@ __device__ __forceinline__ void ResolvePixel(const ResolveArgs& a, const Resolve
     }
     float3 diff = make_float3(0.0f, 0.0f, 0.0f), spec = diff;
     if (a.diffMode)
-        diff = ResolveSignal<false, SPLIT>(a.diffMode, a.diffResolve, a.diffWide != 0u, a.diffIn0, a.diffIn1, a.diffOut, sp.diffHitDist, sp.rgb, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
+        diff = ResolveSignal<false, SPLIT>(a.diffMode, a.diffResolve, a.diffWide != 0u, a.diffIn0, a.diffIn1, a.diffOut, sp.diffHitDist, sp.rgb, x, y, w, h, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
             a.remodulate != 0u, diffFactor);
     if (a.specMode)
-        spec = ResolveSignal<true, SPLIT>(a.specMode, a.specResolve, a.specWide != 0u, a.specIn0, a.specIn1, a.specOut, sp.specHitDist, sp.rgb, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
+        spec = ResolveSignal<true, SPLIT>(a.specMode, a.specResolve, a.specWide != 0u, a.specIn0, a.specIn1, a.specOut, sp.specHitDist, sp.rgb, x, y, w, h, x, y, w, h, viewZ, N, V, roughness, a.hitDistParams, a.denormalize != 0u,
             a.remodulate != 0u, specFactor);
     if (a.outComposed.ptr)
         StoreTexel<SPLIT>(a.outComposed, none, sp.rgb, kSplitComposed, x, y, w, h, make_float4(diff.x + spec.x, diff.y + spec.y, diff.z + spec.z, 0.0f));
@@ -525,6 +542,123 @@ __device__ __forceinline__ void ResolvePixel(const ResolveArgs& a, const Resolve
 __global__ void __launch_bounds__(256) ResolveOutputsKernel(const ResolveArgs a) { ResolvePixel<false>(a, ResolveSplitArgs{}); }
 
 __global__ void __launch_bounds__(256) ResolveOutputsSplitKernel(const ResolveArgs a, const ResolveSplitArgs sp) { ResolvePixel<true>(a, sp); }
+
+// ---- quarter-resolution denoising: the resolve of low-size OUT_* planes into the full-size frame (nrdHipResolveOutputsUpsampled; the rule is spelled out in NRDHip.h) -------
+// ResolveArgs::w x h is the FULL size: normalRoughness, viewZ, albedo, rf0 and every output are full-size planes and everything per pixel -- N, roughness, V, the material
+// factors, the depth and roughness of denormalizeHitDist -- is computed as ResolvePixel computes it. The signal planes (in0 / in1, shadow) and lowViewZ are lw x lh: low texel
+// ( i, j ) stands for full pixel ( 2i, 2j ). A pixel looks at the up to four low texels around it, takes the one nearest in depth ("nearest Z") and reads its signals there.
+// A 64-lane row touches 33 consecutive low texels of one or two rows; the row pair above / below re-reads them from the cache: no LDS.
+struct UpsampleArgs {
+    FePlane lowViewZ, outSource;
+    float viewZScale, denoisingRange, depthThreshold;
+    int32_t lw, lh;
+};
+
+constexpr uint32_t kNoSource = 255u;
+
+// zeros where a pixel has no source: the signal's output and its split hit-distance plane
+template <bool SPEC, bool SPLIT>
+__device__ __forceinline__ void StoreNoSignal(uint32_t mode, const FePlane& out, const FePlane& outHitDist, uint32_t splitBits, int x, int y, int w, int h) {
+    if (mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION)
+        StoreR32F(AsPlane(out, w, h), x, y, 0.0f);
+    else
+        StoreTexel<SPLIT>(out, outHitDist, splitBits, SPEC ? kSplitSpecOut : kSplitDiffOut, x, y, w, h, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+}
+
+template <bool SPLIT>
+__device__ __forceinline__ void ResolveUpsampledPixel(const ResolveArgs& a, const ResolveSplitArgs& sp, const UpsampleArgs& u) {
+    const FePlane none = {nullptr, 0};
+    const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
+    const int w = a.w, h = a.h, lw = u.lw, lh = u.lh;
+    if (x >= w || y >= h)
+        return;
+    const float viewZ = LoadR32F(AsPlane(a.viewZ, w, h), x, y);
+    float3 N = make_float3(0.0f, 0.0f, 1.0f);
+    float roughness = 1.0f;
+    if (a.normalRoughness.ptr) {
+        const float4 nr = NRD_FrontEnd_UnpackNormalAndRoughness(NRD_LoadNormalRoughnessTexel(*TexelPtr<const NRD_NormalRoughnessTexel>(AsPlane(a.normalRoughness, w, h), x, y)));
+        N = Xyz(nr);
+        roughness = nr.w;
+    }
+    float3 V = make_float3(0.0f, 0.0f, 0.0f);
+    if (a.needV) {
+        V = ViewVector(a.camera, x, y, w, h, viewZ);
+        if (a.outViewVector.ptr)
+            StoreTexel<SPLIT>(a.outViewVector, none, sp.rgb, kSplitViewVector, x, y, w, h, make_float4(V.x, V.y, V.z, 0.0f));
+    }
+    float3 diffFactor = make_float3(1.0f, 1.0f, 1.0f), specFactor = diffFactor;
+    if (a.needFactors) {
+        NRD_MaterialFactors(N, V, LoadColour<SPLIT>(a.albedo, sp.rgb, kSplitAlbedo, x, y, w, h), LoadColour<SPLIT>(a.rf0, sp.rgb, kSplitRf0, x, y, w, h), roughness, diffFactor, specFactor);
+        if (a.outDiffFactor.ptr)
+            StoreTexel<SPLIT>(a.outDiffFactor, none, sp.rgb, kSplitDiffFactor, x, y, w, h, make_float4(diffFactor.x, diffFactor.y, diffFactor.z, 0.0f));
+        if (a.outSpecFactor.ptr)
+            StoreTexel<SPLIT>(a.outSpecFactor, none, sp.rgb, kSplitSpecFactor, x, y, w, h, make_float4(specFactor.x, specFactor.y, specFactor.z, 0.0f));
+    }
+
+    // nearest Z: candidate k = a + 2b is low texel ( ( x >> 1 ) + a, ( y >> 1 ) + b ); an even coordinate has the one texel that stands for it, an odd one the two around it
+    const float Zf = fabsf(viewZ * u.viewZScale);
+    uint32_t source = kNoSource;
+    float best = 0.0f;
+    if (!(isnan(Zf) || Zf > u.denoisingRange)) {
+        const Plane lz = AsPlane(u.lowViewZ, lw, lh);
+        const int i0 = x >> 1, j0 = y >> 1;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            const int ca = (int)(k & 1u), cb = (int)(k >> 1);
+            const bool exists = (ca == 0 || (x & 1)) && (cb == 0 || (y & 1)) && i0 + ca < lw && j0 + cb < lh;
+            if (!exists)
+                continue;
+            const float Zk = fabsf(LoadR32F(lz, i0 + ca, j0 + cb) * u.viewZScale);
+            if (isnan(Zk) || Zk > u.denoisingRange)
+                continue;
+            const float dk = fabsf(Zk - Zf);
+            if (source == kNoSource || dk < best) { // (a tie stays with the lowest k)
+                source = k;
+                best = dk;
+            }
+        }
+        if (source != kNoSource && u.depthThreshold > 0.0f && best > u.depthThreshold * Zf)
+            source = kNoSource;
+    }
+    if (u.outSource.ptr)
+        StoreR8U(AsPlane(u.outSource, w, h), x, y, source);
+
+    if (source == kNoSource) { // sky at full size, or nothing denoised nearby: zeros, and no signal texel is loaded
+        if (a.diffMode)
+            StoreNoSignal<false, SPLIT>(a.diffMode, a.diffOut, sp.diffHitDist, sp.rgb, x, y, w, h);
+        if (a.specMode)
+            StoreNoSignal<true, SPLIT>(a.specMode, a.specOut, sp.specHitDist, sp.rgb, x, y, w, h);
+        if (a.outComposed.ptr)
+            StoreTexel<SPLIT>(a.outComposed, none, sp.rgb, kSplitComposed, x, y, w, h, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        if (a.outShadow.ptr) {
+            if (a.shadowIsRGBA)
+                StoreRGBA32F(AsPlane(a.outShadow, w, h), x, y, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            else
+                StoreR32F(AsPlane(a.outShadow, w, h), x, y, 0.0f);
+        }
+        return;
+    }
+    const int sx = (x >> 1) + (int)(source & 1u), sy = (y >> 1) + (int)(source >> 1);
+    float3 diff = make_float3(0.0f, 0.0f, 0.0f), spec = diff;
+    if (a.diffMode)
+        diff = ResolveSignal<false, SPLIT>(a.diffMode, a.diffResolve, a.diffWide != 0u, a.diffIn0, a.diffIn1, a.diffOut, sp.diffHitDist, sp.rgb, x, y, w, h, sx, sy, lw, lh, viewZ, N, V, roughness, a.hitDistParams,
+            a.denormalize != 0u, a.remodulate != 0u, diffFactor);
+    if (a.specMode)
+        spec = ResolveSignal<true, SPLIT>(a.specMode, a.specResolve, a.specWide != 0u, a.specIn0, a.specIn1, a.specOut, sp.specHitDist, sp.rgb, x, y, w, h, sx, sy, lw, lh, viewZ, N, V, roughness, a.hitDistParams,
+            a.denormalize != 0u, a.remodulate != 0u, specFactor);
+    if (a.outComposed.ptr)
+        StoreTexel<SPLIT>(a.outComposed, none, sp.rgb, kSplitComposed, x, y, w, h, make_float4(diff.x + spec.x, diff.y + spec.y, diff.z + spec.z, 0.0f));
+    if (a.outShadow.ptr) {
+        if (a.shadowIsRGBA)
+            StoreRGBA32F(AsPlane(a.outShadow, w, h), x, y, SIGMA_BackEnd_UnpackShadow(LoadRGBA8Unorm(AsPlane(a.shadow, lw, lh), sx, sy)));
+        else
+            StoreR32F(AsPlane(a.outShadow, w, h), x, y, SIGMA_BackEnd_UnpackShadow(LoadR8Unorm(AsPlane(a.shadow, lw, lh), sx, sy)));
+    }
+}
+
+__global__ void __launch_bounds__(256) ResolveUpsampledKernel(const ResolveArgs a, const UpsampleArgs u) { ResolveUpsampledPixel<false>(a, ResolveSplitArgs{}, u); }
+
+__global__ void __launch_bounds__(256) ResolveUpsampledSplitKernel(const ResolveArgs a, const ResolveSplitArgs sp, const UpsampleArgs u) { ResolveUpsampledPixel<true>(a, sp, u); }
 
 // ---- the high-quality resolve of an SH denoiser (nrdHipResolveOutputsEx with reJitter): SG / SH resolve, NRD_SG_ReJitter, remodulation ---------------
 // NRD_SG_ReJitter is the one stencil of the back end: it wants viewZ and the decoded normal of the four edge neighbours. NRD_REJITTER_TILE = 1 (shipped; DESIGN.md
@@ -710,8 +844,9 @@ void FrontEndSignal(Checker& c, const NrdHipFrontEndSignal& s, const char* name,
 }
 
 // hitDistDesc: the signal's companion of NrdHipBackEndSplit (an absent plane for the old calls); outBit: the kSplit* bit of its output
+// upsampled: nrdHipResolveOutputsUpsampled -- in0 / in1 are low-size planes, the output and its companion full-size ones
 void BackEndSignal(Checker& c, const NrdHipBackEndSignal& s, const char* name, const NrdHipPlaneDesc& hitDistDesc, uint32_t outBit, FePlane& in0, FePlane& in1, FePlane& out, FePlane& outHitDist,
-    uint32_t& wide) {
+    uint32_t& wide, bool upsampled = false) {
     using F = nrd::Format;
     const std::string n(name), companion = "split: " + n + "HitDist";
     if (s.mode == NRD_HIP_SIGNAL_NONE) {
@@ -731,6 +866,7 @@ void BackEndSignal(Checker& c, const NrdHipBackEndSignal& s, const char* name, c
         if (!c.Failed() && s.in1.format != s.in0.format)
             c.Error(nrd::Result::INVALID_ARGUMENT, (n + ".in1").c_str(), "SH0 and SH1 must have the same format");
     }
+    FullSize outputs(c, upsampled);
     if (s.mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION) {
         out = c.Check(s.out, (n + ".out").c_str(), "the signal's mode needs it", F::R32_SFLOAT);
         if (hitDistDesc.data)
@@ -761,7 +897,9 @@ uint32_t CheckSamples(const NrdHipSignalSamples& s, uint32_t mode, const char* n
 }
 
 // split != nullptr or splitEntry: nrdHipPackInputsSplit -- RGB32_SFLOAT planes and their companions are accepted
-uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, const NrdHipFrontEndSplit* split, bool splitEntry, void* hipStream) {
+// decimated: nrdHipPackInputsDecimated with guideShift = 1 -- the G-buffer planes form the full-size class of the checker, everything else the low-size one
+uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, const NrdHipFrontEndSplit* split, bool splitEntry, void* hipStream,
+    bool decimated = false) {
     using F = nrd::Format;
     static const NrdHipFrontEndSplit noSplit = {};
     const NrdHipFrontEndSplit& sd = split ? *split : noSplit;
@@ -772,6 +910,8 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
     const uint32_t checkerboardMode = options ? options->checkerboardMode : 0u;
     if (checkerboardMode > (uint32_t)nrd::CheckerboardMode::WHITE)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsEx: options: unknown checkerboardMode");
+    if (decimated && checkerboardMode)
+        return Fail(nrd::Result::UNSUPPORTED, "nrdHipPackInputsDecimated: options: checkerboardMode: checkerboarding combined with decimation (guideShift = 1) is out of scope");
     if (checkerboardMode && d->diffuse.mode == NRD_HIP_SIGNAL_NONE && d->specular.mode == NRD_HIP_SIGNAL_NONE)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsEx: options: checkerboardMode without a diffuse or a specular signal to checkerboard");
     SampleArgs sa = {};
@@ -788,27 +928,36 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
         sa.trim = samples->hitDistTrimThreshold;
     }
     const bool multiSample = sa.diffNum > 1u || sa.specNum > 1u || sa.trim > 0.0f; // else: the kernels of nrdHipPackInputsEx, the same bytes, no extra loads
-    const char* entry = splitEntry ? "nrdHipPackInputsSplit" : "nrdHipPackInputs";
+    const char* entry = decimated ? "nrdHipPackInputsDecimated" : splitEntry ? "nrdHipPackInputsSplit" : "nrdHipPackInputs";
     Checker c{entry};
     c.split = splitEntry;
     PackArgs a = {};
     SplitArgs sp = {};
-    a.normalRoughness = c.CheckColour(d->normalRoughness, "normalRoughness", "required", kSplitNormalRoughness);
-    sp.roughness = c.CheckCompanion(sd.roughness, "split: roughness", (c.rgb & kSplitNormalRoughness) != 0u, "normalRoughness is RGB32_SFLOAT: the roughness comes from this plane", "normalRoughness");
-    a.viewZ = c.Check(d->viewZ, "viewZ", "required", F::R32_SFLOAT);
-    a.materialID = c.Check(d->materialID, "materialID", nullptr, F::R32_SFLOAT);
+    {
+        FullSize guides(c, decimated);
+        a.normalRoughness = c.CheckColour(d->normalRoughness, "normalRoughness", "required", kSplitNormalRoughness);
+        sp.roughness = c.CheckCompanion(sd.roughness, "split: roughness", (c.rgb & kSplitNormalRoughness) != 0u, "normalRoughness is RGB32_SFLOAT: the roughness comes from this plane", "normalRoughness");
+        a.viewZ = c.Check(d->viewZ, "viewZ", "required", F::R32_SFLOAT);
+        a.materialID = c.Check(d->materialID, "materialID", nullptr, F::R32_SFLOAT);
+    }
     a.outNormalRoughness = c.Check(d->outNormalRoughness, "outNormalRoughness", nullptr, kNormalRoughnessFormat);
     a.outViewZ = c.Check(d->outViewZ, "outViewZ", nullptr, F::R32_SFLOAT);
     a.outMv = c.Check(d->outMv, "outMv", nullptr, F::RGBA16_SFLOAT);
-    a.motion = c.CheckColour(d->motion, "motion", a.outMv.ptr ? "outMv needs it" : nullptr, kSplitMotion, F::RG32_SFLOAT);
+    {
+        FullSize guides(c, decimated);
+        a.motion = c.CheckColour(d->motion, "motion", a.outMv.ptr ? "outMv needs it" : nullptr, kSplitMotion, F::RG32_SFLOAT);
+    }
     a.motionIsRG = d->motion.format == (uint32_t)F::RG32_SFLOAT;
     a.outPenumbra = c.Check(d->outPenumbra, "outPenumbra", nullptr, F::R16_SFLOAT);
     a.outTranslucency = c.Check(d->outTranslucency, "outTranslucency", nullptr, F::RGBA8_UNORM);
     a.occluder = c.Check(d->distanceToOccluder, "distanceToOccluder", a.outPenumbra.ptr || a.outTranslucency.ptr ? "outPenumbra / outTranslucency need it" : nullptr, F::R32_SFLOAT);
     a.translucency = c.CheckColour(d->translucency, "translucency", a.outTranslucency.ptr ? "outTranslucency needs it" : nullptr, kSplitTranslucency);
     const bool demodulate = d->albedo.data || d->rf0.data;
-    a.albedo = c.CheckColour(d->albedo, "albedo", demodulate ? "demodulation needs albedo and rf0" : nullptr, kSplitAlbedo);
-    a.rf0 = c.CheckColour(d->rf0, "rf0", demodulate ? "demodulation needs albedo and rf0" : nullptr, kSplitRf0);
+    {
+        FullSize guides(c, decimated);
+        a.albedo = c.CheckColour(d->albedo, "albedo", demodulate ? "demodulation needs albedo and rf0" : nullptr, kSplitAlbedo);
+        a.rf0 = c.CheckColour(d->rf0, "rf0", demodulate ? "demodulation needs albedo and rf0" : nullptr, kSplitRf0);
+    }
     FrontEndSignal(c, d->diffuse, "diffuse", sd.diffuseHitDist, kSplitDiffIn, kSplitDiffDir, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sp.diffHitDist);
     FrontEndSignal(c, d->specular, "specular", sd.specularHitDist, kSplitSpecIn, kSplitSpecDir, a.specIn, a.specDir, a.specOut0, a.specOut1, sp.specHitDist);
     if (multiSample && samples && splitEntry) { // the same rules, in dwords where the stack holds RGB32_SFLOAT texels, and for the companions
@@ -830,6 +979,8 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
         CheckLayerBytes(c, sa.specDirLayer = samples->specular.directionLayerBytes, a.specDir, sa.specNum, "samples: specular.directionLayerBytes");
         c.entry = entry;
     }
+    if (decimated && !c.Failed() && !c.w) // (every plane given is a G-buffer plane: nothing has the low size)
+        c.Error(nrd::Result::INVALID_ARGUMENT, "descriptor", "no low-size plane: no output and no signal");
     if (demodulate)
         Camera(c, d->commonSettings, "demodulation needs the frame's camera", a.camera);
     if (c.Failed())
@@ -844,7 +995,17 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
     a.h = c.h;
     t_LastError.clear();
     const dim3 grid((c.w + 63u) / 64u, (c.h + 3u) / 4u), block(64, 4);
-    if (c.rgb) { // something to split: the twins. (Else the kernels of the old calls: the same code, the same bytes.)
+    if (decimated) { // the decimated twins: plain, samples and their split forms (checkerboarding was refused above)
+        sp.rgb = c.rgb;
+        if (c.rgb && multiSample)
+            hipLaunchKernelGGL(PackDecimatedSamplesSplitKernel, grid, block, 0, (hipStream_t)hipStream, a, sa, sp);
+        else if (c.rgb)
+            hipLaunchKernelGGL(PackDecimatedSplitKernel, grid, block, 0, (hipStream_t)hipStream, a, sp);
+        else if (multiSample)
+            hipLaunchKernelGGL(PackDecimatedSamplesKernel, grid, block, 0, (hipStream_t)hipStream, a, sa);
+        else
+            hipLaunchKernelGGL(PackDecimatedKernel, grid, block, 0, (hipStream_t)hipStream, a);
+    } else if (c.rgb) { // something to split: the twins. (Else the kernels of the old calls: the same code, the same bytes.)
         sp.rgb = c.rgb;
         const uint32_t diffCell = checkerboardMode == (uint32_t)nrd::CheckerboardMode::BLACK ? 0u : 1u, frameIndex = options ? options->frameIndex & 1u : 0u;
         if (multiSample && checkerboardMode)
@@ -886,10 +1047,18 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsSplit
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputs(const NrdHipFrontEndDesc* d, void* hipStream) { return nrdHipPackInputsEx(d, nullptr, hipStream); }
 
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsDecimated(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples,
+    const NrdHipFrontEndSplit* split, uint32_t guideShift, void* hipStream) {
+    if (guideShift > 1u)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsDecimated: guideShift: 0 (the call is nrdHipPackInputsSplit) or 1 (G-buffer planes of twice the size, read at every second texel)");
+    return PackInputs(d, options, samples, split, true, hipStream, guideShift == 1u);
+}
+
 namespace {
 
 // splitEntry: nrdHipResolveOutputsSplit -- RGB32_SFLOAT planes and the hit-distance companions are accepted
-uint32_t ResolveOutputs(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* options, const NrdHipBackEndSplit* split, bool splitEntry, void* hipStream) {
+// up: nrdHipResolveOutputsUpsampled -- the signal planes, the shadow and up->lowViewZ form the low-size class of the checker, everything else the full-size one
+uint32_t ResolveOutputs(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* options, const NrdHipBackEndSplit* split, bool splitEntry, void* hipStream, const NrdHipBackEndUpsample* up = nullptr) {
     using F = nrd::Format;
     static const NrdHipBackEndSplit noSplit = {};
     const NrdHipBackEndSplit& sd = split ? *split : noSplit;
@@ -906,15 +1075,28 @@ uint32_t ResolveOutputs(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* 
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsEx: options: reJitter scales a resolved colour: the resolve of both signals must be SH or SG, not SG_EXTRACT_COLOR");
     if (!reJitter && options && options->outReJitterScale.data)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsEx: options: outReJitterScale: given without reJitter");
-    Checker c{splitEntry ? "nrdHipResolveOutputsSplit" : "nrdHipResolveOutputs"};
+    const bool upsampled = up != nullptr;
+    if (upsampled && reJitter)
+        return Fail(nrd::Result::UNSUPPORTED, "nrdHipResolveOutputsUpsampled: options: reJitter: re-jittering needs full-size SG neighbours; combined with upsampling it is out of scope");
+    if (upsampled && up->reserved)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsUpsampled: upsample: reserved: must be 0");
+    if (upsampled && !(up->depthThreshold >= 0.0f && up->depthThreshold <= 3.402823466e+38f)) // (a NaN fails every comparison)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipResolveOutputsUpsampled: upsample: depthThreshold: NaN, negative or infinite");
+    Checker c{upsampled ? "nrdHipResolveOutputsUpsampled" : splitEntry ? "nrdHipResolveOutputsSplit" : "nrdHipResolveOutputs"};
     c.split = splitEntry;
     ReJitterArgs ra = {};
     ResolveArgs& a = ra.r;
     ResolveSplitArgs sp = {};
-    BackEndSignal(c, ds, "diffuse", sd.diffuseHitDist, kSplitDiffOut, a.diffIn0, a.diffIn1, a.diffOut, sp.diffHitDist, a.diffWide);
-    BackEndSignal(c, ss, "specular", sd.specularHitDist, kSplitSpecOut, a.specIn0, a.specIn1, a.specOut, sp.specHitDist, a.specWide);
+    BackEndSignal(c, ds, "diffuse", sd.diffuseHitDist, kSplitDiffOut, a.diffIn0, a.diffIn1, a.diffOut, sp.diffHitDist, a.diffWide, upsampled);
+    BackEndSignal(c, ss, "specular", sd.specularHitDist, kSplitSpecOut, a.specIn0, a.specIn1, a.specOut, sp.specHitDist, a.specWide, upsampled);
     a.shadow = c.Check(d->shadow, "shadow", d->outShadow.data ? "outShadow needs it" : nullptr, F::R8_UNORM, F::RGBA8_UNORM);
     a.shadowIsRGBA = d->shadow.format == (uint32_t)F::RGBA8_UNORM;
+    UpsampleArgs ua = {};
+    if (upsampled)
+        ua.lowViewZ = c.Check(up->lowViewZ, "upsample: lowViewZ", "required: the IN_VIEWZ plane the denoiser ran with", F::R32_SFLOAT);
+    FullSize outputsAndGuides(c, upsampled); // from here on every plane is a full-size one
+    if (upsampled)
+        ua.outSource = c.Check(up->outSource, "upsample: outSource", nullptr, F::R8_UINT);
     a.outShadow = c.Check(d->outShadow, "outShadow", nullptr, a.shadowIsRGBA ? F::RGBA32_SFLOAT : F::R32_SFLOAT);
     a.outComposed = c.CheckColour(d->outComposed, "outComposed", nullptr, kSplitComposed);
     a.outViewVector = c.CheckColour(d->outViewVector, "outViewVector", nullptr, kSplitViewVector);
@@ -931,15 +1113,18 @@ uint32_t ResolveOutputs(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* 
     if (a.outComposed.ptr && !(carriesColour(ds) && carriesColour(ss)) && !c.Failed())
         c.Error(nrd::Result::INVALID_ARGUMENT, "outComposed", "needs a diffuse and a specular signal that carry a colour");
     a.normalRoughness = c.Check(d->normalRoughness, "normalRoughness", needN ? "the chosen resolves / remodulation / specular hit distance need N and the roughness" : nullptr, kNormalRoughnessFormat);
-    a.viewZ = c.Check(d->viewZ, "viewZ", needV || (d->denormalizeHitDist && anyReblur) ? "the view vector / denormalizeHitDist need it" : nullptr, F::R32_SFLOAT);
+    a.viewZ = c.Check(d->viewZ, "viewZ", upsampled ? "required: nearest-Z upsampling compares it with lowViewZ" : needV || (d->denormalizeHitDist && anyReblur) ? "the view vector / denormalizeHitDist need it" : nullptr,
+        F::R32_SFLOAT);
     a.albedo = c.CheckColour(d->albedo, "albedo", needFactors ? "remodulation needs albedo and rf0" : nullptr, kSplitAlbedo);
     a.rf0 = c.CheckColour(d->rf0, "rf0", needFactors ? "remodulation needs albedo and rf0" : reJitter ? "reJitter needs Rf0" : nullptr, kSplitRf0);
     if (reJitter)
         ra.outScale = c.Check(options->outReJitterScale, "outReJitterScale", nullptr, F::RG32_SFLOAT);
+    c.full = false; // (Camera holds rectSize against w x h: the low size of an upsampled call)
     if (!c.Failed() && !c.w)
         c.Error(nrd::Result::INVALID_ARGUMENT, "descriptor", "nothing to do: no signal, no shadow, no output plane");
-    if (needV)
-        Camera(c, d->commonSettings, "the chosen resolves / remodulation / outViewVector need the frame's camera", a.camera);
+    if (needV || upsampled)
+        Camera(c, d->commonSettings, upsampled ? "required: viewZScale, denoisingRange and the camera of the frame the denoiser ran with" : "the chosen resolves / remodulation / outViewVector need the frame's camera",
+            a.camera);
     if (c.Failed())
         return c.result;
     a.diffMode = ds.mode;
@@ -955,6 +1140,22 @@ uint32_t ResolveOutputs(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* 
     a.h = c.h;
     t_LastError.clear();
     sp.rgb = c.rgb;
+    if (upsampled) { // one thread per FULL pixel
+        const nrd::CommonSettings& cs = *(const nrd::CommonSettings*)d->commonSettings;
+        ua.viewZScale = cs.viewZScale;
+        ua.denoisingRange = cs.denoisingRange;
+        ua.depthThreshold = up->depthThreshold;
+        ua.lw = c.w;
+        ua.lh = c.h;
+        a.w = c.fw;
+        a.h = c.fh;
+        const dim3 grid((c.fw + 63u) / 64u, (c.fh + 3u) / 4u), block(64, 4);
+        if (c.rgb)
+            hipLaunchKernelGGL(ResolveUpsampledSplitKernel, grid, block, 0, (hipStream_t)hipStream, a, sp, ua);
+        else
+            hipLaunchKernelGGL(ResolveUpsampledKernel, grid, block, 0, (hipStream_t)hipStream, a, ua);
+        return hipGetLastError() == hipSuccess ? (uint32_t)nrd::Result::SUCCESS : Fail(nrd::Result::FAILURE, "nrdHipResolveOutputsUpsampled: the kernel launch failed");
+    }
     const dim3 reJitterGrid((c.w + (uint32_t)kReJitterTileW - 1u) / (uint32_t)kReJitterTileW, (c.h + (uint32_t)kReJitterTileH - 1u) / (uint32_t)kReJitterTileH);
     if (c.rgb && reJitter) // something to split: the twins. (Else the kernels of the old calls: the same code, the same bytes.)
         hipLaunchKernelGGL(ReJitterSplitKernel, reJitterGrid, dim3(kReJitterTileW, kReJitterTileH), 0, (hipStream_t)hipStream, ra, sp);
@@ -979,3 +1180,8 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsS
 }
 
 extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputs(const NrdHipBackEndDesc* d, void* hipStream) { return nrdHipResolveOutputsEx(d, nullptr, hipStream); }
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipResolveOutputsUpsampled(const NrdHipBackEndDesc* d, const NrdHipBackEndOptions* options, const NrdHipBackEndSplit* split,
+    const NrdHipBackEndUpsample* upsample, void* hipStream) {
+    return ResolveOutputs(d, options, split, true, hipStream, upsample);
+}

@@ -208,7 +208,10 @@ def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.Checkerboa
     checkerboard_mode (api.CheckerboardMode) other than OFF: the noisy signals are traced for every other pixel of frame `frame_index` (CommonSettings::frameIndex) and their
     texels go to the left half of the signal planes, whose other texels are left as they are (NRDHip.h nrdHipPackInputsEx). A signal given as a stack of sample layers
     ([N, H, W, 4]: many paths per pixel) or hit_dist_trim != 0 goes through nrdHipPackInputsSamples, which reduces the layers by the reference's rules in the same launch;
-    every other call is the call it was."""
+    every other call is the call it was.
+    guide_shift=1 (quarter-resolution tracing, NRDHip.h nrdHipPackInputsDecimated): normal_roughness, viewz, material_id, motion, albedo and rf0 are the FULL-size [H, W] G-buffer,
+    read at every second texel of every second row; the signals, distance_to_occluder and translucency are traced at the low size [(H + 1) >> 1, (W + 1) >> 1], which is the size
+    of every packed plane returned; common_settings (demodulation) is that of the low-size frame."""
     given = inspect.signature(describe_pack).bind(normal_roughness, viewz, *args, **kw).arguments
     in_place = given.get("in_place")
     in_place = PACK_IN_PLACE if in_place is None else bool(in_place)
@@ -218,7 +221,14 @@ def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.Checkerboa
         lib = kw.get("lib") or api.load_library()
         layered = any(_layers(sig[k])[0] for sig in (given.get("diffuse"), given.get("specular")) if sig for k in ("radiance_hitdist", "direction") if sig.get(k) is not None)
         split = pack_split(normal_roughness, given.get("diffuse"), given.get("specular")) if in_place else None
-        if split is not None and _anything_split(d, split):  # three-channel planes and (xyz, w) pairs where they lie (NRDHip.h nrdHipPackInputsSplit): no copy, no allocation
+        if int(given.get("guide_shift", 0)) != 0:  # quarter-resolution tracing (NRDHip.h nrdHipPackInputsDecimated): one entry point for plain, sampled and split planes
+            in_place_here = split is not None and _anything_split(d, split)
+            samples = pack_samples(given.get("diffuse"), given.get("specular"), given.get("hit_dist_trim", 0.0), in_place=in_place_here)
+            options = pack_options(checkerboard_mode, frame_index)
+            split = split if in_place_here else api.HipFrontEndSplit()
+            _check(lib, lib.nrdHipPackInputsDecimated(C.byref(d), C.byref(options), C.byref(samples), C.byref(split), int(given["guide_shift"]), _stream(viewz, kw.get("stream"))),
+                   "nrdHipPackInputsDecimated")
+        elif split is not None and _anything_split(d, split):  # three-channel planes and (xyz, w) pairs where they lie (NRDHip.h nrdHipPackInputsSplit): no copy, no allocation
             samples = pack_samples(given.get("diffuse"), given.get("specular"), given.get("hit_dist_trim", 0.0), in_place=True)
             options = pack_options(checkerboard_mode, frame_index)
             _check(lib, lib.nrdHipPackInputsSplit(C.byref(d), C.byref(options), C.byref(samples), C.byref(split), _stream(viewz, kw.get("stream"))), "nrdHipPackInputsSplit")
@@ -289,7 +299,7 @@ def _anything_split(d, split):
 
 def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffuse=None, specular=None, albedo=None, rf0=None, distance_to_occluder=None, translucency=None,
                   common_settings=None, hit_dist_params=HIT_DIST_PARAMS, viewz_scale=1.0, tan_of_light_angular_radius=0.0, out=None, stream=None, lib=None, hit_dist_trim=0.0,
-                  in_place=None):
+                  in_place=None, guide_shift=0):
     """The descriptor of one nrdHipPackInputs launch, without launching: (packed planes, api.HipFrontEndDesc, arrays the descriptor points into besides its arguments) -- for a
     caller that launches the same frame layout repeatedly through the C-ABI itself. fp32 inputs: normal_roughness [H, W, 4] (or a (normal [H, W, 3], roughness [H, W]) pair), viewz [H, W], material_id [H, W],
     motion [H, W, 4] or [H, W, 2], albedo / rf0 / translucency [H, W, 4] or [H, W, 3], distance_to_occluder [H, W]; diffuse / specular: dict(mode=SignalMode,
@@ -301,13 +311,18 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
     in_place=True (default here: False -- the descriptor then suits nrdHipPackInputs / Ex / Samples): three-channel arrays, (xyz, w) pairs and [N, H, W, 3] stacks are not widened;
     the descriptor points at the caller's own arrays as RGB32_SFLOAT planes and is for nrdHipPackInputsSplit alone, with pack_split(...) for the w halves and
     pack_samples(..., in_place=True): a relaunch after the caller refreshed its tensors packs the new values. (A bare [H, W, 3] normal_roughness / radiance_hitdist, which has
-    no w anywhere, is still widened with zeros.) A signal in the occlusion mode may give radiance_hitdist=(None, hit_dist)."""
+    no w anywhere, is still widened with zeros.) A signal in the occlusion mode may give radiance_hitdist=(None, hit_dist).
+    guide_shift=1: the descriptor is for nrdHipPackInputsDecimated( ..., guideShift = 1 ) alone -- the G-buffer arguments are full-size, everything else and every output low-size
+    (see pack_inputs)."""
     in_place = bool(in_place)
     d = api.HipFrontEndDesc()
     keep = []  # widened copies must outlive the launch call
     nr, d.normalRoughness = _rgba_arg(normal_roughness, "normal_roughness", in_place, needs_w=True)
     keep.append(nr)
     h, w = viewz.shape
+    assert int(guide_shift) in (0, 1), "guide_shift: 0 or 1"
+    if int(guide_shift):  # the outputs have the low size
+        h, w = (h + 1) >> 1, (w + 1) >> 1
     d.viewZ = _fp32_plane(viewz, 1, "viewz")
     d.commonSettings = _settings_ptr(common_settings)
     d.hitDistParams[:] = hit_dist_params
@@ -373,13 +388,21 @@ def _packed_plane(t, what):
 def resolve_outputs(rejitter=False, **kw):
     """see describe_resolve; launches on `stream` (as pack_inputs) and returns the fp32 planes. rejitter=True (both signals in an SH mode, resolve SH or SG; needs rf0): the
     resolved colours are multiplied by NRD_SG_ReJitter before the remodulation (NRDHip.h nrdHipResolveOutputsEx); "rejitter_scale" in `want` adds the two factors, fp32 [H, W, 2].
-    channels=3 (describe_resolve) goes through nrdHipResolveOutputsSplit."""
+    channels=3 (describe_resolve) goes through nrdHipResolveOutputsSplit.
+    low_viewz= (quarter-resolution denoising, NRDHip.h nrdHipResolveOutputsUpsampled): the signal planes and the shadow are the LOW-size OUT_* planes of the denoiser and low_viewz the
+    IN_VIEWZ it ran with; normal_roughness, viewz, albedo and rf0 are full-size and so is every plane returned. Each full pixel takes its signal from the low texel around it that is
+    nearest in depth (depth_threshold > 0: and no further than depth_threshold * depth away, else it gets zeros); want_source=True adds "source", uint8 [H, W]: which of the four
+    texels (0..3), api.NO_SOURCE where none. common_settings is the denoiser's own (rectSize = the low size)."""
     like = next(t for t in (kw.get("shadow"), kw.get("viewz"), kw.get("normal_roughness"), (kw.get("diffuse") or {}).get("in0"), (kw.get("specular") or {}).get("in0")) if t is not None)
     with _stream_scope(like, kw.get("stream")):
         want = tuple(kw.get("want", ()))
         res, d, keep = describe_resolve(**dict(kw, want=tuple(n for n in want if n != "rejitter_scale")))
         lib = kw.get("lib") or api.load_library()
-        if int(kw.get("channels", 4)) == 3:
+        if kw.get("low_viewz") is not None:
+            options = resolve_options(res, kw["viewz"], rejitter=rejitter, want_scale="rejitter_scale" in want, out=kw.get("out"))
+            split, upsample = resolve_split(res), resolve_upsample(res, kw["low_viewz"], kw.get("depth_threshold", 0.0))
+            _check(lib, lib.nrdHipResolveOutputsUpsampled(C.byref(d), C.byref(options), C.byref(split), C.byref(upsample), _stream(like, kw.get("stream"))), "nrdHipResolveOutputsUpsampled")
+        elif int(kw.get("channels", 4)) == 3:
             options = resolve_options(res, like, rejitter=rejitter, want_scale="rejitter_scale" in want, out=kw.get("out"))
             split = resolve_split(res)
             _check(lib, lib.nrdHipResolveOutputsSplit(C.byref(d), C.byref(options), C.byref(split), _stream(like, kw.get("stream"))), "nrdHipResolveOutputsSplit")
@@ -413,27 +436,44 @@ def resolve_split(res):
     return split
 
 
+def resolve_upsample(res, low_viewz, depth_threshold=0.0):
+    """api.HipBackEndUpsample for nrdHipResolveOutputsUpsampled, next to the descriptor of describe_resolve(low_viewz=...): `res` is the dict it returned, whose "source" plane
+    (there with want_source) takes the chosen texel of every pixel"""
+    upsample = api.HipBackEndUpsample()
+    upsample.lowViewZ = _fp32_plane(low_viewz, 1, "low_viewz")
+    upsample.depthThreshold = float(depth_threshold)
+    if "source" in res:
+        upsample.outSource = _plane(res["source"], F.R8_UINT)
+    return upsample
+
+
 def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=None, viewz=None, albedo=None, rf0=None, common_settings=None, hit_dist_params=HIT_DIST_PARAMS,
-                     denormalize_hit_dist=False, remodulate=False, want=(), out=None, stream=None, lib=None, channels=4):
+                     denormalize_hit_dist=False, remodulate=False, want=(), out=None, stream=None, lib=None, channels=4, low_viewz=None, depth_threshold=0.0, want_source=False):
     """The descriptor of one nrdHipResolveOutputs launch, without launching: (fp32 planes, api.HipBackEndDesc, arrays it points into besides its arguments). diffuse / specular: dict(mode=SignalMode, resolve=ResolveMode, in0=OUT_*_RADIANCE_HITDIST / _SH0 / _HITDIST / DIRECTION_HITDIST array,
     in1=OUT_*_SH1 array) -- the arrays bound as outputs (fp16 / int16) or fp32 [H, W, 4]; shadow: the OUT_SHADOW_TRANSLUCENCY array (uint8 [H, W] or [H, W, 4]);
     normal_roughness / viewz: the packed IN_NORMAL_ROUGHNESS / IN_VIEWZ arrays; want: any of "composed", "view_vector", "factors". Returns fp32 arrays under
     "diffuse", "specular", "shadow", "composed", "view_vector", "diff_factor", "spec_factor".
     channels=3 (default 4): "diffuse", "specular", "composed", "view_vector", "diff_factor" and "spec_factor" are [H, W, 3] (RGB32_SFLOAT planes), the hit distances go to
     "diffuse_hit_dist" / "specular_hit_dist" [H, W] where `want` asks for them and nowhere otherwise, and albedo / rf0 given as [H, W, 3] are read where they lie; the
-    descriptor is then for nrdHipResolveOutputsSplit alone, with resolve_split(res)."""
+    descriptor is then for nrdHipResolveOutputsSplit alone, with resolve_split(res).
+    low_viewz given (see resolve_outputs): in0 / in1 / shadow and low_viewz are low-size arrays, viewz (required) and the other inputs full-size, and every output has the size of
+    viewz; want_source adds "source" (uint8 [H, W]). The descriptor is then for nrdHipResolveOutputsUpsampled alone, with resolve_split(res) and resolve_upsample(res, low_viewz,
+    depth_threshold)."""
     assert channels in (3, 4), "channels: 3 or 4"
     colour, colour_format = (3, F.RGB32_SFLOAT) if channels == 3 else (4, F.RGBA32_SFLOAT)
     d = api.HipBackEndDesc()
     like = next(t for t in (shadow, viewz, normal_roughness, (diffuse or {}).get("in0"), (specular or {}).get("in0")) if t is not None)
     h, w = like.shape[:2]
+    if low_viewz is not None:
+        assert viewz is not None, "the upsampled resolve needs the full-size viewz next to low_viewz"
+        h, w = viewz.shape[:2]
     keep, res = [], {}
     d.commonSettings = _settings_ptr(common_settings)
     d.hitDistParams[:] = hit_dist_params
     d.denormalizeHitDist, d.remodulate = int(bool(denormalize_hit_dist)), int(bool(remodulate))
 
-    def output(name, shape, fmt):
-        t = _reuse(out, name, like, shape, "float32")
+    def output(name, shape, fmt, dtype="float32"):
+        t = _reuse(out, name, like, shape, dtype)
         res[name] = t
         return _plane(t, fmt)
 
@@ -460,7 +500,7 @@ def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=
             output(which + "_hit_dist", (h, w), F.R32_SFLOAT)
     if shadow is not None:
         d.shadow = _packed_plane(shadow, "shadow")
-        d.outShadow = output("shadow", tuple(shadow.shape), F.R32_SFLOAT if shadow.ndim == 2 else F.RGBA32_SFLOAT)
+        d.outShadow = output("shadow", (h, w) + tuple(shadow.shape[2:]), F.R32_SFLOAT if shadow.ndim == 2 else F.RGBA32_SFLOAT)
     if "composed" in want:
         d.outComposed = output("composed", (h, w, colour), colour_format)
     if "view_vector" in want:
@@ -468,6 +508,9 @@ def describe_resolve(diffuse=None, specular=None, shadow=None, normal_roughness=
     if "factors" in want:
         d.outDiffFactor = output("diff_factor", (h, w, colour), colour_format)
         d.outSpecFactor = output("spec_factor", (h, w, colour), colour_format)
+    if want_source:
+        assert low_viewz is not None, "want_source: only the upsampled resolve (low_viewz=) has a source"
+        output("source", (h, w), F.R8_UINT, "uint8")
     return res, d, keep + [common_settings]
 
 

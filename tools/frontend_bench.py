@@ -18,6 +18,9 @@ answer: torch.isfinite over the four planes, masked with the range test, .all().
 --guides is a run of its own that adds the `guides` and `isa_guides` objects to the output file: nrdHipPackGuides on RGB32_SFLOAT position and positionPrev planes (36 B per pixel
 with IN_VIEWZ and IN_MV) against the copy rate of the same run, next to the four shadow-light calls of --shadow-lights on planes of the same size -- streaming kernels of the same
 shape, its yardstick; the whole set three times with the rows alternating, each row's spread over the rounds next to its number.
+--upsample is a run of its own that adds the `upsample` and `isa_upsample` objects to the output file: quarter-resolution denoising, REBLUR_DIFFUSE_SPECULAR radiance with
+remodulation. nrdHipResolveOutputsUpsampled from 1280 x 720 planes to 2560 x 1440 against the plain resolve of the same configuration at 2560 x 1440 and the copy rate, five
+alternating rounds, medians; and whole frames (pack + denoise + resolve, default settings) at full size and at quarter resolution.
 usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]] [--split]
        [--check-inputs] [--shadow-lights] [--guides]"""
 import argparse
@@ -764,6 +767,151 @@ def guides_main(args):
     print(json.dumps({"guides": rows, "copy_gigabytes_per_second": gbps.value, "lowest_shadow_light_fraction": yardstick, "run_to_run_spread": spread}))
 
 
+def upsample_isa():
+    """static facts about the kernels behind nrdHipResolveOutputsUpsampled and nrdHipPackInputsDecimated (the `isa_upsample` object of profiles/frontend_bench.json), as isa(),
+    next to the plain kernels they are twins of"""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_frontend.s")
+        flags = [f for f in B._flags(SRC) if f not in ("-x", "hip")]
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+    names = {"ResolveUpsampledKernel": "resolve_upsampled", "ResolveUpsampledSplitKernel": "resolve_upsampled_split", "ResolveOutputsKernel": "resolve", "PackDecimatedKernel": "pack_decimated",
+             "PackDecimatedSamplesKernel": "pack_decimated_samples", "PackDecimatedSplitKernel": "pack_decimated_split", "PackDecimatedSamplesSplitKernel": "pack_decimated_samples_split",
+             "PackInputsKernel": "pack"}
+    out = {}
+    for mangled, s in stats.items():
+        for kernel, name in names.items():
+            if re.search(r"\d+" + kernel + "E", mangled):
+                c = s["counter"]
+                out[name] = {"vgprs": s["vgpr"], "waves_per_simd": s["occ"], "scratch_bytes": s["scratch"], "lds_bytes": s["ldsb"], "valu": s["valu"], "salu": s["salu"], "vmem": s["vmem"],
+                             "global_load_dwordx4": c.get("global_load_dwordx4", 0), "global_load_dwordx2": c.get("global_load_dwordx2", 0), "global_load_dword": c.get("global_load_dword", 0),
+                             "global_store_dwordx4": c.get("global_store_dwordx4", 0), "global_store_byte": c.get("global_store_byte", 0)}
+    assert set(out) == set(names.values()), (sorted(out), list(stats))
+    return out
+
+
+def upsample_main(args):
+    """--upsample (see the module text). Times are device events around --reps back-to-back calls, per call; five rounds with the rows alternating, the median of each row."""
+    result = {"isa_upsample": upsample_isa()}
+    if args.isa_only:
+        print(json.dumps(result))
+        return
+    import statistics
+
+    import torch
+
+    from raytracingdenoiser_amd import api, frontend, scene, synth
+    from raytracingdenoiser_amd.executor import HipExecutor
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    W, H = args.width, args.height
+    w, h = (W + 1) >> 1, (H + 1) >> 1
+    lib, stream = api.load_library(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    R, S, name = api.ResourceType, frontend.SignalMode, "REBLUR_DIFFUSE_SPECULAR"
+    frame = synth.render_frame(W, H, 1, device="cuda", want=("reblur", "raw"))
+    raw = frame["raw"]
+    cat = lambda a, b: torch.cat([a, b.unsqueeze(-1)], -1).contiguous()
+    nr, viewz, motion = cat(raw["normal"], raw["roughness"]), frame["viewz"].contiguous(), frame["mv"].float().contiguous()
+    diff, spec = cat(raw["diff_radiance"], raw["diff_hit_dist"]), cat(raw["spec_radiance"], raw["spec_hit_dist"])
+    g = torch.Generator(device="cuda").manual_seed(31)
+    albedo, rf0 = (torch.rand(H, W, 4, device="cuda", generator=g).contiguous() * 0.9 + 0.05 for _ in range(2))
+    dec = lambda t: t[::2, ::2].contiguous()
+    sig = lambda d, s: dict(diffuse=dict(mode=S.REBLUR_RADIANCE, radiance_hitdist=d), specular=dict(mode=S.REBLUR_RADIANCE, radiance_hitdist=s))
+    cam = frame["camera"]
+    cs = {"full": scene.common_settings(cam, cam, W, H, 1), "low": scene.common_settings(cam, cam, w, h, 1)}  # halved: rectSize / resourceSize; the matrices are the frame's
+    packed = {"full": frontend.describe_pack(nr, viewz, material_id=raw["material_id"].contiguous(), motion=motion, **sig(diff, spec)),
+              "low": frontend.describe_pack(nr, viewz, material_id=raw["material_id"].contiguous(), motion=motion, guide_shift=1, **sig(dec(diff), dec(spec)))}
+    guides = frontend.describe_pack(nr, viewz)  # the quarter-resolution frame's full-size guide pack: IN_NORMAL_ROUGHNESS and IN_VIEWZ for the upsampled resolve
+    none = {"options": api.HipFrontEndOptions(), "samples": api.HipFrontEndSamples(), "split": api.HipFrontEndSplit()}
+
+    def check(code):
+        assert code == 0, lib.nrdHipGetLastFrontEndError()
+
+    pack = {"full": lambda: check(lib.nrdHipPackInputs(C.byref(packed["full"][1]), stream)), "guides": lambda: check(lib.nrdHipPackInputs(C.byref(guides[1]), stream)),
+            "low": lambda: check(lib.nrdHipPackInputsDecimated(C.byref(packed["low"][1]), C.byref(none["options"]), C.byref(none["samples"]), C.byref(none["split"]), 1, stream))}
+    chains = {}
+    for key, (cw, ch) in (("full", (W, H)), ("low", (w, h))):
+        inst = api.Instance([(0, scene.DENOISERS[name][0])])
+        ex = HipExecutor(inst, cw, ch)
+        outs = {rt: (torch.zeros((ch, cw, c), dtype=dtype, device="cuda"), fmt) for rt, dtype, c, fmt in scene.output_planes(name, cw, ch)}
+        for rt, (t, fmt) in outs.items():
+            ex.bind(rt, t, fmt)
+        ex.bind_packed(packed[key][0])
+        assert inst.set_denoiser_settings(0, scene.denoiser_settings(name, frame)) == api.Result.SUCCESS and inst.set_common_settings(cs[key]) == api.Result.SUCCESS
+        chains[key] = (inst, ex, outs)
+    signals = lambda outs: dict(diffuse=dict(mode=S.REBLUR_RADIANCE, in0=outs[R.OUT_DIFF_RADIANCE_HITDIST][0]), specular=dict(mode=S.REBLUR_RADIANCE, in0=outs[R.OUT_SPEC_RADIANCE_HITDIST][0]))
+    common = dict(normal_roughness=guides[0][R.IN_NORMAL_ROUGHNESS][0], viewz=guides[0][R.IN_VIEWZ][0], albedo=albedo, rf0=rf0, remodulate=True, want=("composed",))
+    plain_res, plain_desc, keep_a = frontend.describe_resolve(common_settings=cs["full"], **signals(chains["full"][2]), **common)
+    up_res, up_desc, keep_b = frontend.describe_resolve(common_settings=cs["low"], low_viewz=packed["low"][0][R.IN_VIEWZ][0], want_source=True, **signals(chains["low"][2]), **common)
+    up_struct, no_options, no_split = frontend.resolve_upsample(up_res, packed["low"][0][R.IN_VIEWZ][0]), api.HipBackEndOptions(), api.HipBackEndSplit()
+    resolve = lambda: check(lib.nrdHipResolveOutputs(C.byref(plain_desc), stream))
+    resolve_upsampled = lambda: check(lib.nrdHipResolveOutputsUpsampled(C.byref(up_desc), C.byref(no_options), C.byref(no_split), C.byref(up_struct), stream))
+
+    def frame_full():
+        pack["full"]()
+        chains["full"][1].denoise()
+        resolve()
+
+    def frame_quarter():
+        pack["guides"]()
+        pack["low"]()
+        chains["low"][1].denoise()
+        resolve_upsampled()
+
+    for _ in range(8):  # history builds up; every call has run once
+        frame_full()
+        frame_quarter()
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(up_res["composed"]).all()) and bool((up_res["source"][frame["viewz"].abs() <= cs["low"].denoisingRange] != api.NO_SOURCE).all())
+
+    def timed(fn, reps):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / reps
+
+    rows = {"resolve": (resolve, args.reps), "resolve_upsampled": (resolve_upsampled, args.reps), "pack_decimated": (pack["low"], args.reps), "pack": (pack["full"], args.reps),
+            "frame_full": (frame_full, max(args.reps // 10, 8)), "frame_quarter": (frame_quarter, max(args.reps // 10, 8))}
+    rounds = [{k: timed(fn, reps) for k, (fn, reps) in rows.items()} for _ in range(5)]
+    median = {k: statistics.median(r[k] for r in rounds) for k in rows}
+    spread = {k: (max(r[k] for r in rounds) - min(r[k] for r in rounds)) / min(r[k] for r in rounds) for k in rows}
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
+    # per FULL pixel, from the formats: IN_NORMAL_ROUGHNESS 4, viewZ 4, albedo 16, rf0 16; three RGBA32_SFLOAT outputs 48; the two RGBA16_SFLOAT signal planes 16 at full size,
+    # a quarter of that plus a quarter of lowViewZ (4) and outSource (1) when upsampling
+    bytes_px = {"resolve": 4 + 4 + 16 + 16 + 48 + 16, "resolve_upsampled": 4 + 4 + 16 + 16 + 48 + (16 + 4) / 4.0 + 1}
+    fraction = lambda k: bytes_px[k] * W * H / (median[k] * 1e-3) / 1e9 / gbps.value
+    result["upsample"] = dict(
+        device=torch.cuda.get_device_name(0), width=W, height=H, low_width=w, low_height=h, reps=args.reps, warmup=args.warmup, rounds=rounds, median_ms=median, spread=spread,
+        copy_gigabytes_per_second=gbps.value, bytes_per_full_pixel=bytes_px, resolve_fraction_of_copy_rate=fraction("resolve"), resolve_upsampled_fraction_of_copy_rate=fraction("resolve_upsampled"),
+        resolve_upsampled_over_resolve=median["resolve_upsampled"] / median["resolve"], frame_quarter_over_frame_full=median["frame_quarter"] / median["frame_full"],
+        what="REBLUR_DIFFUSE_SPECULAR, radiance mode, remodulation, outComposed; `resolve` is nrdHipResolveOutputs on full-size OUT_* planes, `resolve_upsampled` nrdHipResolveOutputsUpsampled "
+             "on the half-size ones (with outSource); frame_full = pack + denoise + resolve at full size, frame_quarter = full-size guide pack + decimated pack + denoise at the low size + "
+             "upsampled resolve; default denoiser settings, one synthetic frame repeated",
+        times_are="device events around back-to-back calls, per call (frames: a tenth of --reps); five rounds with the rows alternating; median_ms is the median over the rounds, "
+                  "spread = ( worst - best ) / best",
+        fraction_is_not="a share of HBM bandwidth: the working set partly fits the memory-side cache, as for pack and resolve (DESIGN.md section 3.4)")
+    for inst, ex, outs in chains.values():
+        ex.destroy()
+    record = {}
+    if os.path.exists(args.out):  # the other fields of the record are another run's: kept as they are
+        with open(args.out) as fp:
+            record = json.load(fp)
+    record.update(result)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fp:
+        json.dump(record, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps({k: v for k, v in result["upsample"].items() if k != "rounds"}))
+
+
 def synth_pack(raw, synth, torch):
     """the packing of synth.render_frame for REBLUR_DIFFUSE_SPECULAR on the raw values: its packers, elementwise torch operations with fp32 intermediates"""
     out = {"normal_roughness": synth.pack_normal_roughness(raw["normal"], raw["roughness"], raw["material"]).contiguous(), "viewz": raw["viewz"].clone(),
@@ -848,9 +996,13 @@ def main():
                     "--height say otherwise) against the copy rate and the same recipes as torch elementwise operations; adds the `shadow_lights` and `isa_shadow_lights` objects to --out")
     ap.add_argument("--guides", action="store_true", help="a run of its own: nrdHipPackGuides on RGB32_SFLOAT position planes against the copy rate, next to the four shadow-light "
                     "calls on planes of the same size, the whole set three times; adds the `guides` and `isa_guides` objects to --out and leaves its other fields as they are")
+    ap.add_argument("--upsample", action="store_true", help="a run of its own: nrdHipResolveOutputsUpsampled (half-size planes to --width x --height) against the plain resolve of the same "
+                    "configuration and the copy rate, and whole frames at full and at quarter resolution; adds the `upsample` and `isa_upsample` objects to --out")
     args = ap.parse_args()
     default_size = (1920, 1080) if args.shadow_lights else (2560, 1440)
     args.width, args.height = args.width or default_size[0], args.height or default_size[1]
+    if args.upsample:
+        return upsample_main(args)
     if args.guides:
         return guides_main(args)
     if args.shadow_lights:
