@@ -5,7 +5,8 @@
 // MI355X mapping. Both are LDS-tile stencils over a scalar luma plane plus per-pixel work:
 //   HistoryFix: 36x12 LDS tiles (32x8 outputs + halo 2) of the fast-history luma (one per signal) feed the 5x5 moments;
 //     the 5x5-minus-corners history reconstruction is a strided gather that only runs where fewer than
-//     historyFixFrameNum frames are accumulated (disocclusions), the 9x9 anti-firefly box (off by default) reads global.
+//     historyFixFrameNum frames are accumulated (disocclusions), two taps requested at a time; viewZ comes with the guide texel
+//     (IN_VIEWZ is not read); the 9x9 anti-firefly box (off by default) reads global.
 //   TemporalStabilization: 34x10 LDS tiles (halo 1) of luma = .x of the YCoCg signal, decoded once per workgroup, feed
 //     the 3x3 moments and the min/max clamp; the stabilised-luma history comes through Catmull-Rom fetches of an R16F plane.
 // LDS rows are padded to an odd dword count (37 / 35) so that the two rows a wave touches start in different banks.
@@ -33,7 +34,38 @@ constexpr int BORDER = 2;
 constexpr int BUF_X = TILE_X + 2 * BORDER; // 36
 constexpr int BUF_Y = TILE_Y + 2 * BORDER; // 12
 constexpr int BUF_STRIDE = BUF_X + 1;      // 37
+
+// The reconstruction stencil: 5x5 without its corners and its centre, 20 taps in the reference's order (j outer, i inner). Tap k has i + 2 / j + 2 in bits
+// 3k .. 3k + 2 of TAP_I / TAP_J: k is uniform, so a rolled loop over groups of taps gets its offsets from two scalar shifts.
+constexpr int TAPS = 20;
+constexpr uint64_t PackTaps(bool rows) {
+    uint64_t packed = 0;
+    int k = 0;
+    for (int j = -2; j <= 2; j++)
+        for (int i = -2; i <= 2; i++) {
+            if ((i == 0 && j == 0) || ((i < 0 ? -i : i) + (j < 0 ? -j : j) == 4))
+                continue;
+            packed |= uint64_t((rows ? j : i) + 2) << (3 * k++);
+        }
+    return packed;
+}
+constexpr uint64_t TAP_I = PackTaps(false), TAP_J = PackTaps(true);
 } // namespace hf
+
+// The reconstruction requests the texels of NRD_HF_TAP_BATCH taps (a divisor of 20) before it forms the first weight of the group: no tap address depends on another tap.
+// The taps are weighted and summed in the reference's order whatever the group size. Measured at 1440p (profiles/HISTORY.md "HistoryFix: tap batches"): the loop is bound
+// by the VALU issue of waves with a few young lanes (~110 instructions per tap and wave), not by its chain of loads -- two taps in flight are worth 1.7-2.3 us and fit the
+// 6 waves of the rolled loop (80 VGPRs, passes.h NRD_WAVES_REBLUR_HF); four or five need 91-99 VGPRs, and the wave they give up costs the pixels that reconstruct
+// nothing 1.3-6 us.
+// A/B builds (tools/build_variant.py): 0 = the rolled j / i loops, one tap in flight.
+#ifndef NRD_HF_TAP_BATCH
+#define NRD_HF_TAP_BATCH 2
+#endif
+static_assert(NRD_HF_TAP_BATCH >= 0 && (NRD_HF_TAP_BATCH == 0 || hf::TAPS % NRD_HF_TAP_BATCH == 0), "NRD_HF_TAP_BATCH: 0 or a divisor of 20");
+// Timing-only A/B builds, never the product: 0 compiles the tap loop out (what the reconstruction costs = the difference of the HistoryFix rows of two kernel traces)
+#ifndef NRD_HF_RECONSTRUCT
+#define NRD_HF_RECONSTRUCT 1
+#endif
 
 struct HfPlanes {
     Plane tiles, normalRoughness, data1, viewZ, inDiff, inSpec, inDiffFast, inSpecFast, outDiff, outSpec, outDiffFast, outSpecFast;
@@ -85,55 +117,115 @@ NRD_D typename ReblurSignal<KIND>::type HistoryFixSignal(const ReblurCB& c, cons
         if (SH)
             sh = F4(sh.x * sumw, sh.y * sumw, sh.z * sumw, IS_SPEC ? sh.w : sh.w * sumw);
 
-        for (int j = -2; j <= 2; j++) {
-            for (int i = -2; i <= 2; i++) {
-                if ((i == 0 && j == 0) || (abs(i) + abs(j) == 4))
-                    continue;
+        // material IDs are 0..3: a minimum >= 3 (the default is 4) makes every comparison hold. The loop exists twice, with and without the test (a uniform test inside
+        // the tap is if-converted: decode, compare and select would then run for every tap, 11 of its ~105 VALU instructions)
+        const float minMaterial = IS_SPEC ? c.gSpecMinMaterial : c.gDiffMinMaterial;
+        const bool compareMaterials = minMaterial < 3.0f;
 
+        // Per-pixel factors of the tap weights, formed once in front of the loop (the reciprocals are opaque to the optimiser, nrdmath.h Rcp: left inside the tap they are
+        // three v_rcp_f32 per tap). Same operations on the same values:
+        //   GetHitDistFactor( hs, frustumSize ) = Sat( hs * Rcp( frustumSize ) )
+        //   SmoothStep( 0.2 + b, 0.05 + b, d ) = SmoothStep01( Sat( ( d - ( 0.2 + b ) ) * Rcp( ( 0.05 + b ) - ( 0.2 + b ) ) ) ), b = LinearStep( 0.03, 0.05, roughness )
+        const float rcpFrustumSize = Rcp(s.frustumSize);
+        const float hitDistEdgeBase = LinearStep(0.03f, 0.05f, s.roughness);
+        const float hitDistEdge = 0.2f + hitDistEdgeBase;
+        const float hitDistRcpRange = Rcp((0.05f + hitDistEdgeBase) - hitDistEdge);
+
+        // A tap in two halves: the texels it reads, as requested, and what they add to the sums. The address of a clamped texel is always legal.
+        // The tap's viewZ rides in its guide texel: |IN_VIEWZ * gViewZScale| of this frame, the very product UnpackViewZ forms (kernels_common.hip DecodeGuidesKernel; the
+        // full-rect taps of PrePass and Blur rely on the same): one gather request less per tap.
+        struct Tap {
+            float4 normalViewZ; // the guide pair of LoadDecodedNormalRoughness (reblur_device.h), undecoded
+            uint32_t roughnessWord;
+            float2 data1;
+            S smp;
+            float4 sh;
+        };
+        auto reconstruct = [&](auto materials) {
+            constexpr bool MATERIALS = decltype(materials)::value;
+            auto requestTap = [&](int i, int j) {
+                const int sx = ClampI(s.px + i * stridei, 0, rw), sy = ClampI(s.py + j * stridei, 0, rh);
+                Tap t;
+                const uint32_t offset = TexelOffset(P.decodedNR.nz, sx, sy, 16u, true);
+                t.normalViewZ = *(const float4*)(P.decodedNR.nz.ptr + offset);
+                t.roughnessWord = 0u;
+                if (IS_SPEC || MATERIALS) // (a diffuse tap needs the word for its material ID alone)
+                    t.roughnessWord = *(const uint32_t*)(P.decodedNR.word.ptr + (offset >> 2));
+                t.data1 = F2(0.0f, 0.0f);
+                if (!PERF)
+                    t.data1 = LoadData1<DIFF, SPEC>(P.data1, sx, sy);
+                t.smp = Sig::Load(gIn_Signal, sx, sy);
+                t.sh = F4(0.0f);
+                if (SH)
+                    t.sh = LoadRGBA16F(gIn_Sh, sx, sy);
+                return t;
+            };
+            auto addTap = [&](const Tap& t, int i, int j) {
                 float2 uv = s.pixelUv + F2(float(i), float(j)) * stride * rectSizeInv;
-                int sx = ClampI(s.px + i * stridei, 0, rw), sy = ClampI(s.py + j * stridei, 0, rh);
 
-                float zs = UnpackViewZ(c, LoadR32F(P.viewZ, sx, sy));
-                float materialIDs;
-                float4 Ns = LoadDecodedNormalRoughness(P.decodedNR, sx, sy, materialIDs);
+                float zs = t.normalViewZ.w;
+                float4 Ns = F4(t.normalViewZ.x, t.normalViewZ.y, t.normalViewZ.z, DecodedRoughness(t.roughnessWord));
 
                 float angle = AcosApprox(Dot(Xyz(Ns), s.N));
                 float3 Xvs = ReconstructViewPosition(uv, ToF4(c.gFrustum), zs, NRD_ORTHO_MODE(c));
 
                 float w = IsInScreenNearest(uv);
                 w *= ComputeWeight(Dot(s.Nv, Xvs), geometryWeightParams.x, geometryWeightParams.y);
-                w *= CompareMaterials(s.materialID, materialIDs, IS_SPEC ? c.gSpecMinMaterial : c.gDiffMinMaterial) ? 1.0f : 0.0f;
+                if (MATERIALS)
+                    w *= CompareMaterials(s.materialID, DecodedMaterialID(t.roughnessWord), minMaterial) ? 1.0f : 0.0f;
                 w *= ComputeExponentialWeight(angle, normalWeightParam, 0.0f);
                 if (IS_SPEC)
                     w *= ComputeExponentialWeight(Ns.w * Ns.w, relaxedRoughnessWeightParams.x, relaxedRoughnessWeightParams.y);
 
-                if (!PERF) {
-                    float2 d1 = LoadData1<DIFF, SPEC>(P.data1, sx, sy);
-                    w *= 1.0f + (IS_SPEC ? d1.y : d1.x);
-                }
+                if (!PERF)
+                    w *= 1.0f + (IS_SPEC ? t.data1.y : t.data1.x);
 
-                S smp = Sig::Load(gIn_Signal, sx, sy);
-                smp = Select(w == 0.0f, Sig::Zero(), smp);
+                S smp = Select(w == 0.0f, Sig::Zero(), t.smp);
 
                 float hs = ExtractHitDist(smp) * hitDistScale;
-                float hsFactor = GetHitDistFactor(hs, s.frustumSize);
+                float hsFactor = Sat(hs * rcpFrustumSize);
                 w *= ComputeExponentialWeight(hsFactor, hitDistanceWeightParams.x, hitDistanceWeightParams.y);
 
                 if (IS_SPEC) {
                     float d = Div(Abs(hitDist - hs), Max(hitDist, hs) + 0.001f);
-                    float b = LinearStep(0.03f, 0.05f, s.roughness);
-                    w *= SmoothStep(0.2f + b, 0.05f + b, d);
+                    w *= SmoothStep01(Sat((d - hitDistEdge) * hitDistRcpRange));
                 }
 
                 sumw += w;
                 sig = Mad(smp, w, sig);
                 if (SH) {
-                    float4 t = LoadRGBA16F(gIn_Sh, sx, sy);
-                    t = Select(w == 0.0f, F4(0.0f), t);
-                    sh = F4(sh.x + t.x * w, sh.y + t.y * w, sh.z + t.z * w, IS_SPEC ? sh.w : sh.w + t.w * w);
+                    float4 tsh = Select(w == 0.0f, F4(0.0f), t.sh);
+                    sh = F4(sh.x + tsh.x * w, sh.y + tsh.y * w, sh.z + tsh.z * w, IS_SPEC ? sh.w : sh.w + tsh.w * w);
+                }
+            };
+
+#if !NRD_HF_RECONSTRUCT
+            (void)requestTap, (void)addTap;
+#elif NRD_HF_TAP_BATCH == 0
+            for (int j = -2; j <= 2; j++) {
+                for (int i = -2; i <= 2; i++) {
+                    if ((i == 0 && j == 0) || (abs(i) + abs(j) == 4))
+                        continue;
+                    addTap(requestTap(i, j), i, j);
                 }
             }
-        }
+#else
+#pragma unroll 1
+            for (int first = 0; first < hf::TAPS; first += NRD_HF_TAP_BATCH) {
+                Tap taps[NRD_HF_TAP_BATCH];
+#pragma unroll
+                for (int n = 0; n < NRD_HF_TAP_BATCH; n++)
+                    taps[n] = requestTap(int((hf::TAP_I >> (3 * (first + n))) & 7u) - 2, int((hf::TAP_J >> (3 * (first + n))) & 7u) - 2);
+#pragma unroll
+                for (int n = 0; n < NRD_HF_TAP_BATCH; n++)
+                    addTap(taps[n], int((hf::TAP_I >> (3 * (first + n))) & 7u) - 2, int((hf::TAP_J >> (3 * (first + n))) & 7u) - 2);
+            }
+#endif
+        };
+        if (compareMaterials)
+            reconstruct(std::true_type());
+        else
+            reconstruct(std::false_type());
 
         sumw = PositiveRcp(sumw);
         sig = sig * sumw;
@@ -201,7 +293,8 @@ NRD_D typename ReblurSignal<KIND>::type HistoryFixSignal(const ReblurCB& c, cons
 #define NRD_REBLUR_HF_ROTATE 1 // (0.0857 -> 0.0658 ms at 1440p, r04_q: the young pixels this pass reconstructs are the columns entering the screen -- on ONE XCD in the striped order)
 #endif
 template <bool DIFF, bool SPEC, bool PERF, int KIND, bool SH>
-__global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF) void ReblurHistoryFixKernel(ReblurCB c, HfPlanes P, RowRange rr) {
+// (performance mode keeps a bound of one wave less: at NRD_WAVES_REBLUR_HF = 6 its diffuse + specular kernel needs 8 B of scratch)
+__global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF - (PERF ? 1 : 0)) void ReblurHistoryFixKernel(ReblurCB c, HfPlanes P, RowRange rr) {
     typedef ReblurSignal<KIND> Sig;
     typedef typename Sig::type S;
     __shared__ float s_DiffLuma[DIFF ? hf::BUF_Y * hf::BUF_STRIDE : 1];
@@ -219,9 +312,8 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF) void 
     // the pixel's own inputs, requested in front of the tile fill (see ReblurTemporalStabilizationKernel; this pass ran 32 % above its L1-resident time)
     const int qx = min(px, rw), qy = min(max(py, 0), rh);
     const bool preSky = TileByteIsSky(tileBytes, tx >> 4); // a thread that stays has (qx, qy) = (px, py): one of the two tiles under this workgroup
-    const float preViewZ = LoadR32F(P.viewZ, qx, qy);
-    float preMaterialID;
-    const float4 preNormalAndRoughness = LoadDecodedNormalRoughness(P.decodedNR, qx, qy, preMaterialID);
+    float preMaterialID, preViewZ; // (viewZ = |IN_VIEWZ * gViewZScale| rides in the guide texel, here and at the taps: IN_VIEWZ itself is not read)
+    const float4 preNormalAndRoughness = LoadDecodedNormalRoughness(P.decodedNR, qx, qy, preMaterialID, preViewZ);
     const float2 preData1 = LoadData1<DIFF, SPEC>(P.data1, qx, qy);
     S preDiff = Sig::Zero(), preSpec = Sig::Zero();
     if (DIFF)
@@ -246,7 +338,7 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF) void 
     if (preSky)
         return;
     HfPixel s;
-    s.viewZ = UnpackViewZ(c, preViewZ);
+    s.viewZ = preViewZ;
     if (s.viewZ > c.gDenoisingRange)
         return;
 

@@ -17,7 +17,7 @@
 #define NRD_WAVES_REBLUR_SPATIAL 0
 #endif
 #ifndef NRD_WAVES_REBLUR_HF
-#define NRD_WAVES_REBLUR_HF 5 // 111 -> 84 VGPRs without scratch (6 would need 12 B of scratch)
+#define NRD_WAVES_REBLUR_HF 6 // 80 VGPRs without scratch with two reconstruction taps in flight (a bound of 5 lets the kernel take 86 and lose the wave); performance mode: see the kernel
 #endif
 #ifndef NRD_WAVES_REBLUR_TS
 #define NRD_WAVES_REBLUR_TS 0
