@@ -477,6 +477,83 @@ uint32_t nrdHipResolveOutputsSplit(const NrdHipBackEndDesc* desc, const NrdHipBa
 uint32_t nrdHipPackInputsDecimated(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, const NrdHipFrontEndSplit* split,
                                    uint32_t guideShift, void* hipStream);
 
+// One traced lobe per sample: the probabilistic diffuse / specular split (reference README "NOISY INPUTS": "Probabilistic split at primary hit": divide the radiance by the
+// selection probability, do not divide the hit distance, set the hit distance of the signal that was not traced to exactly 0, turn hitDistanceReconstructionMode and the
+// pre-pass on, and guarantee a valid sample in every 3x3 / 5x5 area). The application holds ONE traced plane -- what the one path of a pixel returned -- a byte per pixel
+// saying which lobe that path took and, optionally, the probability with which the specular lobe is chosen there; the call builds both packed signals from them in one launch,
+// each traced byte loaded once. lobes == NULL is exactly nrdHipPackInputsSplit( desc, options, NULL, split, stream ): the same kernels, the same bytes. The contract is the one
+// above: validated before the first HIP call, nothing enqueued on an error, no allocation, no synchronisation, one launch, capturable into a graph, errors through
+// nrdHipGetLastFrontEndError, the 32-bit limits for every plane and layer. Sample layer s of a plane of `lobes` is the plane with its `data` advanced by s x its layer stride
+// (64-bit); with samplesNum > 1 a stride is a multiple of 16 for an RGBA32_SFLOAT stack and of 4 for RGB32_SFLOAT, R32_SFLOAT and R8_UINT stacks, and >= rowPitchBytes x height.
+// With `lobes` given:
+//   INVALID_ARGUMENT, naming the field: a non-NULL { diffuse, specular }.radianceHitDist or .direction of the descriptor, or split->{ diffuse, specular }HitDist (the traced
+//       data would have two sources); a signal whose mode is NONE (both are produced); a missing lobe plane; a missing direction when a mode reads one; samplesNum > 64;
+//       a non-zero reserved; a bad layer stride
+//   UNSUPPORTED: a checkerboardMode other than OFF (checkerboarding is the other way to split); a format other than the one listed
+// The G-buffer inputs and outputs, demodulation, split->roughness and the SIGMA outputs behave as in the plain call. Decimation is out of scope.
+//
+// Per pixel and signal X (0 diffuse, 1 specular), in unfused fp32 with correctly rounded division, for s = 0 .. N - 1 in this order:
+//   1. ( rad, h ), dir where a mode of either signal reads a direction, the byte L and, when the probability plane is given, p are read from layer s, each once
+//   2. q = L == NRD_HIP_LOBE_SPECULAR ? p : 1 - p;  q = 1 without the probability plane
+//   3. the sample counts for X iff L == X and q > 0 (false for a NaN): then rad_s = rad / q component-wise, h_s = h, dir_s = dir;
+//      else rad_s = ( 0, 0, 0 ), h_s = 0 and dir_s = ( 0, 0, 1 ) -- never the loaded values, which may be NaN where the other lobe was traced
+//   4. steps 3 and 4 of nrdHipPackInputsSamples: demodulation, then P_s = the mode's packer with sanitize = true
+// Then
+//   both signals, every channel but the one carrying the hit distance:  ( ( ( P_0 + P_1 ) + P_2 ) + ... ) / float( N ) over ALL N samples -- the zeros of the samples that do
+//                                                                       not count are what makes rad / q an unbiased estimate
+//   specular hit distance:  NRD_FrontEnd_SpecHitDistAveraging_Begin / _Add( h_s ) / _End over all samples (zeros drop out by that rule; 0 if none), then the packer's
+//                           hit-distance output for that value, as nrdHipPackInputsSamples does
+//   diffuse hit distance:   the sum, in order, of the packer's hit-distance output over the n COUNTED samples only, divided by float( n ); 0 when n == 0. (A mean that took in
+//                           the zeros of the other samples would pull the distance toward 0 and still mark the texel valid for the hit-distance reconstruction.)
+// and the texel goes through the store codec of the plain call. With N = 1 every output byte equals nrdHipPackInputsEx fed two RGBA32_SFLOAT planes that hold ( rad / q, h )
+// -- direction planes: dir -- where the sample counts and ( 0, 0, 0, 0 ) -- direction planes: ( 0, 0, 1 ) -- elsewhere.
+#define NRD_HIP_LOBE_DIFFUSE 0u
+#define NRD_HIP_LOBE_SPECULAR 1u // any other byte: nothing was traced for this sample
+typedef struct NrdHipFrontEndLobes {
+    NrdHipPlaneDesc radianceHitDist; // in, RGBA32_SFLOAT, or RGB32_SFLOAT with hitDist below: what the ONE traced path returned (may be absent when both modes read .w only and hitDist is given)
+    NrdHipPlaneDesc hitDist;         // in, R32_SFLOAT: .w when radianceHitDist is RGB32_SFLOAT (rules of nrdHipPackInputsSplit)
+    NrdHipPlaneDesc direction;       // in, RGBA32_SFLOAT / RGB32_SFLOAT: needed when either signal's mode reads a direction
+    NrdHipPlaneDesc lobe;            // in, R8_UINT, required: NRD_HIP_LOBE_*
+    NrdHipPlaneDesc probability;     // in, R32_SFLOAT, optional: probability with which the SPECULAR lobe is chosen at this pixel; absent = radiance is already divided (q = 1)
+    uint32_t samplesNum;             // 0 is read as 1; at most 64
+    uint32_t reserved;               // must be 0
+    uint64_t radianceHitDistLayerBytes, hitDistLayerBytes, directionLayerBytes, lobeLayerBytes, probabilityLayerBytes;
+} NrdHipFrontEndLobes;
+uint32_t nrdHipPackInputsLobes(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSplit* split, const NrdHipFrontEndLobes* lobes,
+                               void* hipStream);
+
+// Does every pixel have a valid hit distance in the area the hit-distance reconstruction searches? A probabilistic split (above) leaves the hit distance of the lobe that was not
+// traced at 0, and REBLUR / RELAX_HitDistReconstruction look no further than 3x3 or 5x5 texels: a pixel whose area holds no valid sample keeps a hit distance of 0, silently, and
+// the history keeps it. nrdHipCheckInputs cannot see that -- it is a property of a neighbourhood. This call audits the PACKED planes as they will be bound; it needs no executor.
+//   in range:         viewZ is finite and !( abs( viewZ * viewZScale ) > denoisingRange ) -- the passes' own predicate, as in nrdHipCheckInputs
+//   valid neighbour:  inside the plane, in range, and its stored hit distance != 0 as the passes test it on the decoded value ( .w of an RGBA16_SFLOAT / RGBA16_SNORM texel, the
+//                     channel of an R16_UNORM one); a NaN counts as non-zero (whether values are finite is rules 2..5 of nrdHipCheckInputs)
+//   empty[ s ]:       in-range pixels whose own stored hit distance is 0
+//   holes[ s ]:       of those, the pixels with no valid neighbour in the ( 2 area + 1 )^2 texels around them: CERTAINLY unreconstructable. A necessary condition only: the passes
+//                     also weight by geometry and normal, so a pixel that is not a hole can still end up with nothing.
+// The report goes to 4-byte aligned CALLER device memory, zeroed and filled in stream order: no allocation, no synchronisation, capturable into a graph. Counts are integers and
+// firstHole is a minimum: the report does not depend on the order of the waves. Everything is validated before the first HIP call and nothing is enqueued on an error
+// (nrdHipGetLastFrontEndError): a missing viewZ or report, no signal at all, an area of 0 or above 2, a non-zero reserved, planes of different sizes -> INVALID_ARGUMENT; any
+// other format -> UNSUPPORTED.
+typedef struct NrdHipCoverageSignal {
+    NrdHipPlaneDesc plane; // IN_*_RADIANCE_HITDIST / IN_*_SH0 RGBA16_SFLOAT (.w), IN_*_HITDIST R16_UNORM, IN_DIFF_DIRECTION_HITDIST RGBA16_SNORM (.w); data NULL = absent
+} NrdHipCoverageSignal;
+typedef struct NrdHipCoverageDesc {
+    NrdHipPlaneDesc viewZ; // IN_VIEWZ R32_SFLOAT, required
+    NrdHipCoverageSignal diffuse, specular;
+    float viewZScale;      // 0 is read as 1
+    float denoisingRange;
+    uint32_t area;         // nrd::HitDistanceReconstructionMode: 1 = 3x3, 2 = 5x5
+    uint32_t reserved;     // must be 0
+} NrdHipCoverageDesc;
+typedef struct NrdHipCoverageReport { // per signal s: 0 diffuse, 1 specular
+    uint32_t inRangePixels;
+    uint32_t empty[2];     // in-range pixels whose own stored hit distance is 0
+    uint32_t holes[2];     // of those, pixels with no valid neighbour in the area
+    uint32_t firstHole[2]; // smallest y * width + x; 0xFFFFFFFF when holes is 0
+} NrdHipCoverageReport;
+uint32_t nrdHipCheckHitDistCoverage(const NrdHipCoverageDesc* desc, void* deviceReport, void* hipStream);
+
 // nrdHipResolveOutputsUpsampled. upsample == NULL is exactly nrdHipResolveOutputsSplit( desc, options, split, stream ). With upsample given:
 //   low size:   diffuse.in0 / in1, specular.in0 / in1, shadow and upsample->lowViewZ -- the denoiser's OUT_* planes and its IN_VIEWZ
 //   full size:  normalRoughness (the IN_NORMAL_ROUGHNESS format, packed at full size by a plain pack call), viewZ, albedo, rf0, every output of the descriptor, the split
@@ -639,6 +716,8 @@ static_assert(sizeof(NrdHipShadowLight) == 16 && sizeof(NrdHipShadowLightsPackDe
 static_assert(sizeof(NrdHipFrontEndSplit) == 88 && sizeof(NrdHipBackEndSplit) == 48, "mirrored by raytracingdenoiser_amd/api.py");
 static_assert(sizeof(NrdHipInputReport) == 72, "mirrored by raytracingdenoiser_amd/api.py");
 static_assert(sizeof(NrdHipBackEndUpsample) == 56, "mirrored by raytracingdenoiser_amd/api.py"); // 2 planes of 24 bytes + 8
+static_assert(sizeof(NrdHipFrontEndLobes) == 168, "mirrored by raytracingdenoiser_amd/api.py"); // 5 planes of 24 bytes + 8 + 5 strides
+static_assert(sizeof(NrdHipCoverageDesc) == 88 && sizeof(NrdHipCoverageReport) == 28, "mirrored by raytracingdenoiser_amd/api.py");
 #endif
 
 #ifdef __cplusplus

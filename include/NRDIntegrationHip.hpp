@@ -189,6 +189,14 @@ public:
     inline bool ResolveOutputsUpsampled(const NrdHipBackEndDesc& desc, const NrdHipBackEndUpsample& upsample, const NrdHipBackEndOptions* options = nullptr, const NrdHipBackEndSplit* split = nullptr) {
         return nrdHipResolveOutputsUpsampled(&desc, options, split, &upsample, m_Stream) == (uint32_t)Result::SUCCESS;
     }
+    // One traced lobe per pixel, the probabilistic diffuse / specular split of the README's "NOISY INPUTS" (nrdHipPackInputsLobes): both signals from ONE traced plane set, a lobe
+    // byte and a probability. options / split may be NULL. Set "hitDistanceReconstructionMode" and the pre-pass radii of the denoiser: the signal that was not traced has hit distance 0
+    inline bool PackInputsLobes(const NrdHipFrontEndDesc& desc, const NrdHipFrontEndLobes& lobes, const NrdHipFrontEndOptions* options = nullptr, const NrdHipFrontEndSplit* split = nullptr) {
+        return nrdHipPackInputsLobes(&desc, options, split, &lobes, m_Stream) == (uint32_t)Result::SUCCESS;
+    }
+    // ... and the audit of the dithering that chose the lobes (nrdHipCheckHitDistCoverage): sizeof( NrdHipCoverageReport ) bytes of the caller's device memory are filled in stream
+    // order; holes[ s ] != 0 = pixels of signal s with no valid hit distance in the area the reconstruction searches
+    inline bool CheckHitDistCoverage(const NrdHipCoverageDesc& desc, void* deviceReport) { return nrdHipCheckHitDistCoverage(&desc, deviceReport, m_Stream) == (uint32_t)Result::SUCCESS; }
     inline const char* GetLastFrontEndError() const { return nrdHipGetLastFrontEndError(); }
 
     // Assumes that no work of this integration is in flight on the stream

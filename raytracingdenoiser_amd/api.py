@@ -87,6 +87,12 @@ class CheckerboardMode(enum.IntEnum):
     WHITE = 2
 
 
+class HitDistanceReconstructionMode(enum.IntEnum):  # nrd::HitDistanceReconstructionMode: ReblurSettings / RelaxSettings::hitDistanceReconstructionMode, NrdHipCoverageDesc::area
+    OFF = 0
+    AREA_3X3 = 1
+    AREA_5X5 = 2
+
+
 # ----------------------------------------------------------------------------------------------- descs
 class AllocationCallbacks(C.Structure):
     _fields_ = [("Allocate", C.c_void_p), ("Reallocate", C.c_void_p), ("Free", C.c_void_p), ("userArg", C.c_void_p)]
@@ -329,6 +335,33 @@ class HipBackEndUpsample(C.Structure):  # include/NRDHip.h NrdHipBackEndUpsample
 NO_SOURCE = 255  # NrdHipBackEndUpsample::outSource of a pixel that took no low texel
 
 
+class Lobe(enum.IntEnum):  # include/NRDHip.h NRD_HIP_LOBE_*: the bytes of NrdHipFrontEndLobes::lobe; any other byte = nothing was traced for the sample
+    DIFFUSE = 0
+    SPECULAR = 1
+
+
+class HipFrontEndLobes(C.Structure):  # include/NRDHip.h NrdHipFrontEndLobes
+    _fields_ = [("radianceHitDist", HipPlaneDesc), ("hitDist", HipPlaneDesc), ("direction", HipPlaneDesc), ("lobe", HipPlaneDesc), ("probability", HipPlaneDesc),
+                ("samplesNum", C.c_uint32), ("reserved", C.c_uint32), ("radianceHitDistLayerBytes", C.c_uint64), ("hitDistLayerBytes", C.c_uint64), ("directionLayerBytes", C.c_uint64),
+                ("lobeLayerBytes", C.c_uint64), ("probabilityLayerBytes", C.c_uint64)]
+
+
+class HipCoverageSignal(C.Structure):  # include/NRDHip.h NrdHipCoverageSignal
+    _fields_ = [("plane", HipPlaneDesc)]
+
+
+class HipCoverageDesc(C.Structure):  # include/NRDHip.h NrdHipCoverageDesc
+    _fields_ = [("viewZ", HipPlaneDesc), ("diffuse", HipCoverageSignal), ("specular", HipCoverageSignal), ("viewZScale", C.c_float), ("denoisingRange", C.c_float),
+                ("area", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HipCoverageReport(C.Structure):  # include/NRDHip.h NrdHipCoverageReport
+    _fields_ = [("inRangePixels", C.c_uint32), ("empty", C.c_uint32 * 2), ("holes", C.c_uint32 * 2), ("firstHole", C.c_uint32 * 2)]
+
+
+assert C.sizeof(HipFrontEndLobes) == 168 and C.sizeof(HipCoverageDesc) == 88 and C.sizeof(HipCoverageReport) == 28
+
+
 class LightType(enum.IntEnum):  # include/NRDHip.h NRD_HIP_LIGHT_*
     DIRECTIONAL = 0
     LOCAL = 1
@@ -410,7 +443,7 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit",
                    "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString", "nrdHipPackShadowLights", "nrdHipResolveShadowLights",
                    "nrdHipPackGuides", "nrdHipCreateExecutorLayered", "nrdHipBindResourceLayers", "nrdHipGetPoolPlaneLayer", "nrdHipGetLayersNum",
-                   "nrdHipPackInputsDecimated", "nrdHipResolveOutputsUpsampled"]
+                   "nrdHipPackInputsDecimated", "nrdHipResolveOutputsUpsampled", "nrdHipPackInputsLobes", "nrdHipCheckHitDistCoverage"]
 
 _libs = {}
 
@@ -493,6 +526,9 @@ def load_library(path=None):
     lib.nrdHipPackInputsDecimated.restype = C.c_uint32
     lib.nrdHipResolveOutputsUpsampled.argtypes = [P(HipBackEndDesc), P(HipBackEndOptions), P(HipBackEndSplit), P(HipBackEndUpsample), C.c_void_p]
     lib.nrdHipResolveOutputsUpsampled.restype = C.c_uint32
+    lib.nrdHipPackInputsLobes.argtypes = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSplit), P(HipFrontEndLobes), C.c_void_p]
+    lib.nrdHipPackInputsLobes.restype = C.c_uint32
+    lib.nrdHipCheckHitDistCoverage.argtypes, lib.nrdHipCheckHitDistCoverage.restype = [P(HipCoverageDesc), C.c_void_p, C.c_void_p], C.c_uint32
     lib.nrdHipPackShadowLights.argtypes, lib.nrdHipPackShadowLights.restype = [P(HipShadowLightsPackDesc), C.c_void_p], C.c_uint32
     lib.nrdHipResolveShadowLights.argtypes, lib.nrdHipResolveShadowLights.restype = [P(HipShadowLightsResolveDesc), C.c_void_p], C.c_uint32
     lib.nrdHipPackGuides.argtypes, lib.nrdHipPackGuides.restype = [P(HipGuidesDesc), C.c_void_p], C.c_uint32

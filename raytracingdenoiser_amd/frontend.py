@@ -201,7 +201,7 @@ def _reuse(out, key, like, shape, dtype):
 
 
 # ---- front end -------------------------------------------------------------------------------------------------------------------------------------------
-def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0, **kw):
+def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0, lobes=None, **kw):
     """see describe_pack; launches on `stream` (a torch.cuda.Stream or a raw handle; default: the current stream) and returns the packed planes. Three-channel arrays, (xyz, w)
     pairs and [N, H, W, 3] stacks are read where they lie through nrdHipPackInputsSplit -- no copy, no allocation (in_place=False: widened into [.., 4] copies first, as before;
     that path allocates, so a raw stream handle suits it with four-channel inputs only); four-channel arguments take the calls they always took.
@@ -211,7 +211,9 @@ def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.Checkerboa
     every other call is the call it was.
     guide_shift=1 (quarter-resolution tracing, NRDHip.h nrdHipPackInputsDecimated): normal_roughness, viewz, material_id, motion, albedo and rf0 are the FULL-size [H, W] G-buffer,
     read at every second texel of every second row; the signals, distance_to_occluder and translucency are traced at the low size [(H + 1) >> 1, (W + 1) >> 1], which is the size
-    of every packed plane returned; common_settings (demodulation) is that of the low-size frame."""
+    of every packed plane returned; common_settings (demodulation) is that of the low-size frame.
+    lobes= (one traced lobe per pixel: the probabilistic diffuse / specular split, NRDHip.h nrdHipPackInputsLobes): a dict of pack_lobes' arguments, or what pack_lobes returned.
+    diffuse and specular are then dict(mode=SignalMode) alone -- both are built from the one traced plane set in the same launch."""
     given = inspect.signature(describe_pack).bind(normal_roughness, viewz, *args, **kw).arguments
     in_place = given.get("in_place")
     in_place = PACK_IN_PLACE if in_place is None else bool(in_place)
@@ -221,7 +223,13 @@ def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.Checkerboa
         lib = kw.get("lib") or api.load_library()
         layered = any(_layers(sig[k])[0] for sig in (given.get("diffuse"), given.get("specular")) if sig for k in ("radiance_hitdist", "direction") if sig.get(k) is not None)
         split = pack_split(normal_roughness, given.get("diffuse"), given.get("specular")) if in_place else None
-        if int(given.get("guide_shift", 0)) != 0:  # quarter-resolution tracing (NRDHip.h nrdHipPackInputsDecimated): one entry point for plain, sampled and split planes
+        if lobes is not None:
+            assert int(given.get("guide_shift", 0)) == 0 and given.get("hit_dist_trim", 0.0) == 0.0, "lobes: neither decimation nor a trim threshold"
+            lo, keep_lobes = pack_lobes(**lobes) if isinstance(lobes, dict) else lobes
+            options = pack_options(checkerboard_mode, frame_index)
+            split = split if split is not None else api.HipFrontEndSplit()
+            _check(lib, lib.nrdHipPackInputsLobes(C.byref(d), C.byref(options), C.byref(split), C.byref(lo), _stream(viewz, kw.get("stream"))), "nrdHipPackInputsLobes")
+        elif int(given.get("guide_shift", 0)) != 0:  # quarter-resolution tracing (NRDHip.h nrdHipPackInputsDecimated): one entry point for plain, sampled and split planes
             in_place_here = split is not None and _anything_split(d, split)
             samples = pack_samples(given.get("diffuse"), given.get("specular"), given.get("hit_dist_trim", 0.0), in_place=in_place_here)
             options = pack_options(checkerboard_mode, frame_index)
@@ -269,6 +277,38 @@ def pack_samples(diffuse=None, specular=None, hit_dist_trim=0.0, in_place=False)
     return samples
 
 
+def pack_lobes(radiance_hit_dist, lobe, probability=None, direction=None):
+    """(api.HipFrontEndLobes, arrays it points into) for nrdHipPackInputsLobes, next to a descriptor of describe_pack whose diffuse / specular dicts hold a mode alone. Everything
+    is read where it lies, [H, W, ..] for one sample per pixel or [N, H, W, ..] stacks the way pack_samples takes them (the layer stride is stride(0)):
+    radiance_hit_dist float32 [.., 4], or a (radiance [.., 3], hit_dist [..]) pair, or (None, hit_dist) when both modes read the hit distance alone -- what the ONE traced
+    path returned; lobe uint8 [..]: api.Lobe.DIFFUSE / SPECULAR, any other byte = nothing traced; probability float32 [..] or None: the probability with which the SPECULAR lobe
+    is chosen (None: the radiance is already divided by it); direction float32 [.., 3] or [.., 4]: needed when a signal's mode reads one."""
+    lo, keep = api.HipFrontEndLobes(), [radiance_hit_dist, lobe, probability, direction]
+    assert _dtype_name(lobe) == "uint8" and lobe.ndim in (2, 3), "lobe: uint8 [H, W] or [N, H, W]"
+    n = lobe.shape[0] if lobe.ndim == 3 else 1
+
+    def stack(t, plane_ndim, what):
+        assert t.ndim in (plane_ndim, plane_ndim + 1) and (t.shape[0] if t.ndim > plane_ndim else 1) == n, "%s: %d sample layer(s) expected, got shape %s" % (what, n, tuple(t.shape))
+        return (t[0], _stride0_bytes(t)) if t.ndim > plane_ndim else (t, 0)
+
+    layer, lo.lobeLayerBytes = stack(lobe, 2, "lobe")
+    lo.lobe, lo.samplesNum = _plane(layer, F.R8_UINT), n
+    xyz, w = radiance_hit_dist if _is_pair(radiance_hit_dist) else (radiance_hit_dist, None)
+    if xyz is not None:
+        layer, lo.radianceHitDistLayerBytes = stack(xyz, 3, "radiance_hit_dist")
+        lo.radianceHitDist = _fp32_plane(layer, 4 if w is None else 3, "radiance_hit_dist")
+    if w is not None:
+        layer, lo.hitDistLayerBytes = stack(w, 2, "hit_dist")
+        lo.hitDist = _fp32_plane(layer, 1, "hit_dist")
+    if probability is not None:
+        layer, lo.probabilityLayerBytes = stack(probability, 2, "probability")
+        lo.probability = _fp32_plane(layer, 1, "probability")
+    if direction is not None:
+        layer, lo.directionLayerBytes = stack(direction, 3, "direction")
+        lo.direction = _xyz_plane(layer, "direction")
+    return lo, keep
+
+
 # Whether pack_inputs takes three-channel input where it lies by default (in_place=None). Decided by tools/frontend_bench.py --split (DESIGN.md section 3.4, the `split` object of
 # profiles/frontend_bench.json): at 2560 x 1440 the in-place call takes 0.068 ms against 0.119 ms of widening + 0.066 ms of the four-channel call.
 PACK_IN_PLACE = True
@@ -282,7 +322,7 @@ def pack_split(normal_roughness, diffuse=None, specular=None):
     if _stays(normal_roughness, True, True):
         split.roughness = _fp32_plane(normal_roughness[1], 1, "roughness")
     for which, sig in (("diffuse", diffuse), ("specular", specular)):
-        if sig is None or not _stays(sig["radiance_hitdist"], True, True):
+        if sig is None or sig.get("radiance_hitdist") is None or not _stays(sig["radiance_hitdist"], True, True):  # (None: the traced planes are those of pack_lobes)
             continue
         hit = sig["radiance_hitdist"][1]
         if hit.ndim == 3:
@@ -360,7 +400,8 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
             continue
         mode = SignalMode(sig["mode"])
         dst.mode = int(mode)
-        if not (_stays(sig["radiance_hitdist"], in_place, True) and sig["radiance_hitdist"][0] is None):
+        rh = sig.get("radiance_hitdist")  # (None: a descriptor for nrdHipPackInputsLobes, whose traced planes are those of pack_lobes)
+        if rh is not None and not (_stays(rh, in_place, True) and rh[0] is None):
             t, dst.radianceHitDist = _signal_arg(sig["radiance_hitdist"], which + " radiance_hitdist", in_place, needs_w=True)
             keep.append(t)
         if sig.get("direction") is not None:
@@ -372,6 +413,53 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
         if slot1 is not None:
             dst.out1 = output(slot1, (h, w, 4), "float16", F.RGBA16_SFLOAT)
     return res, d, keep + [common_settings]
+
+
+# ---- hit-distance coverage of a probabilistic split ----------------------------------------------------------------------------------------------------------
+class HitDistCoverage:
+    """what nrdHipCheckHitDistCoverage reported: in_range_pixels; per signal ("diffuse", "specular") empty -- in-range pixels whose own hit distance is 0 -- holes -- of those,
+    the pixels with no valid sample in the searched area: certainly unreconstructable -- and first_hole, (x, y) of the raster-first one or None"""
+
+    def __init__(self, words, width):
+        words = [int(v) & 0xFFFFFFFF for v in words]
+        self.in_range_pixels = words[0]
+        self.empty = dict(diffuse=words[1], specular=words[2])
+        self.holes = dict(diffuse=words[3], specular=words[4])
+        self.first_hole = {k: None if v == 0xFFFFFFFF else (v % width, v // width) for k, v in (("diffuse", words[5]), ("specular", words[6]))}
+
+    def __repr__(self):
+        return "HitDistCoverage(in_range_pixels=%d, empty=%r, holes=%r, first_hole=%r)" % (self.in_range_pixels, self.empty, self.holes, self.first_hole)
+
+
+def describe_coverage(viewz, diffuse=None, specular=None, area=api.HitDistanceReconstructionMode.AREA_3X3, viewz_scale=1.0, denoising_range=500000.0):
+    """api.HipCoverageDesc of one nrdHipCheckHitDistCoverage launch, without launching. viewz: the packed IN_VIEWZ array; diffuse / specular: the packed plane that carries the
+    signal's hit distance, as bound -- IN_*_RADIANCE_HITDIST / IN_*_SH0 (float16 [H, W, 4]), IN_*_HITDIST (int16 [H, W]) or IN_DIFF_DIRECTION_HITDIST (int16 [H, W, 4]);
+    area: HitDistanceReconstructionMode of the denoiser (1 = 3x3, 2 = 5x5); viewz_scale and denoising_range: those of its CommonSettings."""
+    d = api.HipCoverageDesc()
+    d.viewZ = _fp32_plane(viewz, 1, "viewz")
+    if diffuse is not None:
+        d.diffuse.plane = _packed_plane(diffuse, "diffuse")
+    if specular is not None:
+        d.specular.plane = _packed_plane(specular, "specular")
+    d.viewZScale, d.denoisingRange, d.area = float(viewz_scale), float(denoising_range), int(area)
+    return d
+
+
+def check_hit_dist_coverage(viewz, diffuse=None, specular=None, area=api.HitDistanceReconstructionMode.AREA_3X3, viewz_scale=1.0, denoising_range=500000.0, stream=None, lib=None):
+    """see describe_coverage; launches on `stream` (as pack_inputs), waits for it and returns a HitDistCoverage. The dithering that decides which lobe a pixel traces is the
+    application's: this is how it learns that a pattern leaves pixels with no valid hit distance within the area the reconstruction searches."""
+    d = describe_coverage(viewz, diffuse, specular, area, viewz_scale, denoising_range)
+    lib = lib or api.load_library()
+    with _stream_scope(viewz, stream):
+        report = _empty(viewz, (7,), "int32")
+        ptr = report.ctypes.data if _is_numpy(report) else report.data_ptr()
+        _check(lib, lib.nrdHipCheckHitDistCoverage(C.byref(d), C.c_void_p(ptr), _stream(viewz, stream)), "nrdHipCheckHitDistCoverage")
+        if not _is_numpy(report):
+            import torch
+
+            torch.cuda.synchronize(viewz.device)  # (a raw stream handle cannot be waited for through torch: the device is)
+            report = report.cpu().numpy()
+    return HitDistCoverage(report, viewz.shape[1])
 
 
 # ---- back end --------------------------------------------------------------------------------------------------------------------------------------------

@@ -21,8 +21,12 @@ shape, its yardstick; the whole set three times with the rows alternating, each 
 --upsample is a run of its own that adds the `upsample` and `isa_upsample` objects to the output file: quarter-resolution denoising, REBLUR_DIFFUSE_SPECULAR radiance with
 remodulation. nrdHipResolveOutputsUpsampled from 1280 x 720 planes to 2560 x 1440 against the plain resolve of the same configuration at 2560 x 1440 and the copy rate, five
 alternating rounds, medians; and whole frames (pack + denoise + resolve, default settings) at full size and at quarter resolution.
+--lobes is a run of its own that adds the `lobes` and `isa_lobes` objects to the output file: the probabilistic diffuse / specular split at 2560 x 1440, REBLUR_RADIANCE on both
+signals, one traced plane, a lobe byte and a probability per pixel. Five alternating rounds of (a) nrdHipPackInputsLobes, (b) nrdHipPackInputs producing the same outputs from two
+prepared RGBA32_SFLOAT planes, (c) the torch chain that prepares those planes, (d) nrdHipCheckHitDistCoverage with area 2 on both packed signals; the copy rate of the same run,
+each row's spread over the rounds, and whether (a) is slower than (b) by more than that spread.
 usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]] [--split]
-       [--check-inputs] [--shadow-lights] [--guides]"""
+       [--check-inputs] [--shadow-lights] [--guides] [--upsample] [--lobes]"""
 import argparse
 import ctypes as C
 import json
@@ -912,6 +916,142 @@ def upsample_main(args):
     print(json.dumps({k: v for k, v in result["upsample"].items() if k != "rounds"}))
 
 
+COVERAGE_SRC = os.path.join(B.CSRC, "hip", "kernels_coverage.hip")
+LOBES_READ = {"normal_roughness RGBA32_SFLOAT": 16, "viewZ R32_SFLOAT": 4, "traced radiance_hitdist RGBA32_SFLOAT": 16, "lobe R8_UINT": 1, "probability R32_SFLOAT": 4}
+LOBES_WRITE = {"IN_NORMAL_ROUGHNESS": 4, "IN_VIEWZ R32_SFLOAT": 4, "IN_DIFF_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "IN_SPEC_RADIANCE_HITDIST RGBA16_SFLOAT": 8}
+PLAIN_READ = {"normal_roughness RGBA32_SFLOAT": 16, "viewZ R32_SFLOAT": 4, "diffuse radiance_hitdist RGBA32_SFLOAT": 16, "specular radiance_hitdist RGBA32_SFLOAT": 16}
+COVERAGE_READ = {"IN_VIEWZ R32_SFLOAT": 4, "IN_DIFF_RADIANCE_HITDIST .w": 2, "IN_SPEC_RADIANCE_HITDIST .w": 2}
+
+
+def lobes_isa():
+    """static facts about the kernels behind nrdHipPackInputsLobes and nrdHipCheckHitDistCoverage (the `isa_lobes` object of profiles/frontend_bench.json), as isa(): "pack_lobes",
+    "coverage_3x3" and "coverage_5x5"; atomics: the global atomics of a listing -- all of them sit behind the wave's exit"""
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for src in (SRC, COVERAGE_SRC):
+            listing = os.path.join(tmp, os.path.basename(src) + ".s")
+            flags = [f for f in B._flags(src) if f not in ("-x", "hip")]
+            subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", src, "-o", listing], check=True, capture_output=True, text=True)
+            for mangled, k in isa_stats.parse(listing).items():
+                m = re.search(r"HitDistCoverageKernelILi(\d)E", mangled)
+                name = "pack_lobes" if "PackLobesKernel" in mangled else "coverage_%dx%d" % ((2 * int(m.group(1)) + 1,) * 2) if m else None
+                if name:
+                    c = k["counter"]
+                    out[name] = dict(_facts(k), global_load_dwordx4=c.get("global_load_dwordx4", 0), global_load_dwordx3=c.get("global_load_dwordx3", 0),
+                                     atomics={i: v for i, v in c.items() if i.startswith("global_atomic")})
+    assert set(out) == {"pack_lobes", "coverage_3x3", "coverage_5x5"}, sorted(out)
+    return out
+
+
+def lobes_main(args):
+    """--lobes: see the module text"""
+    result = {"isa_lobes": lobes_isa()}
+    if args.isa_only:
+        print(json.dumps(result))
+        return
+    import torch
+
+    from raytracingdenoiser_amd import api, frontend
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    w, h = args.width, args.height
+    px = w * h
+    S = api.SignalMode
+    g = torch.Generator(device="cuda").manual_seed(7)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    normal = torch.nn.functional.normalize(rand(h, w, 3) - 0.5, dim=-1)
+    nr = torch.cat([normal, rand(h, w, 1) * 0.95 + 0.05], -1).contiguous()
+    viewz = rand(h, w) * 49.0 + 1.0
+    traced = torch.cat([rand(h, w, 3) * 4.0, rand(h, w, 1) * 29.9 + 0.1], -1).contiguous()
+    prob = rand(h, w) * 0.9 + 0.05
+    bayer = torch.tensor([[0, 8, 2, 10], [12, 4, 14, 6], [3, 11, 1, 9], [15, 7, 13, 5]], device="cuda", dtype=torch.float32)
+    threshold = (bayer.repeat((h + 3) // 4, (w + 3) // 4)[:h, :w] + 0.5) / 16.0
+    lobe = (threshold < prob).to(torch.uint8).contiguous()  # the application's dithering: a 4 x 4 Bayer threshold against the probability of the specular lobe
+    lib, stream = api.load_library(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sig = dict(mode=S.REBLUR_RADIANCE)
+    packed, lobes_desc, keep0 = frontend.describe_pack(nr, viewz, diffuse=sig, specular=sig)
+    lo, keep1 = frontend.pack_lobes(traced, lobe, prob)
+    options, split = frontend.pack_options(), api.HipFrontEndSplit()
+
+    def prepare():  # what a tensor host does today before the plain call: two full RGBA32_SFLOAT planes
+        q = torch.where(lobe == 1, prob, 1.0 - prob)
+        scaled = torch.cat([traced[..., :3] / q.unsqueeze(-1), traced[..., 3:]], -1)
+        return tuple(torch.where(((lobe == X) & (q > 0)).unsqueeze(-1), scaled, torch.zeros((), device="cuda")) for X in (0, 1))
+
+    planes = prepare()
+    plain_packed, plain_desc, keep2 = frontend.describe_pack(nr, viewz, diffuse=dict(sig, radiance_hitdist=planes[0]), specular=dict(sig, radiance_hitdist=planes[1]))
+    R = api.ResourceType
+    coverage_desc = frontend.describe_coverage(packed[R.IN_VIEWZ][0], packed[R.IN_DIFF_RADIANCE_HITDIST][0], packed[R.IN_SPEC_RADIANCE_HITDIST][0], area=2)
+    report = torch.zeros(7, dtype=torch.int32, device="cuda")
+    raw_report = C.c_void_p(report.data_ptr())
+
+    def pack_lobes():
+        assert lib.nrdHipPackInputsLobes(C.byref(lobes_desc), C.byref(options), C.byref(split), C.byref(lo), stream) == 0, lib.nrdHipGetLastFrontEndError()
+
+    def pack_plain():
+        assert lib.nrdHipPackInputs(C.byref(plain_desc), stream) == 0, lib.nrdHipGetLastFrontEndError()
+
+    def coverage():
+        assert lib.nrdHipCheckHitDistCoverage(C.byref(coverage_desc), raw_report, stream) == 0, lib.nrdHipGetLastFrontEndError()
+
+    pack_lobes()
+    pack_plain()
+    coverage()
+    torch.cuda.synchronize()
+    for rt in packed:  # the two paths produce the same planes: what is timed is the same work
+        assert torch.equal(packed[rt][0].view(torch.uint8), plain_packed[rt][0].view(torch.uint8)), rt
+    words = report.cpu().numpy().view("uint32")
+    assert int(words[0]) == px and int(words[1]) > px // 4 and int(words[2]) > px // 4, words
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(args.reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / args.reps
+
+    rows = {"pack_lobes_ms": pack_lobes, "pack_plain_ms": pack_plain, "torch_prepare_ms": prepare, "coverage_5x5_ms": coverage}
+    rounds = [{k: timed(fn) for k, fn in rows.items()} for _ in range(5)]
+    best = {k: min(r[k] for r in rounds) for k in rows}
+    median = {k: sorted(r[k] for r in rounds)[2] for k in rows}
+    spread = {k: (max(r[k] for r in rounds) - min(r[k] for r in rounds)) / min(r[k] for r in rounds) for k in rows}
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
+    rate = lambda bytes_per_px, ms: bytes_per_px * px / (ms * 1e-3) / 1e9
+    lobes_bytes, plain_bytes, coverage_bytes = sum(LOBES_READ.values()) + sum(LOBES_WRITE.values()), sum(PLAIN_READ.values()) + sum(LOBES_WRITE.values()), sum(COVERAGE_READ.values())
+    noise = max(spread["pack_lobes_ms"], spread["pack_plain_ms"])
+    result["lobes"] = dict(
+        best=best, median=median, run_to_run_spread=spread, rounds=rounds, device=torch.cuda.get_device_name(0), width=w, height=h, reps=args.reps, warmup=args.warmup,
+        times_are="device events around --reps back-to-back calls, per call; five rounds with the four rows alternating inside each round; spread = ( max - min ) / min of a row over the rounds",
+        scene="REBLUR_RADIANCE on both signals; lobe = a 4 x 4 Bayer threshold against a probability in [0.05, 0.95]; pack_plain_ms packs the two planes torch_prepare_ms builds, and both pack rows write the same bytes",
+        lobes_read_bytes_per_pixel=LOBES_READ, plain_read_bytes_per_pixel=PLAIN_READ, write_bytes_per_pixel=LOBES_WRITE, coverage_read_bytes_per_pixel=COVERAGE_READ,
+        pack_lobes_gigabytes_per_second=rate(lobes_bytes, best["pack_lobes_ms"]), pack_plain_gigabytes_per_second=rate(plain_bytes, best["pack_plain_ms"]),
+        coverage_gigabytes_per_second=rate(coverage_bytes, best["coverage_5x5_ms"]), copy_gigabytes_per_second=gbps.value,
+        pack_lobes_fraction_of_copy_rate=rate(lobes_bytes, best["pack_lobes_ms"]) / gbps.value, coverage_fraction_of_copy_rate=rate(coverage_bytes, best["coverage_5x5_ms"]) / gbps.value,
+        coverage_bytes_are="the 8 bytes per pixel the kernel consumes (viewZ and the 16 bits of .w of either signal); the memory system moves whole 8-byte texels' sectors, 20 per pixel",
+        fraction_is_not="a share of HBM bandwidth: the working set partly fits the memory-side cache, as for pack and resolve (DESIGN.md section 3.4)",
+        pack_lobes_over_pack_plain=median["pack_lobes_ms"] / median["pack_plain_ms"], pack_lobes_over_plain_path=median["pack_lobes_ms"] / (median["pack_plain_ms"] + median["torch_prepare_ms"]),
+        pack_lobes_slower_than_plain_beyond_the_spread=bool(median["pack_lobes_ms"] > median["pack_plain_ms"] * (1.0 + noise)), holes_5x5=[int(words[3]), int(words[4])])
+    record = {}
+    if os.path.exists(args.out):  # the other fields of the record are another run's: kept as they are
+        with open(args.out) as fp:
+            record = json.load(fp)
+    record.update(result)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fp:
+        json.dump(record, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps({k: v for k, v in result["lobes"].items() if k != "rounds"}))
+    print(json.dumps(result["isa_lobes"]))
+    assert not result["lobes"]["pack_lobes_slower_than_plain_beyond_the_spread"], "nrdHipPackInputsLobes is slower than the plain pack it replaces by more than the run-to-run spread"
+
+
 def synth_pack(raw, synth, torch):
     """the packing of synth.render_frame for REBLUR_DIFFUSE_SPECULAR on the raw values: its packers, elementwise torch operations with fp32 intermediates"""
     out = {"normal_roughness": synth.pack_normal_roughness(raw["normal"], raw["roughness"], raw["material"]).contiguous(), "viewz": raw["viewz"].clone(),
@@ -996,11 +1136,15 @@ def main():
                     "--height say otherwise) against the copy rate and the same recipes as torch elementwise operations; adds the `shadow_lights` and `isa_shadow_lights` objects to --out")
     ap.add_argument("--guides", action="store_true", help="a run of its own: nrdHipPackGuides on RGB32_SFLOAT position planes against the copy rate, next to the four shadow-light "
                     "calls on planes of the same size, the whole set three times; adds the `guides` and `isa_guides` objects to --out and leaves its other fields as they are")
+    ap.add_argument("--lobes", action="store_true", help="a run of its own: nrdHipPackInputsLobes against nrdHipPackInputs on two prepared planes and the torch chain that prepares them, "
+                    "and nrdHipCheckHitDistCoverage against the copy rate; adds the `lobes` and `isa_lobes` objects to --out")
     ap.add_argument("--upsample", action="store_true", help="a run of its own: nrdHipResolveOutputsUpsampled (half-size planes to --width x --height) against the plain resolve of the same "
                     "configuration and the copy rate, and whole frames at full and at quarter resolution; adds the `upsample` and `isa_upsample` objects to --out")
     args = ap.parse_args()
     default_size = (1920, 1080) if args.shadow_lights else (2560, 1440)
     args.width, args.height = args.width or default_size[0], args.height or default_size[1]
+    if args.lobes:
+        return lobes_main(args)
     if args.upsample:
         return upsample_main(args)
     if args.guides:
