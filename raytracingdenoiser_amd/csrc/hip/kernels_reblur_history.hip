@@ -52,20 +52,15 @@ constexpr uint64_t PackTaps(bool rows) {
 constexpr uint64_t TAP_I = PackTaps(false), TAP_J = PackTaps(true);
 } // namespace hf
 
-// The reconstruction requests the texels of NRD_HF_TAP_BATCH taps (a divisor of 20) before it forms the first weight of the group: no tap address depends on another tap.
+// The reconstruction requests the texels of TAP_BATCH taps (a divisor of 20) before it forms the first weight of the group: no tap address depends on another tap.
 // The taps are weighted and summed in the reference's order whatever the group size. Measured at 1440p (profiles/HISTORY.md "HistoryFix: tap batches"): the loop is bound
 // by the VALU issue of waves with a few young lanes (~110 instructions per tap and wave), not by its chain of loads -- two taps in flight are worth 1.7-2.3 us and fit the
 // 6 waves of the rolled loop (80 VGPRs, passes.h NRD_WAVES_REBLUR_HF); four or five need 91-99 VGPRs, and the wave they give up costs the pixels that reconstruct
 // nothing 1.3-6 us.
-// A/B builds (tools/build_variant.py): 0 = the rolled j / i loops, one tap in flight.
-#ifndef NRD_HF_TAP_BATCH
-#define NRD_HF_TAP_BATCH 2
-#endif
-static_assert(NRD_HF_TAP_BATCH >= 0 && (NRD_HF_TAP_BATCH == 0 || hf::TAPS % NRD_HF_TAP_BATCH == 0), "NRD_HF_TAP_BATCH: 0 or a divisor of 20");
-// Timing-only A/B builds, never the product: 0 compiles the tap loop out (what the reconstruction costs = the difference of the HistoryFix rows of two kernel traces)
-#ifndef NRD_HF_RECONSTRUCT
-#define NRD_HF_RECONSTRUCT 1
-#endif
+namespace hf {
+constexpr int TAP_BATCH = 2;
+static_assert(TAP_BATCH > 0 && TAPS % TAP_BATCH == 0, "hf::TAP_BATCH: a divisor of 20");
+} // namespace hf
 
 struct HfPlanes {
     Plane tiles, normalRoughness, data1, viewZ, inDiff, inSpec, inDiffFast, inSpecFast, outDiff, outSpec, outDiffFast, outSpecFast;
@@ -199,28 +194,16 @@ NRD_D typename ReblurSignal<KIND>::type HistoryFixSignal(const ReblurCB& c, cons
                 }
             };
 
-#if !NRD_HF_RECONSTRUCT
-            (void)requestTap, (void)addTap;
-#elif NRD_HF_TAP_BATCH == 0
-            for (int j = -2; j <= 2; j++) {
-                for (int i = -2; i <= 2; i++) {
-                    if ((i == 0 && j == 0) || (abs(i) + abs(j) == 4))
-                        continue;
-                    addTap(requestTap(i, j), i, j);
-                }
-            }
-#else
 #pragma unroll 1
-            for (int first = 0; first < hf::TAPS; first += NRD_HF_TAP_BATCH) {
-                Tap taps[NRD_HF_TAP_BATCH];
+            for (int first = 0; first < hf::TAPS; first += hf::TAP_BATCH) {
+                Tap taps[hf::TAP_BATCH];
 #pragma unroll
-                for (int n = 0; n < NRD_HF_TAP_BATCH; n++)
+                for (int n = 0; n < hf::TAP_BATCH; n++)
                     taps[n] = requestTap(int((hf::TAP_I >> (3 * (first + n))) & 7u) - 2, int((hf::TAP_J >> (3 * (first + n))) & 7u) - 2);
 #pragma unroll
-                for (int n = 0; n < NRD_HF_TAP_BATCH; n++)
+                for (int n = 0; n < hf::TAP_BATCH; n++)
                     addTap(taps[n], int((hf::TAP_I >> (3 * (first + n))) & 7u) - 2, int((hf::TAP_J >> (3 * (first + n))) & 7u) - 2);
             }
-#endif
         };
         if (compareMaterials)
             reconstruct(std::true_type());
@@ -289,9 +272,6 @@ NRD_D typename ReblurSignal<KIND>::type HistoryFixSignal(const ReblurCB& c, cons
     return ChangeLuma(sig, luma);
 }
 
-#ifndef NRD_REBLUR_HF_ROTATE
-#define NRD_REBLUR_HF_ROTATE 1 // (0.0857 -> 0.0658 ms at 1440p, r04_q: the young pixels this pass reconstructs are the columns entering the screen -- on ONE XCD in the striped order)
-#endif
 template <bool DIFF, bool SPEC, bool PERF, int KIND, bool SH>
 // (performance mode keeps a bound of one wave less: at NRD_WAVES_REBLUR_HF = 6 its diffuse + specular kernel needs 8 B of scratch)
 __global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF - (PERF ? 1 : 0)) void ReblurHistoryFixKernel(ReblurCB c, HfPlanes P, RowRange rr) {
@@ -302,7 +282,8 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF - (PER
 
     const int tx = threadIdx.x % TILE_X, ty = threadIdx.x / TILE_X;
     const int blockY = BlockTileY(rr);
-    const int tileX = NRD_REBLUR_HF_ROTATE ? BlockTileXRotated(rr, blockY) : BlockTileX(rr); // (A/B switch: passes.h BlockTileXRotated)
+    // rotated tile order (passes.h BlockTileXRotated; 0.0857 -> 0.0658 ms at 1440p, r04_q): the young pixels this pass reconstructs are the columns entering the screen -- on ONE XCD in the striped order
+    const int tileX = BlockTileXRotated(rr, blockY);
     const int px = tileX * TILE_X + tx, py = blockY * TILE_Y + ty;
     const int rw = c.gRectSizeMinusOne.x, rh = c.gRectSizeMinusOne.y;
 
@@ -458,7 +439,7 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_TS) void ReblurTem
     __shared__ float s_SpecLuma[SPEC ? ts::BUF_Y * ts::BUF_STRIDE : 1];
 
     const int tx = threadIdx.x % TILE_X, ty = threadIdx.x / TILE_X;
-    const int blockY = BlockTileY(rr, NRD_ALT_TILE_ORDER != 0); // (A/B: kernels_reblur_spatial.hip)
+    const int blockY = BlockTileY(rr);
     const int px = BlockTileX(rr) * TILE_X + tx, py = blockY * TILE_Y + ty;
     const int rw = c.gRectSizeMinusOne.x, rh = c.gRectSizeMinusOne.y;
 

@@ -538,10 +538,9 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_SPATIAL) void Rebl
     typedef typename Sig::type S;
     const int tileX = BlockTileX(rr);
     const int px = tileX * TILE_X + (threadIdx.x % TILE_X);
-    // NRD_ALT_TILE_ORDER (A/B, round 6): the passes of the chain alternate their walk through the tile rows as the reference's NRD_CTA_ORDER_DEFAULT / _REVERSED do
-    // (Common.hlsli:92-106: "helps to reuse data already stored in caches") -- PrePass top-down, TemporalAccumulation bottom-up, HistoryFix top-down, Blur bottom-up, PostBlur
-    // top-down, TemporalStabilization bottom-up: every pass starts on the rows its predecessor wrote last
-    const int blockY = BlockTileY(rr, NRD_ALT_TILE_ORDER && MODE == BLUR);
+    // top-down in every spatial pass (passes.h BlockTileY: bottom-up loses 1-2 % here; alternating the direction from pass to pass as the reference's
+    // NRD_CTA_ORDER_DEFAULT / _REVERSED do, Common.hlsli:92-106, did not pay either: profiles/HISTORY.md)
+    const int blockY = BlockTileY(rr);
     const int py = blockY * TILE_Y + (threadIdx.x / TILE_X);
     // a workgroup over sky tiles only leaves on a scalar test, before any vector-memory instruction (planes.h LoadTileBytesUniform)
     const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, tileX, blockY);

@@ -27,15 +27,8 @@ constexpr int BUF_Y = TILE_Y + 2 * BORDER; // 10
 constexpr int BUF_STRIDE = BUF_X + 1;      // 35 float4 slots per row
 
 // The surface-motion window (MODE 1, below): the texels of the previous frame a workgroup's pixels reproject to, staged in LDS
-#ifndef NRD_TA_WIN_H
-#define NRD_TA_WIN_W 64 // at most 64: one lane per column when the window is filled
-#define NRD_TA_WIN_H 16
-#endif
-#ifndef NRD_TA_SKY_FLAG_STORE
-#define NRD_TA_SKY_FLAG_STORE 1 // (A/B switch, tools/build_variant.py; 0 is not a product build: the fallback statistics would count stale flags)
-#endif
-constexpr int WIN_W = NRD_TA_WIN_W;
-constexpr int WIN_H = NRD_TA_WIN_H;
+constexpr int WIN_W = 64; // at most 64: one lane per column when the window is filled
+constexpr int WIN_H = 16;
 
 struct TaPlanes {
     uint32_t* historyReach; // passes.h PassArgs::historyReachWord (multi-GPU hosts; nullptr otherwise)
@@ -69,7 +62,7 @@ NRD_D void WindowFastTexels(const HistoryFilter&, const uint32_t*, int, int, con
 // OCC = occlusion family (REBLUR_OCCLUSION): hit-distance-only signals in R16_UNORM, no pre-pass output to read, no DATA2, no firefly suppressor
 // SH = the *_SH denoisers: the SH1 plane of every signal is accumulated with the same speeds (custom-weight bilinear history fetch)
 // WAVES = waves per SIMD the register allocation aims at (__launch_bounds__): 2 for the kernels with a specular signal (3 would need scratch), 3 for
-// the diffuse-only ones (NRD_HIP_TA_WAVES overrides the choice at launch for A/B runs; measurements in DESIGN.md section 3)
+// the diffuse-only ones, 3 for the window kernel (fixed by the launcher; measurements in DESIGN.md section 3)
 //
 // MODE 1 = "window" kernel. Everything the pass reads at the surface-motion position -- the 4x4 previous-depth / internal-data footprint, the 2x2 previous
 // normals, the 12 + 12 history texels of the two signals and their fast histories: 320 bytes per pixel through the L1, ~90 VGPRs of requests in flight, and
@@ -130,9 +123,9 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
     const bool preSky = TileByteIsSky(tileBytes, tx >> 4); // an active thread's pixel lies in one of the two tiles under this workgroup
     {
         if (!TileBytesHaveGeometry<2>(tileBytes)) {
-            // (the flag byte of a sky tile: one store of lane 0 that nothing waits for. NRD_TA_SKY_FLAG_STORE=0, an A/B build that leaves the byte stale, measures what
-            // it costs the exit: nothing that a kernel trace resolves -- profiles/HISTORY.md)
-            if (NRD_TA_SKY_FLAG_STORE && MODE == 1 && threadIdx.x == 0 && tileFlag)
+            // (the flag byte of a sky tile: one store of lane 0 that nothing waits for, and without it the fallback statistics would count stale flags. A build that
+            // left the byte stale measured what it costs the exit: nothing that a kernel trace resolves -- profiles/HISTORY.md)
+            if (MODE == 1 && threadIdx.x == 0 && tileFlag)
                 *tileFlag = 0;
             return; // uniform across the block
         }
@@ -1142,14 +1135,13 @@ static const char* LaunchTemporalAccumulation(const PassArgs& a) {
     }
 
     RowGrid g = GridForRows(c.gRectSizeMinusOne.x + 1, c.gRectSizeMinusOne.y + 1, TILE_X, TILE_Y, a.rowBegin, a.rowEnd);
-    // register budget: with a specular signal the batched requests need ~250 VGPRs (2 waves per SIMD); the diffuse-only kernel fits 168 without scratch,
-    // which keeps its third wave (r02_k: 0.135 ms at 2 waves against 0.109 before the batching)
-    static const int wavesEnv = getenv("NRD_HIP_TA_WAVES") ? atoi(getenv("NRD_HIP_TA_WAVES")) : 0;
-    static const bool windowEnv = !(getenv("NRD_HIP_TA_WINDOW") && atoi(getenv("NRD_HIP_TA_WINDOW")) == 0); // A/B switch
+    // register budget of the plain kernel: with a specular signal the batched requests need ~250 VGPRs (2 waves per SIMD); the diffuse-only kernel fits 168 without
+    // scratch, which keeps its third wave (r02_k: 0.135 ms at 2 waves against 0.109 before the batching)
+    constexpr int PLAIN_WAVES = SPEC ? 2 : 3;
     // the window kernel pays where the pass is heaviest: radiance + hit distance with BOTH signals (0.267 + 0.002 ms against 0.298). Measured and left out: the
     // single-signal denoisers (REBLUR_DIFFUSE: 0.126 + launch of the fallback against 0.112 -- the plain kernel already runs 3 waves and is VALU-bound, r03_i)
     constexpr bool HAS_WINDOW = DIFF && SPEC && !PERF && KIND == SIGNAL_RADIANCE;
-    if (HAS_WINDOW && windowEnv && !wavesEnv) {
+    if constexpr (HAS_WINDOW) {
         if (!a.tileFlags.ptr || (uint32_t)a.tileFlags.w * TILE_X < (uint32_t)P.viewZ.w || (uint32_t)a.tileFlags.h * TILE_Y < (uint32_t)P.viewZ.h ||
             a.tileFlags.pitch % TILE_FLAG_GROUP != 0 || ((uintptr_t)a.tileFlags.ptr & 255u) != 0) // (planes.h AnyTileFlagUniform: whole groups of flags are read at once)
             return "REBLUR temporal accumulation: the executor's tile-flag scratch is missing or too small";
@@ -1165,17 +1157,13 @@ static const char* LaunchTemporalAccumulation(const PassArgs& a) {
         P.winMaxW = limW < WIN_W ? limW : WIN_W;
         P.winMaxH = limH < WIN_H ? limH : WIN_H;
         // window kernel (LDS-staged surface-motion footprints, 3 waves per SIMD), then the plain kernel on the tiles the first one declined
-        LaunchPass(a, (ReblurTemporalAccumulationKernel<DIFF, SPEC, PERF, KIND, SH, 3, HAS_WINDOW ? 1 : 0>), g.grid, dim3(TILE_X * TILE_Y), c, P, MakeRowRange(g));
+        LaunchPass(a, (ReblurTemporalAccumulationKernel<DIFF, SPEC, PERF, KIND, SH, 3, 1>), g.grid, dim3(TILE_X * TILE_Y), c, P, MakeRowRange(g));
         dim3 fallbackGrid = g.grid;
         fallbackGrid.x = (unsigned)((P.tileFlags.w + FALLBACK_TILES - 1) / FALLBACK_TILES);
-        LaunchPass(a, (ReblurTemporalAccumulationKernel<DIFF, SPEC, PERF, KIND, SH, SPEC ? 2 : 3, HAS_WINDOW ? 2 : 0>), fallbackGrid, dim3(TILE_X * TILE_Y), c, P, MakeRowRange(g));
-        return nullptr;
+        LaunchPass(a, (ReblurTemporalAccumulationKernel<DIFF, SPEC, PERF, KIND, SH, PLAIN_WAVES, 2>), fallbackGrid, dim3(TILE_X * TILE_Y), c, P, MakeRowRange(g));
+    } else {
+        LaunchPass(a, (ReblurTemporalAccumulationKernel<DIFF, SPEC, PERF, KIND, SH, PLAIN_WAVES, 0>), g.grid, dim3(TILE_X * TILE_Y), c, P, MakeRowRange(g));
     }
-    const int waves = wavesEnv ? wavesEnv : (SPEC ? 2 : 3);
-    if (waves >= 3)
-        LaunchPass(a, (ReblurTemporalAccumulationKernel<DIFF, SPEC, PERF, KIND, SH, 3, 0>), g.grid, dim3(TILE_X * TILE_Y), c, P, MakeRowRange(g));
-    else
-        LaunchPass(a, (ReblurTemporalAccumulationKernel<DIFF, SPEC, PERF, KIND, SH, 2, 0>), g.grid, dim3(TILE_X * TILE_Y), c, P, MakeRowRange(g));
     return nullptr;
 }
 

@@ -504,14 +504,11 @@ struct HistoryFixPlanes {
     SignalPlanes spec, diff;
 };
 
-#ifndef NRD_RELAX_HF_ROTATE
-#define NRD_RELAX_HF_ROTATE 1
-#endif
 template <bool DIFF, bool SPEC, bool SH>
 __global__ __launch_bounds__(256, NRD_WAVES_RELAX_HF) void RelaxHistoryFixKernel(HistoryFixPlanes P, RelaxCB c, RowRange rows) {
     const int blockY = BlockTileY(rows, false) /* (top-down: 0.0985 against 0.101 ms bottom-up, r04_v / r04_w) */;
     // (rotated tile order: the pixels with young history -- all this pass works on -- are the columns entering the screen and the silhouettes; passes.h BlockTileXRotated)
-    const int tileX = NRD_RELAX_HF_ROTATE ? BlockTileXRotated(rows, blockY) : BlockTileX(rows);
+    const int tileX = BlockTileXRotated(rows, blockY);
     // a workgroup over sky tiles only leaves on a scalar test, before any vector-memory instruction (planes.h LoadTileBytesUniform)
     const uint32_t tileBytes = LoadBlockTileBytes(P.tiles, tileX, blockY);
     if (!TileBytesHaveGeometry<2>(tileBytes))

@@ -240,17 +240,11 @@ inline dim3 GridFor(int w, int h, int tileW, int tileH) { return dim3((unsigned)
 //     tileX = (blockIdx.x % 8) * bandTiles + blockIdx.x / 8,      bandTiles = ceil(tilesX / 8)
 // XCD k owns the vertical band of tile columns [k * bandTiles, (k + 1) * bandTiles): neighbouring tiles share their halos in ONE L2, all eight
 // XCDs sweep the frame top to bottom together, and a horizontal sky band costs every XCD the same (the r01 experiment with bands of tile ROWS lost
-// 1.46x to that imbalance). Placement is a speed matter only: results do not depend on it. NRD_HIP_XCD_BANDS=0 restores the plain order.
-// NRD_HIP_XCD_BANDS: 0 = plain order; 1 = one band per XCD; n > 1 = stripes of n tile columns dealt round-robin to the XCDs (several stripes per XCD);
-// default (-1) = stripes whose width is picked per launch: the widest of 4, 3, 2 tile columns that gives every XCD the same number of stripes.
-// Measured (profiles/r02_b_*, r02_c_*): one band per XCD cuts the counter traffic of the sparse-tap passes from 2-4x to 1.1-1.3x the algorithmic
-// bytes but runs 3-5 % SLOWER than the plain order (the passes are not HBM-bound, and a band's cost depends on what it shows); stripes of 2-3 tile
-// columns are the fastest order (REBLUR 1440p 1.014 ms vs 1.020 plain vs 1.056 banded; RELAX 4K 3.32 vs 3.37 vs 3.55).
-inline int XcdBandsSetting() {
-    static const int v = getenv("NRD_HIP_XCD_BANDS") ? atoi(getenv("NRD_HIP_XCD_BANDS")) : -1;
-    return v;
-}
-inline bool XcdBandsEnabled() { return XcdBandsSetting() != 0; }
+// 1.46x to that imbalance). Placement is a speed matter only: results do not depend on it.
+// An XCD's tile columns are dealt out as stripes, round-robin over the XCDs, whose width is picked per launch: the widest of 4, 3, 2 tile columns that gives
+// every XCD the same number of stripes. Measured (profiles/r02_b_*, r02_c_*): one band per XCD cuts the counter traffic of the sparse-tap passes from 2-4x to
+// 1.1-1.3x the algorithmic bytes but runs 3-5 % SLOWER than the plain order (the passes are not HBM-bound, and a band's cost depends on what it shows); stripes
+// of 2-3 tile columns are the fastest order (REBLUR 1440p 1.014 ms vs 1.020 plain vs 1.056 banded; RELAX 4K 3.32 vs 3.37 vs 3.55).
 struct RowGrid {
     dim3 grid;
     int firstBlockY, rowBegin, rowEnd, bandTiles, stripeTiles;
@@ -265,18 +259,15 @@ inline RowGrid GridForRows(int w, int h, int tileW, int tileH, int rowBegin, int
     int lastBlockY = (g.rowEnd + tileH - 1) / tileH;
     int ny = lastBlockY - g.firstBlockY;
     const int tilesX = (w + tileW - 1) / tileW;
-    g.bandTiles = (XcdBandsEnabled() && tilesX >= 16) ? (tilesX + 7) / 8 : 0;
+    g.bandTiles = tilesX >= 16 ? (tilesX + 7) / 8 : 0; // (narrower frames: plain tile order)
     g.stripeTiles = g.bandTiles;
-    int stripe = XcdBandsSetting();
-    if (g.bandTiles && stripe < 0) { // automatic: equal stripe counts per XCD if possible
-        stripe = 2;
-        for (int b = 4; b >= 2; b--)
+    if (g.bandTiles) { // stripes: the XCD's tile columns are dealt out in groups of stripeTiles
+        int stripe = 2;
+        for (int b = 4; b >= 2; b--) // equal stripe counts per XCD if possible
             if (tilesX % (8 * b) == 0) {
                 stripe = b;
                 break;
             }
-    }
-    if (g.bandTiles && stripe > 1) { // stripes: the XCD's tile columns are dealt out in groups of stripeTiles
         g.stripeTiles = stripe < g.bandTiles ? stripe : g.bandTiles;
         g.bandTiles = ((g.bandTiles + g.stripeTiles - 1) / g.stripeTiles) * g.stripeTiles;
     }
@@ -293,23 +284,11 @@ inline RowRange MakeRowRange(const RowGrid& g) { return RowRange{g.firstBlockY, 
 // Tile row of this workgroup. bottomUp: the grid walks the tile rows from the bottom of the frame, so that -- with the sky at the top, as usual -- the workgroups dispatched
 // last are the ones that leave at the tile test, and the stream of sky tiles runs in the shadow of the draining geometry tiles instead of in front of them. Measured per
 // pass (profiles/r04_v_*, r04_w_*): the temporal-accumulation kernels and the RELAX passes gain 1-1.5 %, the REBLUR spatial passes lose 1-2 % (their L2 working set follows
-// the dispatch front): each kernel names its order. NRD_REVERSE_TILE_ROWS = 0 / 1 forces top-down / bottom-up everywhere (A/B).
-#ifndef NRD_ALT_TILE_ORDER
-#define NRD_ALT_TILE_ORDER 0 // 1: REBLUR's Blur and TemporalStabilization walk the tile rows bottom-up (kernels_reblur_spatial.hip: the reference's alternating CTA order)
-#endif
-#ifndef NRD_REVERSE_TILE_ROWS
-#define NRD_REVERSE_TILE_ROWS -1
-#endif
+// the dispatch front): each kernel names its order.
 __device__ __forceinline__ int BlockTileY(const RowRange& r, bool bottomUp = false) {
-    const bool reverse = NRD_REVERSE_TILE_ROWS < 0 ? bottomUp : NRD_REVERSE_TILE_ROWS != 0;
-    return r.firstBlockY + (reverse ? (int)(gridDim.y - 1u - blockIdx.y) : (int)blockIdx.y);
+    return r.firstBlockY + (bottomUp ? (int)(gridDim.y - 1u - blockIdx.y) : (int)blockIdx.y);
 }
-// NRD_XCD_STAIRCASE_ROWS = K > 0 (A/B switch, off): in EVERY pass the stripes move on by one XCD every K tile rows (see BlockTileXRotated below, which is that with K = 1 for the passes
-// that want it unconditionally)
-#ifndef NRD_XCD_STAIRCASE_ROWS
-#define NRD_XCD_STAIRCASE_ROWS 0
-#endif
-__device__ __forceinline__ int BlockTileXPlain(const RowRange& r) {
+__device__ __forceinline__ int BlockTileX(const RowRange& r) {
     const unsigned bx = blockIdx.x;
     if (!r.bandTiles)
         return (int)bx;
@@ -319,20 +298,13 @@ __device__ __forceinline__ int BlockTileXPlain(const RowRange& r) {
     const unsigned stripe = j / (unsigned)r.stripeTiles, within = j - stripe * (unsigned)r.stripeTiles;
     return (int)((stripe * 8u + xcd) * (unsigned)r.stripeTiles + within);
 }
-__device__ __forceinline__ int BlockTileX(const RowRange& r) {
-    const int t = BlockTileXPlain(r);
-    if (NRD_XCD_STAIRCASE_ROWS == 0 || !r.bandTiles)
-        return t;
-    const unsigned blockY = (unsigned)BlockTileY(r);
-    return (int)(((unsigned)t + (blockY / (unsigned)(NRD_XCD_STAIRCASE_ROWS ? NRD_XCD_STAIRCASE_ROWS : 1)) * (unsigned)r.stripeTiles) % gridDim.x);
-}
 
 // The same with the tile columns of tile row `blockY` moved on by one stripe per row: the stripes of one XCD form a staircase instead of a column. For passes whose work is
 // concentrated in a vertical feature -- the columns that enter the screen under a yawing camera, where RELAX HistoryFix does all of its work -- the XCD-aware order
 // puts that feature on ONE XCD (32 of the 256 CUs); rotated, every XCD gets every eighth tile row of it. Costs the L2 locality of vertical neighbours: only for passes
 // that read no vertical halo worth keeping.
 __device__ __forceinline__ int BlockTileXRotated(const RowRange& r, int blockY) {
-    const int t = BlockTileXPlain(r);
+    const int t = BlockTileX(r);
     if (!r.bandTiles)
         return t;
     return (int)(((unsigned)t + (unsigned)blockY * (unsigned)r.stripeTiles) % gridDim.x);

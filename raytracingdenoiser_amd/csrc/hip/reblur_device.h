@@ -235,11 +235,7 @@ NRD_D float GetEncodingAwareNormalWeight(float3 Ncurr, float3 Nprev, float maxAn
     return SmoothStep01(1.0f - Div(angle - curvatureAngle - thresholdAngle, maxAngle));
 }
 NRD_D float GetDisocclusionThreshold(float disocclusionThreshold, float frustumSize, float NoV) { return frustumSize * Sat(Div(disocclusionThreshold, Max(0.01f, NoV))); }
-#if NRD_EXPERIMENT_NO_MATERIALS // A/B builds only: what a compile-time "no material test in this frame" flag would buy (tools/build_variant.py)
-NRD_D bool CompareMaterials(float, float, float) { return true; }
-#else
 NRD_D bool CompareMaterials(float m0, float m, float minm) { return Max(m0, minm) == Max(m, minm); }
-#endif
 
 NRD_D float GetMinAllowedLimitForHitDistNonLinearAccumSpeed(const ReblurCB& c, float roughness) {
     float frameNum = 0.5f * GetSpecMagicCurve(roughness) * c.gMaxAccumulatedFrameNum;
@@ -896,9 +892,6 @@ struct ReblurSignal<SIGNAL_RADIANCE> {
     // conversions -- 2 selects instead of 4, and the conversions then sit directly in front of the accumulating multiply-adds, where the compiler folds
     // them into v_fma_mix_f32 (the conversion of an fp16 value is exact, so cvt + fma and fma_mix are the same number). Same values bit for bit.
     static NRD_D float4 LoadOrZero(const Plane& p, int x, int y, bool zero) {
-#if NRD_EXPERIMENT_LEGACY_DENANIFY // A/B builds only (tools/build_variant.py): the selection after the conversions, as up to round 3
-        return Select(zero, F4(0.0f), LoadRGBA16F(p, x, y));
-#endif
         return RawOrZero(*TexelPtr<const uint2>(p, x, y), zero);
     }
     static NRD_D float4 RawOrZero(uint2 raw, bool zero) {

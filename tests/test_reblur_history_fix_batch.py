@@ -1,4 +1,4 @@
-"""REBLUR HistoryFix requests the texels of its reconstruction taps in groups (kernels_reblur_history.hip NRD_HF_TAP_BATCH) and sums them in the reference's order:
+"""REBLUR HistoryFix requests the texels of its reconstruction taps in groups (kernels_reblur_history.hip hf::TAP_BATCH) and sums them in the reference's order:
 no value may change. Every case is held against the oracle bit for bit -- every user output and every pool plane of every frame -- on the paths the grouping touches:
 all pixels young (frames 0-1), young and old lanes mixed in one wave (later frames of a moving camera), taps clamped at every edge (stride 14 reaches +-28 px),
 partial tiles, every settings field the loop reads, every instantiation of the kernel, and a camera cut in mid-sequence."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # (development) kernel-trace A/B of library variants and run-time switches on the GPU box:
-#   bash tools/ab_session.sh TAG WORKLOAD GREP NAME[:ENV=VAL,...][@VARIANT] ...     e.g.  bash tools/ab_session.sh r06_d relax_ds_sh Atrous base g32@g32 march:NRD_HIP_ATROUS_MARCH=16   (GREP: ONE word)
+#   bash tools/ab_session.sh TAG WORKLOAD GREP NAME[:ENV=VAL,...][@VARIANT] ...     e.g.  bash tools/ab_session.sh r06_d reblur_ds Spatial base g32@g32 generic:NRD_HIP_GENERIC_TAPS=1   (GREP: ONE word)
 cd "$(dirname "$0")/.." 2>/dev/null; export TMPDIR=/tmp
 tag=$1; w=$2; pat=$3; shift 3
 out=${OUT_DIR:-session_out}; mkdir -p $out

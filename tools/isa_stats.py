@@ -1,5 +1,6 @@
 """Static instruction statistics per kernel of a `hipcc -S --cuda-device-only` listing (optionally next to a second listing).
 usage: python tools/isa_stats.py a.s [b.s] [--filter substr] [--top N]
+       python tools/isa_stats.py --identical OLD NEW [--rename FILE]     (files or directories of listings; exit status 1 if a kernel present in both differs: `identical`)
 Columns: VALU / SALU / VMEM / LDS instruction counts, VGPRs, occupancy (waves per SIMD), scratch bytes, LDS bytes.
 --cost adds a static cost estimate from the measured gfx950 price lists (profiles/r02_b_valu_bench.txt, r02_c_gather_bench.txt): SIMD cycles of VALU issue per wave,
 CU cycles of the L1 request path per wave and (conflict-free) LDS-array cycles per wave, and the time both bounds give for --pixels P (default 2560x1440) on 256 CUs at 2.4 GHz. Static = every
@@ -31,9 +32,55 @@ def parse(path):
         c = collections.Counter(ins)
         grp = lambda *ps: sum(v for k, v in c.items() if k.startswith(ps))
         meta = {k: int(v) for k, v in re.findall(r"; (NumVgprs|Occupancy|ScratchSize|LDSByteSize): (\d+)", chunk)}
+        # the instruction lines and block labels as they stand, comments stripped, with the function index of the block labels (.LBB<n>_<m>: <n> counts the functions
+        # of the listing, so it moves when a kernel in front is removed) normalised
+        text = [re.sub(r"\.LBB\d+_", ".LBB_", l.split(";")[0].rstrip()) for l in body.split("\n") if (l.startswith("\t") and not l.strip().startswith((".", ";"))) or l.startswith(".LBB")]
         res[name] = dict(total=len(ins), valu=grp("v_"), salu=grp("s_"), vmem=grp("global_", "buffer_", "flat_"), lds=grp("ds_"), pk=grp("v_pk_"), trans=grp("v_rcp", "v_sqrt", "v_rsq", "v_exp", "v_log"),
-                         vgpr=meta.get("NumVgprs", -1), occ=meta.get("Occupancy", -1), scratch=meta.get("ScratchSize", -1), ldsb=meta.get("LDSByteSize", -1), counter=c)
+                         vgpr=meta.get("NumVgprs", -1), occ=meta.get("Occupancy", -1), scratch=meta.get("ScratchSize", -1), ldsb=meta.get("LDSByteSize", -1), counter=c, text=text)
     return res
+
+
+def identical(argv):
+    """--identical OLD NEW [--rename FILE]: are the kernels present in both listings (a listing = one .s file or a directory of them) the same instruction lines, with the
+    same NumVgprs / Occupancy / ScratchSize / LDSByteSize? FILE pairs kernels whose template argument list changed: lines `old demangled name<TAB>new demangled name`.
+    Prints the counts identical / removed / added / differing with the names of all but the identical ones; exit status 1 if any kernel differs."""
+    import os
+
+    rename = {}
+    if "--rename" in argv:
+        i = argv.index("--rename")
+        rename = dict(l.rstrip("\n").split("\t") for l in open(argv[i + 1]) if "\t" in l)
+        del argv[i:i + 2]
+
+    def load(path):
+        files = sorted(os.path.join(path, f) for f in os.listdir(path) if f.endswith(".s")) if os.path.isdir(path) else [path]
+        kernels = {}
+        for f in files:
+            kernels.update(parse(f))
+        names = demangle(list(kernels))
+        return {names[k]: v for k, v in kernels.items()}
+
+    old, new = load(argv[0]), load(argv[1])
+    old = {rename.get(k, k): v for k, v in old.items()}
+    same, differing = 0, []
+    for name in sorted(set(old) & set(new)):
+        a, b = old[name], new[name]
+        what = [k for k in ("vgpr", "occ", "scratch", "ldsb") if a[k] != b[k]]
+        if a["text"] != b["text"]:
+            first = next((i for i, (x, y) in enumerate(zip(a["text"], b["text"])) if x != y), min(len(a["text"]), len(b["text"])))
+            what.append("instruction line %d of %d / %d" % (first, len(a["text"]), len(b["text"])))
+        if what:
+            differing.append((name, what))
+        else:
+            same += 1
+    removed, added = sorted(set(old) - set(new)), sorted(set(new) - set(old))
+    print("identical %d, removed %d, added %d, differing %d" % (same, len(removed), len(added), len(differing)))
+    for tag, names in (("removed", removed), ("added", added)):
+        for n in names:
+            print("%s: %s" % (tag, n))
+    for n, what in differing:
+        print("DIFFERS: %s: %s" % (n, ", ".join(what)))
+    return 1 if differing else 0
 
 
 FULL_RATE = ("v_fma_f32", "v_fmac_f32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mov_b32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32",
@@ -67,6 +114,9 @@ def cost(counter):
 
 def main():
     args = [a for a in sys.argv[1:]]
+    if "--identical" in args:
+        args.remove("--identical")
+        sys.exit(identical(args))
     flt, top = "", 0
     want_cost = "--cost" in args
     if want_cost:
