@@ -42,6 +42,40 @@ struct TaPlanes {
     Plane inDiffSh, inSpecSh, historyDiffSh, historySpecSh, outDiffSh, outSpecSh; // SH family (RGBA16F)
 };
 
+// The layout assumptions of the pass, ONE list for both sides (SGPR diet, planes.h): every full-resolution plane has the (w, h) of viewZ, the pool planes of one format
+// share their pitch too. The kernel applies the list with ShareSize / ShareLayout (TaShareLayouts), the launcher verifies it with SameSize / SameLayout (TaCheckLayouts),
+// so a plane cannot be named on one side only.
+// (Planes: TaPlanes in the kernel, which overwrites fields; const TaPlanes in the launcher, which only reads)
+template <bool DIFF, bool OCC, typename Planes, typename Op>
+__host__ __device__ __forceinline__ void TaSharedLayouts(Planes& P, Op& op) {
+    const Plane size = P.viewZ, rgba16 = DIFF ? P.historyDiff : P.historySpec, r16 = DIFF ? P.historyDiffFast : P.historySpecFast;
+    op.Size(P.decodedNR, size), op.Size(P.mv, size), op.Size(P.prevViewZ, size), op.Size(P.prevNormalRoughness, size), op.Size(P.prevInternalData, size);
+    op.Size(P.inDiff, size), op.Size(P.inSpec, size), op.Size(P.inSpecHitDistForTracking, size), op.Size(P.outData1, size), op.Size(P.outData2, size);
+    if (OCC) { // the history planes are the user's OUT_*_HITDIST (own pitch); only the pool outputs share a layout
+        const Plane sig = DIFF ? P.outDiff : P.outSpec;
+        op.Size(P.historyDiff, size), op.Size(P.historySpec, size), op.Layout(P.outDiff, sig), op.Layout(P.outSpec, sig);
+    } else {
+        op.Layout(P.historyDiff, rgba16), op.Layout(P.historySpec, rgba16), op.Layout(P.outDiff, rgba16), op.Layout(P.outSpec, rgba16);
+    }
+    op.Layout(P.historyDiffFast, r16), op.Layout(P.historySpecFast, r16), op.Layout(P.prevSpecHitDistForTracking, r16), op.Layout(P.outDiffFast, r16), op.Layout(P.outSpecFast, r16),
+        op.Layout(P.outSpecHitDistForTracking, r16);
+}
+struct TaShareLayouts { // kernel side: the fields of the by-value Plane copies are overwritten with those of one representative
+    template <typename T>
+    NRD_D void Size(T& p, const Plane& ref) { ShareSize(p, ref); }
+    NRD_D void Layout(Plane& p, const Plane& ref) { ShareLayout(p, ref); }
+};
+struct TaCheckLayouts { // launcher side
+    bool ok = true;
+    template <typename T>
+    void Size(const T& p, const Plane& ref) { ok = ok && SameSize(p, ref); }
+    void Layout(const Plane& p, const Plane& ref) { ok = ok && SameLayout(p, ref); }
+};
+
+// Constants are re-read from LDS after each phase boundary of the tile function instead of being kept in VGPRs for the whole kernel (a compiler
+// memory barrier: the LDS loads cannot be hoisted above it)
+#define NRD_CONSTANTS_PHASE() asm volatile("" ::: "memory")
+
 template <typename T>
 NRD_D void WindowHistoryTexels(const HistoryFilter&, const uint2*, int, int, int, T&) {} // other storage kinds have no window kernel
 // the 2x2 of the Load-based bilinear path (texels outside the plane read as 0); `shift` selects the half of the window dword (0 diffuse, 16 specular)
@@ -57,6 +91,74 @@ NRD_D void WindowFastTexels(const HistoryFilter& h, const uint32_t* win, int wx0
 template <typename T>
 NRD_D void WindowFastTexels(const HistoryFilter&, const uint32_t*, int, int, const Plane&, int, T&) {}
 
+// quad (i, j)(i+1, j)(i, j+1)(i+1, j+1) of a 4x4 footprint in an LDS window: xo / yo are the clamped coordinates relative to the window (yo in rows of WIN_W)
+template <typename Win>
+NRD_D float4 WindowQuadZ(const Win& win, const int (&xo)[4], const int (&yo)[4], int i, int j) {
+    return F4(win[yo[j] + xo[i]], win[yo[j] + xo[i + 1]], win[yo[j + 1] + xo[i]], win[yo[j + 1] + xo[i + 1]]);
+}
+template <typename Win>
+NRD_D void WindowQuadId(const Win& win, const int (&xo)[4], const int (&yo)[4], int i, int j, uint32_t (&q)[4]) {
+    q[0] = win[yo[j] + xo[i]], q[1] = win[yo[j] + xo[i + 1]], q[2] = win[yo[j + 1] + xo[i]], q[3] = win[yo[j + 1] + xo[i + 1]];
+}
+// the same quad from a plane, texel by texel with clamped coordinates (a footprint on the border of the plane)
+NRD_D float4 FetchClampedQuadR32F(const Plane& p, int x, int y) {
+    return F4(FetchClampedR32F(p, x, y), FetchClampedR32F(p, x + 1, y), FetchClampedR32F(p, x, y + 1), FetchClampedR32F(p, x + 1, y + 1));
+}
+NRD_D void FetchClampedQuadR16U(const Plane& p, int x, int y, uint32_t (&q)[4]) {
+    q[0] = FetchClampedR16U(p, x, y);
+    q[1] = FetchClampedR16U(p, x + 1, y);
+    q[2] = FetchClampedR16U(p, x, y + 1);
+    q[3] = FetchClampedR16U(p, x + 1, y + 1);
+}
+NRD_D float MaterialMatch(float materialID, uint32_t packedInternalData, float minMaterialID) {
+    return CompareMaterials(materialID, UnpackInternalData(packedInternalData).z, minMaterialID) ? 1.0f : 0.0f;
+}
+// ... for the three texels i, j, k of a quad of packed internal data (the fourth is the corner outside the 12-texel footprint)
+NRD_D float3 MaterialMatch3(float materialID, float minMaterialID, const uint32_t (&q)[4], int i, int j, int k) {
+    return F3(MaterialMatch(materialID, q[i], minMaterialID), MaterialMatch(materialID, q[j], minMaterialID), MaterialMatch(materialID, q[k], minMaterialID));
+}
+
+// Written once for both signals. Firefly suppressor (reference REBLUR_TemporalAccumulation.hlsli:756-771 for specular, :888-903 for diffuse; neither occlusion kind
+// has it): clamps the luma of the accumulated result against the history's; the two factors are kept for the clamp of the fast history (:788-792, :918-922).
+struct TaFirefly {
+    float maxRelativeIntensity, antifireflyFactor;
+};
+template <int KIND, bool SH, typename S>
+NRD_D TaFirefly SuppressFireflies(const ReblurCB& c, float accumSpeed, const S& history, S& result, float4& shResult) {
+    TaFirefly f = {0.0f, 0.0f};
+    if (KIND == SIGNAL_RADIANCE) {
+        f.maxRelativeIntensity = c.gFireflySuppressorMinRelativeScale + Div(REBLUR_FIREFLY_SUPPRESSOR_MAX_RELATIVE_INTENSITY, accumSpeed + 1.0f);
+        f.antifireflyFactor = accumSpeed * c.gMaxBlurRadius * REBLUR_FIREFLY_SUPPRESSOR_RADIUS_SCALE;
+        f.antifireflyFactor = Div(f.antifireflyFactor, 1.0f + f.antifireflyFactor);
+
+        float lumaResult = GetLuma(result);
+        float lumaClamped = Min(lumaResult, GetLuma(history) * f.maxRelativeIntensity);
+        lumaClamped = Lerp(lumaResult, lumaClamped, f.antifireflyFactor);
+        result = ChangeLuma(result, lumaClamped);
+        if (SH) {
+            float k = GetLumaScale(Length(Xyz(shResult)), lumaClamped);
+            shResult = F4(shResult.x * k, shResult.y * k, shResult.z * k, shResult.w);
+        }
+    }
+    return f;
+}
+// ... and its clamp of the fast history
+template <int KIND, typename S>
+NRD_D float ClampFastHistory(const TaFirefly& f, const S& history, float fastResult) {
+    if (KIND == SIGNAL_RADIANCE) {
+        float fastClamped = Min(fastResult, GetLuma(history) * f.maxRelativeIntensity * REBLUR_FIREFLY_SUPPRESSOR_FAST_RELATIVE_INTENSITY);
+        fastResult = Lerp(fastResult, fastClamped, f.antifireflyFactor);
+    }
+    return fastResult;
+}
+// Written once for both signals. The occlusion family resolves a checkerboarded pixel without data from its two horizontal neighbours in the half-width input
+// (columns x0, x1; weights wc: "Checkerboard" in the tile function)
+template <typename Sig>
+NRD_D typename Sig::type ResolveCheckerboard(const Plane& in, int x0, int x1, int py, float2 wc) {
+    typename Sig::type s0 = Select(wc.x == 0.0f, Sig::Zero(), Sig::Load(in, x0, py));
+    typename Sig::type s1 = Select(wc.y == 0.0f, Sig::Zero(), Sig::Load(in, x1, py));
+    return s0 * wc.x + s1 * wc.y;
+}
 
 // PERF = REBLUR_PERFORMANCE_MODE: no Catmull-Rom history fetches (REBLUR_USE_CATROM_FOR_*_MOTION_IN_TA = 0, REBLUR_Config.hlsli:196-201)
 // OCC = occlusion family (REBLUR_OCCLUSION): hit-distance-only signals in R16_UNORM, no pre-pass output to read, no DATA2, no firefly suppressor
@@ -72,7 +174,11 @@ NRD_D void WindowFastTexels(const HistoryFilter&, const uint32_t*, int, int, con
 // where they are used. Results are bit-identical by construction (same texels, same arithmetic). A workgroup whose box does not fit WIN_W x WIN_H
 // (a silhouette with large parallax, a jump of the camera) writes 1 into its byte of P.tileFlags and leaves; MODE 2, the unchanged global-memory kernel
 // behind a flag test, is launched right after and processes exactly those tiles. MODE 0 = the plain kernel (all other signal kinds / the performance mode).
-// The pass for one 32x8 tile (tile column tileX, tile row blockY of the frame); the kernel below is a thin wrapper
+// The pass for one 32x8 tile (tile column tileX, tile row blockY of the frame); the kernel below is a thin wrapper.
+// What both signals and both sides share stands in front of this function: TaSharedLayouts, the window / clamped quads, MaterialMatch, SuppressFireflies +
+// ClampFastHistory, ResolveCheckerboard. Splitting the body itself into phases is open work: a first split changed the scratch size of nine kernels, and which
+// phases do that is not yet known (profiles/HISTORY.md "TemporalAccumulation: one list of layouts ..."). The statement order below is the request schedule that
+// was measured into place.
 template <bool DIFF, bool SPEC, bool PERF, int KIND, bool SH, int MODE>
 __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& cArg, TaPlanes P, const RowRange& rr, const int tileX, const int blockY) {
     typedef ReblurSignal<KIND> Sig;
@@ -86,17 +192,8 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
 
     // SGPR diet (planes.h): one (w, h) for every full-resolution plane, one pitch per pool format; verified by the launcher
     {
-        const Plane size = P.viewZ, rgba16 = DIFF ? P.historyDiff : P.historySpec, r16 = DIFF ? P.historyDiffFast : P.historySpecFast;
-        ShareSize(P.decodedNR, size), ShareSize(P.mv, size), ShareSize(P.prevViewZ, size), ShareSize(P.prevNormalRoughness, size), ShareSize(P.prevInternalData, size);
-        ShareSize(P.inDiff, size), ShareSize(P.inSpec, size), ShareSize(P.inSpecHitDistForTracking, size), ShareSize(P.outData1, size), ShareSize(P.outData2, size);
-        if (OCC) { // the history planes are the user's OUT_*_HITDIST (own pitch); only the pool outputs share a layout
-            const Plane sig = DIFF ? P.outDiff : P.outSpec;
-            ShareSize(P.historyDiff, size), ShareSize(P.historySpec, size), ShareLayout(P.outDiff, sig), ShareLayout(P.outSpec, sig);
-        } else {
-            ShareLayout(P.historyDiff, rgba16), ShareLayout(P.historySpec, rgba16), ShareLayout(P.outDiff, rgba16), ShareLayout(P.outSpec, rgba16);
-        }
-        ShareLayout(P.historyDiffFast, r16), ShareLayout(P.historySpecFast, r16), ShareLayout(P.prevSpecHitDistForTracking, r16), ShareLayout(P.outDiffFast, r16), ShareLayout(P.outSpecFast, r16),
-            ShareLayout(P.outSpecHitDistForTracking, r16);
+        TaShareLayouts share;
+        TaSharedLayouts<DIFF, OCC>(P, share);
     }
     __shared__ float s_HitDistForTracking[BUF_Y * BUF_STRIDE];
     constexpr int WIN_TEXELS = MODE == 1 ? WIN_W * WIN_H : 1;
@@ -165,9 +262,6 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
     }
     __syncthreads();
     const ReblurCB& c = s_Constants;
-// Constants are re-read from LDS after each phase boundary instead of being kept in VGPRs for the whole kernel (a compiler
-// memory barrier: the LDS loads cannot be hoisted above it)
-#define NRD_CONSTANTS_PHASE() asm volatile("" ::: "memory")
 
     // MODE 1: every thread stays until the window is filled. A thread without a pixel to denoise runs the prologue on a position clamped into the rect
     // (lpx, lpy: its loads stay legal, its values are never used), stores nothing and is left out of the bounding box.
@@ -327,16 +421,12 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
 #pragma unroll
         for (int i = 0; i < 4; i++)
             xo[i] = ClampI(cx + i, 0, W1) - wx0, yo[i] = (ClampI(cy + i, 0, H1) - wy0) * WIN_W;
-#define WIN_Z(i, j) s_WinZ[yo[j] + xo[i]]
-#define WIN_ID(i, j) s_WinId[yo[j] + xo[i]]
-        smbViewZ0 = F4(WIN_Z(0, 0), WIN_Z(1, 0), WIN_Z(0, 1), WIN_Z(1, 1)), smbViewZ1 = F4(WIN_Z(2, 0), WIN_Z(3, 0), WIN_Z(2, 1), WIN_Z(3, 1));
-        smbViewZ2 = F4(WIN_Z(0, 2), WIN_Z(1, 2), WIN_Z(0, 3), WIN_Z(1, 3)), smbViewZ3 = F4(WIN_Z(2, 2), WIN_Z(3, 2), WIN_Z(2, 3), WIN_Z(3, 3));
-        id0[0] = WIN_ID(0, 0), id0[1] = WIN_ID(1, 0), id0[2] = WIN_ID(0, 1), id0[3] = WIN_ID(1, 1);
-        id1[0] = WIN_ID(2, 0), id1[1] = WIN_ID(3, 0), id1[2] = WIN_ID(2, 1), id1[3] = WIN_ID(3, 1);
-        id2[0] = WIN_ID(0, 2), id2[1] = WIN_ID(1, 2), id2[2] = WIN_ID(0, 3), id2[3] = WIN_ID(1, 3);
-        id3[0] = WIN_ID(2, 2), id3[1] = WIN_ID(3, 2), id3[2] = WIN_ID(2, 3), id3[3] = WIN_ID(3, 3);
-#undef WIN_Z
-#undef WIN_ID
+        smbViewZ0 = WindowQuadZ(s_WinZ, xo, yo, 0, 0), smbViewZ1 = WindowQuadZ(s_WinZ, xo, yo, 2, 0);
+        smbViewZ2 = WindowQuadZ(s_WinZ, xo, yo, 0, 2), smbViewZ3 = WindowQuadZ(s_WinZ, xo, yo, 2, 2);
+        WindowQuadId(s_WinId, xo, yo, 0, 0, id0);
+        WindowQuadId(s_WinId, xo, yo, 2, 0, id1);
+        WindowQuadId(s_WinId, xo, yo, 0, 2, id2);
+        WindowQuadId(s_WinId, xo, yo, 2, 2, id3);
         const int nx0 = ClampI(bx, 0, W1) - wx0, nx1 = ClampI(bx + 1, 0, W1) - wx0, ny0 = (ClampI(by, 0, H1) - wy0) * WIN_W, ny1 = (ClampI(by + 1, 0, H1) - wy0) * WIN_W;
         n00 = InBounds(P.prevNormalRoughness, bx, by) ? s_WinN[ny0 + nx0] : NrRawZero();
         n10 = InBounds(P.prevNormalRoughness, bx + 1, by) ? s_WinN[ny0 + nx1] : NrRawZero();
@@ -380,17 +470,12 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
         id2[0] = ir2.x & 0xFFFFu, id2[1] = ir2.x >> 16, id2[2] = ir3.x & 0xFFFFu, id2[3] = ir3.x >> 16;
         id3[0] = ir2.y & 0xFFFFu, id3[1] = ir2.y >> 16, id3[2] = ir3.y & 0xFFFFu, id3[3] = ir3.y >> 16;
         if (!footprintInterior) {
-    #define QUADZ(ox, oy) \
-        F4(FetchClampedR32F(P.prevViewZ, cx + ox, cy + oy), FetchClampedR32F(P.prevViewZ, cx + ox + 1, cy + oy), FetchClampedR32F(P.prevViewZ, cx + ox, cy + oy + 1), FetchClampedR32F(P.prevViewZ, cx + ox + 1, cy + oy + 1))
-            smbViewZ0 = QUADZ(0, 0), smbViewZ1 = QUADZ(2, 0), smbViewZ2 = QUADZ(0, 2), smbViewZ3 = QUADZ(2, 2);
-    #undef QUADZ
-    #define QUADU(q, ox, oy)                                                   \
-        q[0] = FetchClampedR16U(P.prevInternalData, cx + ox, cy + oy);         \
-        q[1] = FetchClampedR16U(P.prevInternalData, cx + ox + 1, cy + oy);     \
-        q[2] = FetchClampedR16U(P.prevInternalData, cx + ox, cy + oy + 1);     \
-        q[3] = FetchClampedR16U(P.prevInternalData, cx + ox + 1, cy + oy + 1);
-            QUADU(id0, 0, 0) QUADU(id1, 2, 0) QUADU(id2, 0, 2) QUADU(id3, 2, 2)
-    #undef QUADU
+            smbViewZ0 = FetchClampedQuadR32F(P.prevViewZ, cx, cy), smbViewZ1 = FetchClampedQuadR32F(P.prevViewZ, cx + 2, cy);
+            smbViewZ2 = FetchClampedQuadR32F(P.prevViewZ, cx, cy + 2), smbViewZ3 = FetchClampedQuadR32F(P.prevViewZ, cx + 2, cy + 2);
+            FetchClampedQuadR16U(P.prevInternalData, cx, cy, id0);
+            FetchClampedQuadR16U(P.prevInternalData, cx + 2, cy, id1);
+            FetchClampedQuadR16U(P.prevInternalData, cx, cy + 2, id2);
+            FetchClampedQuadR16U(P.prevInternalData, cx + 2, cy + 2, id3);
         }
         if (!normalsInterior) {
             n00 = InBounds(P.prevNormalRoughness, bx, by) ? LoadNrRaw(P.prevNormalRoughness, bx, by) : NrRawZero();
@@ -468,12 +553,10 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
     // instructions) sit behind a UNIFORM test of the constants -- same values, as in the spatial passes (kernels_reblur_spatial.hip "compareMaterials").
     float minMaterialID = Min(c.gSpecMinMaterial, c.gDiffMinMaterial);
     if (minMaterialID < 3.0f) {
-#define MATCMP(p) (CompareMaterials(materialID, UnpackInternalData(p).z, minMaterialID) ? 1.0f : 0.0f)
-        smbOcclusion0 = smbOcclusion0 * F3(MATCMP(id0[1]), MATCMP(id0[2]), MATCMP(id0[3]));
-        smbOcclusion1 = smbOcclusion1 * F3(MATCMP(id1[0]), MATCMP(id1[2]), MATCMP(id1[3]));
-        smbOcclusion2 = smbOcclusion2 * F3(MATCMP(id2[0]), MATCMP(id2[1]), MATCMP(id2[3]));
-        smbOcclusion3 = smbOcclusion3 * F3(MATCMP(id3[0]), MATCMP(id3[1]), MATCMP(id3[2]));
-#undef MATCMP
+        smbOcclusion0 = smbOcclusion0 * MaterialMatch3(materialID, minMaterialID, id0, 1, 2, 3);
+        smbOcclusion1 = smbOcclusion1 * MaterialMatch3(materialID, minMaterialID, id1, 0, 2, 3);
+        smbOcclusion2 = smbOcclusion2 * MaterialMatch3(materialID, minMaterialID, id2, 0, 1, 3);
+        smbOcclusion3 = smbOcclusion3 * MaterialMatch3(materialID, minMaterialID, id3, 0, 1, 2);
     }
     const uint32_t smbInternalData0 = id0[3], smbInternalData1 = id1[2], smbInternalData2 = id2[1], smbInternalData3 = id3[0];
 
@@ -542,11 +625,8 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
         diffAccumSpeed *= Lerp(diffHistoryConfidence, 1.0f, Rcp(1.0f + diffAccumSpeed));
         diffAccumSpeed = Min(diffAccumSpeed, c.gMaxAccumulatedFrameNum);
 
-        if (OCC && !diffHasData) {
-            S d0 = Select(wc.x == 0.0f, Sig::Zero(), Sig::Load(P.inDiff, cbX0, py));
-            S d1 = Select(wc.y == 0.0f, Sig::Zero(), Sig::Load(P.inDiff, cbX1, py));
-            diff = d0 * wc.x + d1 * wc.y;
-        }
+        if (OCC && !diffHasData)
+            diff = ResolveCheckerboard<Sig>(P.inDiff, cbX0, cbX1, py, wc);
 
         if (MODE == 1) {
             WindowHistoryTexels(smbFilter, s_WinDiff, wx0, wy0, WIN_W, smbDiffTexels);
@@ -566,21 +646,7 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
             diffShResult = MixHistoryAndCurrent(c, smbDiffShHistory, LoadRGBA16F(P.inDiffSh, px, py), diffNonLinearAccumSpeed);
         }
 
-        float diffMaxRelativeIntensity = 0.0f, diffAntifireflyFactor = 0.0f;
-        if (KIND == SIGNAL_RADIANCE) { // firefly suppressor (neither occlusion kind has it)
-            diffMaxRelativeIntensity = c.gFireflySuppressorMinRelativeScale + Div(REBLUR_FIREFLY_SUPPRESSOR_MAX_RELATIVE_INTENSITY, diffAccumSpeed + 1.0f);
-            diffAntifireflyFactor = diffAccumSpeed * c.gMaxBlurRadius * REBLUR_FIREFLY_SUPPRESSOR_RADIUS_SCALE;
-            diffAntifireflyFactor = Div(diffAntifireflyFactor, 1.0f + diffAntifireflyFactor);
-
-            float diffLumaResult = GetLuma(diffResult);
-            float diffLumaClamped = Min(diffLumaResult, GetLuma(smbDiffHistory) * diffMaxRelativeIntensity);
-            diffLumaClamped = Lerp(diffLumaResult, diffLumaClamped, diffAntifireflyFactor);
-            diffResult = ChangeLuma(diffResult, diffLumaClamped);
-            if (SH) {
-                float k = GetLumaScale(Length(Xyz(diffShResult)), diffLumaClamped);
-                diffShResult = F4(diffShResult.x * k, diffShResult.y * k, diffShResult.z * k, diffShResult.w);
-            }
-        }
+        const TaFirefly diffFirefly = SuppressFireflies<KIND, SH>(c, diffAccumSpeed, smbDiffHistory, diffResult, diffShResult);
         Sig::Store(P.outDiff, px, py, diffResult);
         if (SH)
             StoreRGBA16F(P.outDiffSh, px, py, diffShResult);
@@ -590,10 +656,7 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
         if (!diffHasData)
             diffFastNonLinearAccumSpeed *= Lerp(1.0f - c.gCheckerboardResolveAccumSpeed, 1.0f, diffFastNonLinearAccumSpeed);
         float diffFastResult = Lerp(smbDiffFastHistory, GetLuma(diff), diffFastNonLinearAccumSpeed);
-        if (KIND == SIGNAL_RADIANCE) {
-            float diffFastClamped = Min(diffFastResult, GetLuma(smbDiffHistory) * diffMaxRelativeIntensity * REBLUR_FIREFLY_SUPPRESSOR_FAST_RELATIVE_INTENSITY);
-            diffFastResult = Lerp(diffFastResult, diffFastClamped, diffAntifireflyFactor);
-        }
+        diffFastResult = ClampFastHistory<KIND>(diffFirefly, smbDiffHistory, diffFastResult);
         Sig::StoreFast(P.outDiffFast, px, py, diffFastResult);
     }
 
@@ -621,11 +684,8 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
         smbSpecAccumSpeed *= Lerp(specHistoryConfidence, 1.0f, Rcp(1.0f + smbSpecAccumSpeed));
         smbSpecAccumSpeed = Min(smbSpecAccumSpeed, c.gMaxAccumulatedFrameNum);
 
-        if (OCC && !specHasData) {
-            S s0 = Select(wc.x == 0.0f, Sig::Zero(), Sig::Load(P.inSpec, cbX0, py));
-            S s1 = Select(wc.y == 0.0f, Sig::Zero(), Sig::Load(P.inSpec, cbX1, py));
-            spec = s0 * wc.x + s1 * wc.y;
-        }
+        if (OCC && !specHasData)
+            spec = ResolveCheckerboard<Sig>(P.inSpec, cbX0, cbX1, py, wc);
 
         NRD_CONSTANTS_PHASE();
         // Curvature estimation along predicted motion
@@ -995,22 +1055,7 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
         specAccumSpeed = Lerp(smbSpecAccumSpeedBoosted, vmbSpecAccumSpeed, virtualHistoryAmount);
         S specHistory = Lerp(smbSpecHistory, vmbSpecHistory, virtualHistoryAmount);
 
-        // Firefly suppressor (not in the occlusion family)
-        float specMaxRelativeIntensity = 0.0f, specAntifireflyFactor = 0.0f;
-        if (KIND == SIGNAL_RADIANCE) {
-            specMaxRelativeIntensity = c.gFireflySuppressorMinRelativeScale + Div(REBLUR_FIREFLY_SUPPRESSOR_MAX_RELATIVE_INTENSITY, specAccumSpeed + 1.0f);
-            specAntifireflyFactor = specAccumSpeed * c.gMaxBlurRadius * REBLUR_FIREFLY_SUPPRESSOR_RADIUS_SCALE;
-            specAntifireflyFactor = Div(specAntifireflyFactor, 1.0f + specAntifireflyFactor);
-
-            float specLumaResult = GetLuma(specResult);
-            float specLumaClamped = Min(specLumaResult, GetLuma(specHistory) * specMaxRelativeIntensity);
-            specLumaClamped = Lerp(specLumaResult, specLumaClamped, specAntifireflyFactor);
-            specResult = ChangeLuma(specResult, specLumaClamped);
-            if (SH) {
-                float k = GetLumaScale(Length(Xyz(specShResult)), specLumaClamped);
-                specShResult = F4(specShResult.x * k, specShResult.y * k, specShResult.z * k, specShResult.w);
-            }
-        }
+        const TaFirefly specFirefly = SuppressFireflies<KIND, SH>(c, specAccumSpeed, specHistory, specResult, specShResult);
 
         Sig::Store(P.outSpec, px, py, specResult);
         if (SH)
@@ -1023,10 +1068,7 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
         float vmbSpecFast = Lerp(vmbSpecFastHistory, GetLuma(spec), vmbSpecFastNonLinearAccumSpeed);
         float specFastResult = Lerp(smbSpecFast, vmbSpecFast, virtualHistoryAmount);
 
-        if (KIND == SIGNAL_RADIANCE) {
-            float specFastClamped = Min(specFastResult, GetLuma(specHistory) * specMaxRelativeIntensity * REBLUR_FIREFLY_SUPPRESSOR_FAST_RELATIVE_INTENSITY);
-            specFastResult = Lerp(specFastResult, specFastClamped, specAntifireflyFactor);
-        }
+        specFastResult = ClampFastHistory<KIND>(specFirefly, specHistory, specFastResult);
         Sig::StoreFast(P.outSpecFast, px, py, specFastResult);
     }
 
@@ -1118,19 +1160,10 @@ static const char* LaunchTemporalAccumulation(const PassArgs& a) {
     if (k != a.planesNum)
         return "REBLUR temporal accumulation: unexpected resource count";
     {
-        const Plane size = P.viewZ, rgba16 = DIFF ? P.historyDiff : P.historySpec, r16 = DIFF ? P.historyDiffFast : P.historySpecFast;
-        bool ok = SameSize(P.decodedNR, size) && SameSize(P.mv, size) && SameSize(P.prevViewZ, size) && SameSize(P.prevNormalRoughness, size) && SameSize(P.prevInternalData, size) &&
-                  SameSize(P.inDiff, size) && SameSize(P.inSpec, size) && SameSize(P.inSpecHitDistForTracking, size) && SameSize(P.outData1, size) && SameSize(P.outData2, size) &&
-                  SameSize(rgba16, size) && SameSize(r16, size);
-        if (OCC) {
-            const Plane sig = DIFF ? P.outDiff : P.outSpec;
-            ok = ok && SameSize(P.historyDiff, size) && SameSize(P.historySpec, size) && SameLayout(P.outDiff, sig) && SameLayout(P.outSpec, sig);
-        } else {
-            ok = ok && SameLayout(P.historyDiff, rgba16) && SameLayout(P.historySpec, rgba16) && SameLayout(P.outDiff, rgba16) && SameLayout(P.outSpec, rgba16);
-        }
-        ok = ok && SameLayout(P.historyDiffFast, r16) && SameLayout(P.historySpecFast, r16) && SameLayout(P.prevSpecHitDistForTracking, r16) && SameLayout(P.outDiffFast, r16) &&
-             SameLayout(P.outSpecFast, r16) && SameLayout(P.outSpecHitDistForTracking, r16);
-        if (!ok)
+        TaCheckLayouts check; // the kernel's list (TaSharedLayouts), and the two representatives of the pool formats themselves
+        TaSharedLayouts<DIFF, OCC>(static_cast<const TaPlanes&>(P), check);
+        check.Size(DIFF ? P.historyDiff : P.historySpec, P.viewZ), check.Size(DIFF ? P.historyDiffFast : P.historySpecFast, P.viewZ);
+        if (!check.ok)
             return "REBLUR temporal accumulation: planes of one frame must share their size (and pool planes of one format their pitch)";
     }
 
