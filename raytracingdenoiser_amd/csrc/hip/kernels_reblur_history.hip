@@ -303,13 +303,37 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, SH ? 0 : NRD_WAVES_REBLUR_HF - (PER
         preSpec = Sig::Load(P.inSpec, qx, qy);
     {
         const int baseX = tileX * TILE_X - hf::BORDER, baseY = blockY * TILE_Y - hf::BORDER;
-        for (int i = threadIdx.x; i < hf::BUF_X * hf::BUF_Y; i += TILE_X * TILE_Y) {
-            int lx = i % hf::BUF_X, ly = i / hf::BUF_X;
-            int gx = ClampI(baseX + lx, 0, rw), gy = ClampI(baseY + ly, 0, rh);
+        if (!SH) {
+            // interior cell (tx + 2, ty + 2): the fast history at the thread's own clamped coordinate, no index arithmetic; the 176 cells around the interior in one pass
+            // of waves 0-2 (reblur_device.h HaloCell). Every request stands in front of the first LDS write, which waits for them all.
+            // (The SH kernels keep the loop below: the two registers this form holds across the halo pass cost them a wave.)
+            float ownDiffFast = 0.0f, ownSpecFast = 0.0f;
             if (DIFF)
-                s_DiffLuma[ly * hf::BUF_STRIDE + lx] = Sig::LoadFast(P.inDiffFast, gx, gy);
+                ownDiffFast = Sig::LoadFast(P.inDiffFast, qx, qy);
             if (SPEC)
-                s_SpecLuma[ly * hf::BUF_STRIDE + lx] = Sig::LoadFast(P.inSpecFast, gx, gy);
+                ownSpecFast = Sig::LoadFast(P.inSpecFast, qx, qy);
+            if (threadIdx.x < HaloCells<TILE_X, TILE_Y, hf::BORDER>()) {
+                int lx, ly;
+                HaloCell<TILE_X, TILE_Y, hf::BORDER>(threadIdx.x, lx, ly);
+                int gx = ClampI(baseX + lx, 0, rw), gy = ClampI(baseY + ly, 0, rh);
+                if (DIFF)
+                    s_DiffLuma[ly * hf::BUF_STRIDE + lx] = Sig::LoadFast(P.inDiffFast, gx, gy);
+                if (SPEC)
+                    s_SpecLuma[ly * hf::BUF_STRIDE + lx] = Sig::LoadFast(P.inSpecFast, gx, gy);
+            }
+            if (DIFF)
+                s_DiffLuma[(ty + hf::BORDER) * hf::BUF_STRIDE + tx + hf::BORDER] = ownDiffFast;
+            if (SPEC)
+                s_SpecLuma[(ty + hf::BORDER) * hf::BUF_STRIDE + tx + hf::BORDER] = ownSpecFast;
+        } else {
+            for (int i = threadIdx.x; i < hf::BUF_X * hf::BUF_Y; i += TILE_X * TILE_Y) {
+                int lx = i % hf::BUF_X, ly = i / hf::BUF_X;
+                int gx = ClampI(baseX + lx, 0, rw), gy = ClampI(baseY + ly, 0, rh);
+                if (DIFF)
+                    s_DiffLuma[ly * hf::BUF_STRIDE + lx] = Sig::LoadFast(P.inDiffFast, gx, gy);
+                if (SPEC)
+                    s_SpecLuma[ly * hf::BUF_STRIDE + lx] = Sig::LoadFast(P.inSpecFast, gx, gy);
+            }
         }
     }
     __syncthreads();
@@ -464,14 +488,21 @@ __global__ __launch_bounds__(TILE_X* TILE_Y, NRD_WAVES_REBLUR_TS) void ReblurTem
         preSpec = Sig::Load(P.inSpec, qx, qy);
     {
         const int baseX = BlockTileX(rr) * TILE_X - ts::BORDER, baseY = blockY * TILE_Y - ts::BORDER;
-        for (int i = threadIdx.x; i < ts::BUF_X * ts::BUF_Y; i += TILE_X * TILE_Y) {
-            int lx = i % ts::BUF_X, ly = i / ts::BUF_X;
+        // The interior of the tile is the workgroup's 256 own texels -- (qx, qy) is the clamped coordinate of cell (tx + 1, ty + 1) --, loaded above: each thread
+        // writes the luma of its own. Only the 84 cells around them are loaded here, in one pass of waves 0-1 (reblur_device.h HaloCell).
+        if (threadIdx.x < HaloCells<TILE_X, TILE_Y, ts::BORDER>()) {
+            int lx, ly;
+            HaloCell<TILE_X, TILE_Y, ts::BORDER>(threadIdx.x, lx, ly);
             int gx = ClampI(baseX + lx, 0, rw), gy = ClampI(baseY + ly, 0, rh);
             if (DIFF)
                 s_DiffLuma[ly * ts::BUF_STRIDE + lx] = GetLuma(Sig::Load(P.inDiff, gx, gy));
             if (SPEC)
                 s_SpecLuma[ly * ts::BUF_STRIDE + lx] = GetLuma(Sig::Load(P.inSpec, gx, gy));
         }
+        if (DIFF)
+            s_DiffLuma[(ty + ts::BORDER) * ts::BUF_STRIDE + tx + ts::BORDER] = GetLuma(preDiff);
+        if (SPEC)
+            s_SpecLuma[(ty + ts::BORDER) * ts::BUF_STRIDE + tx + ts::BORDER] = GetLuma(preSpec);
     }
     __syncthreads();
 

@@ -227,19 +227,18 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
             return; // uniform across the block
         }
 
-        if (MODE == 1) { // (the plain kernels sit at their register budget: there the guides are requested behind the barrier as before)
-            const int qx = min(px, rw), qy = min(max(py, 0), rh);
-            preViewZ = LoadR32F(P.viewZ, qx, qy);
-            preMv = LoadRGBA16F(P.mv, qx, qy);
-            preNormalAndRoughness = LoadDecodedNormalRoughness(P.decodedNR, qx, qy, preMaterialID);
-        }
         const int baseX = tileX * TILE_X - BORDER, baseY = blockY * TILE_Y - BORDER;
-        for (int i = threadIdx.x; i < BUF_X * BUF_Y; i += TILE_X * TILE_Y) {
-            int lx = i % BUF_X, ly = i / BUF_X;
-            int gx = ClampI(baseX + lx, 0, rw), gy = ClampI(baseY + ly, 0, rh);
-            float unusedMaterialID, texelViewZ; // (the viewZ rides in the guide texel: no extra load)
-            s_Normal_Roughness[ly * BUF_STRIDE + lx] = LoadDecodedNormalRoughness(P.decodedNR, gx, gy, unusedMaterialID, texelViewZ);
+        // One cell of the tile: the decoded guide texel at the clamped coordinate (gx, gy) and, with a specular signal, its hit distance for tracking
+        struct TileTexel {
+            float4 normalRoughness;
+            float hitDist, materialID, viewZ;
+        };
+        auto loadTileTexel = [&](int gx, int gy) {
+            TileTexel t;
+            t.hitDist = 0.0f;
+            t.normalRoughness = LoadDecodedNormalRoughness(P.decodedNR, gx, gy, t.materialID, t.viewZ); // (the viewZ rides in the guide texel: no extra load)
             if (SPEC) {
+                float texelViewZ = t.viewZ;
                 const int shift = (OCC && cArg.gSpecCheckerboard != 2) ? 1 : 0; // checkerboarded occlusion input: left half (reference REBLUR_TemporalAccumulation.hlsli:21-27)
                 float hitDist = (OCC || cArg.gSpecPrepassBlurRadius == 0.0f) ? ExtractHitDist(Sig::Load(P.inSpec, gx >> shift, gy)) : LoadR16F(P.inSpecHitDistForTracking, gx, gy);
                 // Without a pre-pass this is the host's NOISY input, which may hold anything beyond the denoising range: such a texel is no sample (0 = "none"). The reference
@@ -247,12 +246,42 @@ __device__ __forceinline__ void ReblurTemporalAccumulationTile(const ReblurCB& c
                 // host leaves a finite value there (DESIGN.md "Input rules").
                 // (checkerboarded: the packed texel holds the data of the pixel of this pair whose parity matches -- that pixel's viewZ decides)
                 if (shift) {
+                    float unusedMaterialID;
                     const int sx = min((gx & ~1) | (int)((cArg.gSpecCheckerboard ^ (uint32_t)gy ^ cArg.gFrameIndex) & 1u), rw);
                     LoadDecodedNormalRoughness(P.decodedNR, sx, gy, unusedMaterialID, texelViewZ);
                 }
                 if ((OCC || cArg.gSpecPrepassBlurRadius == 0.0f) && texelViewZ > cArg.gDenoisingRange)
                     hitDist = 0.0f;
-                s_HitDistForTracking[ly * BUF_STRIDE + lx] = hitDist == 0.0f ? NRD_INF : hitDist;
+                t.hitDist = hitDist == 0.0f ? NRD_INF : hitDist;
+            }
+            return t;
+        };
+        auto storeTileTexel = [&](int lx, int ly, const TileTexel& t) {
+            s_Normal_Roughness[ly * BUF_STRIDE + lx] = t.normalRoughness;
+            if (SPEC)
+                s_HitDistForTracking[ly * BUF_STRIDE + lx] = t.hitDist;
+        };
+        if (MODE == 1) {
+            // Window kernel. The interior of the tile is the workgroup's 256 own texels: (qx, qy) is the clamped coordinate of cell (tx + 1, ty + 1). Each thread requests
+            // its own texel once, keeps the guides and the material, and writes it into its cell; the 84 cells around the interior are
+            // one pass of waves 0-1 (reblur_device.h HaloCell), which waves 2-3 skip on a uniform test.
+            // (The plain kernels sit at their register budget: their scratch size moves with any change of the fill, so they keep the loop below and request their own
+            // guides behind the barrier as before.)
+            const int qx = min(px, rw), qy = min(max(py, 0), rh);
+            preViewZ = LoadR32F(P.viewZ, qx, qy);
+            preMv = LoadRGBA16F(P.mv, qx, qy);
+            const TileTexel own = loadTileTexel(qx, qy);
+            preNormalAndRoughness = own.normalRoughness, preMaterialID = own.materialID;
+            if (threadIdx.x < HaloCells<TILE_X, TILE_Y, BORDER>()) {
+                int lx, ly;
+                HaloCell<TILE_X, TILE_Y, BORDER>(threadIdx.x, lx, ly);
+                storeTileTexel(lx, ly, loadTileTexel(ClampI(baseX + lx, 0, rw), ClampI(baseY + ly, 0, rh)));
+            }
+            storeTileTexel(tx + BORDER, ty + BORDER, own);
+        } else {
+            for (int i = threadIdx.x; i < BUF_X * BUF_Y; i += TILE_X * TILE_Y) {
+                int lx = i % BUF_X, ly = i / BUF_X;
+                storeTileTexel(lx, ly, loadTileTexel(ClampI(baseX + lx, 0, rw), ClampI(baseY + ly, 0, rh)));
             }
         }
         // constants: kernel-argument segment (cArg is the first argument, offset 0) -> LDS, one dword per thread

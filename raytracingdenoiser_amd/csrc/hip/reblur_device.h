@@ -490,6 +490,27 @@ NRD_D float4 LoadRGBA16FOrZero(const Plane& p, int x, int y) { return InBounds(p
 NRD_D float LoadR16FOrZero(const Plane& p, int x, int y) { return InBounds(p, x, y) ? LoadR16F(p, x, y) : 0.0f; }
 NRD_D float4 LoadR10G10B10A2OrZero(const Plane& p, int x, int y) { return InBounds(p, x, y) ? LoadR10G10B10A2(p, x, y) : F4(0.0f); }
 
+// ---- the halo of an LDS tile ------------------------------------------------------------------------------------------------------------
+// A (TX + 2 B) x (TY + 2 B) tile around a TX x TY workgroup: the interior cell of thread (tx, ty) is (tx + B, ty + B) and needs no index arithmetic; the
+// HaloCells<TX, TY, B>() cells around it are numbered h = 0 .. HaloCells - 1 -- the B rows above, the B rows below, then per interior row its B left and B right
+// cells -- so that threads 0 .. HaloCells - 1 fill them in ONE pass (a wave whose threads all lie beyond skips on a uniform test) without a division:
+// compares and selects only.
+template <int TX, int TY, int B>
+constexpr int HaloCells() { return (TX + 2 * B) * (TY + 2 * B) - TX * TY; }
+template <int TX, int TY, int B>
+NRD_D void HaloCell(int h, int& lx, int& ly) {
+    static_assert(B == 1 || B == 2, "2 B is a power of two");
+    constexpr int BX = TX + 2 * B, ROW_CELLS = 2 * B * BX;
+    int r = 0;
+#pragma unroll
+    for (int k = 1; k < 2 * B; k++)
+        r += h >= k * BX ? 1 : 0;
+    const int k = h - ROW_CELLS, j = k & (2 * B - 1);
+    const bool side = k >= 0;
+    lx = side ? (j < B ? j : j + TX) : h - r * BX;
+    ly = side ? B + (k >> (B == 1 ? 1 : 2)) : (r < B ? r : r + TY);
+}
+
 // ---- row-vector fetches of small footprints ----------------------------------------------------------------------------------------
 // The temporal passes read 2x2 and 4x4 texel footprints at data-dependent positions. One load instruction per texel costs the L1 / address path as much
 // as a 16-byte one (profiles/r02_c_gather_bench.txt), so an INTERIOR footprint (no coordinate needs clamping) is fetched row by row with one vector load
