@@ -13,6 +13,7 @@
 //   SG / SH      NRD_SG, NRD_SG_ExtractColor / Direction / RoughnessAA, NRD_SG_Rotate, NRD_SG_ResolveDiffuse / Specular,
 //                NRD_SH_ResolveDiffuse / Specular, NRD_SG_ReJitter                                               NRD.hlsli:541-586, 937-1111
 //   misc         NRD_IsValidRadiance, REBLUR_GetHitDist, NRD_GetNormalizedStrandThickness                         NRD.hlsli:1136-1162
+//   not in NRD.hlsli   NRD_HIP_MixDiffuseHitDist: the diffuse hit distance of combined direct + indirect lighting (reference README, "GREATER TIPS")
 //
 // Build configuration = the library's (nrd::GetLibraryDesc().normalEncoding / roughnessEncoding): define NRD_NORMAL_ENCODING (0..4) and NRD_ROUGHNESS_ENCODING (0..2) to the
 // values the linked libNRD_hip.so was built with before including this file, as the reference asks for NRDEncoding.hlsli (NRD.hlsli:290-309); undefined, they take the
@@ -698,3 +699,19 @@ NRD_HIP_FN float REBLUR_GetHitDist(float normHitDist, float viewZ, float4 hitDis
 // Normalized strand thickness factor in range [0; 1]: 0 - thick enough (in pixels) for a stable multi-pixel projection, 1 - "pixel soup".
 // pixelSize = size of a pixel in world units at "viewZ" = gUnproject * ( isOrtho ? 1.0 : abs( viewZ ) )
 NRD_HIP_FN float NRD_GetNormalizedStrandThickness(float strandThickness, float pixelSize) { return pixelSize / (pixelSize + strandThickness); }
+
+//=================================================================================================================================
+// NOT PART OF NRD.hlsli: the rule of the reference's README "COMBINED DENOISING OF DIRECT AND INDIRECT LIGHTING", as a function
+//=================================================================================================================================
+
+// The hit distance of a DIFFUSE signal that sums direct and indirect lighting (nrdHipPackInputsDirect applies it per sample):
+//   lerp( indirect, direct, min( Ldirect / ( Ldirect + Lindirect + EPS ), maxContribution ) )
+// lumIndirect / lumDirect: _NRD_Luminance of the sanitised radiances. A direct term never makes an invalid hit distance valid: the two are mixed only where both are finite
+// and above 0 and the weight is above 0 (false for a NaN weight), else the indirect hit distance is returned as it is -- a 0 stays 0 and keeps marking the texel for the
+// hit-distance reconstruction. The specular hit distance is the indirect one alone (a light chosen for its diffuse contribution breaks specular reprojection): no function.
+NRD_HIP_FN float NRD_HIP_MixDiffuseHitDist(float hitDistIndirect, float hitDistDirect, float lumIndirect, float lumDirect, float maxContribution) {
+    float c = lumDirect / ((lumDirect + lumIndirect) + NRD_EPS);
+    c = c > 0.0f ? fminf(c, maxContribution) : 0.0f; // (a NaN weight, which fminf would replace by maxContribution, counts as 0)
+    const bool mixed = c > 0.0f && !_NRD_IsInvalid(hitDistIndirect) && hitDistIndirect > 0.0f && !_NRD_IsInvalid(hitDistDirect) && hitDistDirect > 0.0f;
+    return mixed ? nrd_hip_detail::lerp(hitDistIndirect, hitDistDirect, c) : hitDistIndirect;
+}

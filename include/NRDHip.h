@@ -522,6 +522,54 @@ typedef struct NrdHipFrontEndLobes {
 uint32_t nrdHipPackInputsLobes(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSplit* split, const NrdHipFrontEndLobes* lobes,
                                void* hipStream);
 
+// Combined denoising of direct and indirect lighting (reference README "GREATER TIPS: COMBINED DENOISING OF DIRECT AND INDIRECT LIGHTING"): a path tracer with next-event
+// estimation or ReSTIR holds the two in separate planes and wants one REBLUR / RELAX instance to denoise their sum. The README's rule: the radiance is summed; the SPECULAR
+// hit distance is the indirect one alone ("a light chosen for its diffuse contribution breaks specular reprojection"); the DIFFUSE hit distance is
+// lerp( indirect, direct, min( Ldirect / ( Ldirect + Lindirect + EPS ), maxContribution ) ), which gives sharper contact shadows. nrdHipPackInputsDirect does it in the pack
+// launch, each traced byte loaded once. direct == NULL, or a struct in which neither signal has a direct plane, is exactly nrdHipPackInputsDecimated( desc, options, samples,
+// split, guideShift, stream ): the same kernels, the same bytes. The contract is the one above: validated before the first HIP call, nothing enqueued on an error, no
+// allocation, no synchronisation, one launch, capturable into a graph, errors through nrdHipGetLastFrontEndError, the 32-bit limits for every plane and layer.
+// The planes of the descriptor ( desc->diffuse / specular, split->*HitDist, samples ) are the INDIRECT ones under this call. The direct planes are traced data: low-size under
+// guideShift == 1, and under checkerboarding read only at the pixels selected for their signal. A signal without a direct plane is packed as ever: no load is added to it.
+//
+// Per pixel and signal, in unfused fp32 with correctly rounded division. Sample s = 0 .. N - 1, N the signal's sample count; direct layer t = s when the direct stack has N layers:
+//   1. ( rad_i, h_i ), dir_i from indirect layer s; ( rad_d, h_d ), dir_d from direct layer t. h_d is loaded ONLY for the diffuse signal with maxHitDistContribution > 0.
+//   2. hitDistTrimThreshold > 0: h_i and h_d go through NRD_FrontEnd_TrimHitDistance.
+//   3. Demodulating, both radiances are divided by the signal's factor, as the plain call does.
+//   4. P_i, P_d = the mode's packer ( sanitize = true ) for ( rad_i, h_i, dir_i ) and ( rad_d, 0, dir_d ). Every channel that does not carry the hit distance:
+//      C_s = clamp( P_i + P_d, -NRD_FP16_MAX, NRD_FP16_MAX ) -- a no-op below fp16 overflow: the store codec never rounds a sum of two clamped terms to infinity. The packers are
+//      linear in ( radiance, direction x luminance ): this is the packed estimate of the summed signal, in the radiance and the SH modes alike.
+//   5. Hit distance. SPECULAR: h_i, exactly as without `direct` (with samples: NRD_FrontEnd_SpecHitDistAveraging_* over the h_i). DIFFUSE: the packer's hit-distance output for
+//      h = NRD_HIP_MixDiffuseHitDist( h_i, h_d, L_i, L_d, maxHitDistContribution ) (NRD.hip.h), L = _NRD_Luminance( san( rad ) ) of the demodulated radiance, san the packers'
+//      own first line: _NRD_IsInvalid( r ) ? 0 : clamp( r, 0, NRD_FP16_MAX ). A direct term never makes an invalid hit distance valid: an h_i of 0 stays 0, so the texel stays
+//      marked for HitDistanceReconstruction and nrdHipCheckHitDistCoverage. Where no light was sampled ( rad_d NaN or zero, h_d anything ) every channel is the indirect-only one.
+//   6. Over the samples: colour channels ( ( C_0 + C_1 ) + ... ) / float( N ); the diffuse hit-distance channel is the mean of the packed per-sample values, as
+//      nrdHipPackInputsSamples does; then the store codec of the plain call.
+//   7. ONE direct layer under N > 1 (one NEE / ReSTIR sample per pixel under many indirect paths): the direct texel is loaded once; colour = clamp( mean_s( P_i,s ) + P_d );
+//      the diffuse hit distance mixes every h_i,s with the same ( h_d, L_d ) and its own L_i,s, then takes the mean.
+// INVALID_ARGUMENT, naming the field: a direct plane for a signal whose mode is NONE, REBLUR_OCCLUSION or REBLUR_DIRECTIONAL_OCCLUSION (no radiance to weigh by); a missing
+// direction where the mode reads one, or a direction where it reads none; specular.hitDist given (the specular direct distance is never read: .w of an RGBA32_SFLOAT specular
+// direct plane may hold anything); diffuse.hitDist missing when the plane is RGB32_SFLOAT and maxHitDistContribution > 0, given when the plane is RGBA32_SFLOAT or when
+// maxHitDistContribution == 0; maxHitDistContribution NaN, negative or above 1; samplesNum neither 1 nor the signal's count; a non-zero reserved; layer strides that break the
+// rules of nrdHipPackInputsSamples / Split; size, pitch or alignment mismatches as elsewhere. UNSUPPORTED: a format other than those listed.
+// Out of scope: combining with nrdHipPackInputsLobes; the back end (a combined signal resolves like any other).
+#define NRD_HIP_DIRECT_MAX_CONTRIBUTION_DEFAULT 0.5f // README: "0.65 works good as well"
+typedef struct NrdHipDirectSignal {
+    NrdHipPlaneDesc radianceHitDist; // in, RGBA32_SFLOAT, or RGB32_SFLOAT (+ hitDist below): direct radiance.rgb, distance to the sampled light / occluder in .w; data NULL = this signal has no direct term
+    NrdHipPlaneDesc hitDist;         // in, R32_SFLOAT: .w when radianceHitDist is RGB32_SFLOAT -- DIFFUSE signal only
+    NrdHipPlaneDesc direction;       // in, RGBA32_SFLOAT / RGB32_SFLOAT: direction to the light (SH modes)
+    uint64_t radianceHitDistLayerBytes, hitDistLayerBytes, directionLayerBytes;
+    uint32_t samplesNum;             // 0 is read as 1; must be 1 or the signal's own sample count
+    uint32_t reserved;               // must be 0
+} NrdHipDirectSignal;
+typedef struct NrdHipFrontEndDirect {
+    NrdHipDirectSignal diffuse, specular;
+    float maxHitDistContribution;    // [0, 1]; 0 = the diffuse hit distance stays the indirect one and no direct hit distance is read
+    uint32_t reserved;               // must be 0
+} NrdHipFrontEndDirect;
+uint32_t nrdHipPackInputsDirect(const NrdHipFrontEndDesc* desc, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, const NrdHipFrontEndSplit* split,
+                                const NrdHipFrontEndDirect* direct, uint32_t guideShift, void* hipStream);
+
 // Does every pixel have a valid hit distance in the area the hit-distance reconstruction searches? A probabilistic split (above) leaves the hit distance of the lobe that was not
 // traced at 0, and REBLUR / RELAX_HitDistReconstruction look no further than 3x3 or 5x5 texels: a pixel whose area holds no valid sample keeps a hit distance of 0, silently, and
 // the history keeps it. nrdHipCheckInputs cannot see that -- it is a property of a neighbourhood. This call audits the PACKED planes as they will be bound; it needs no executor.
@@ -717,6 +765,7 @@ static_assert(sizeof(NrdHipFrontEndSplit) == 88 && sizeof(NrdHipBackEndSplit) ==
 static_assert(sizeof(NrdHipInputReport) == 72, "mirrored by raytracingdenoiser_amd/api.py");
 static_assert(sizeof(NrdHipBackEndUpsample) == 56, "mirrored by raytracingdenoiser_amd/api.py"); // 2 planes of 24 bytes + 8
 static_assert(sizeof(NrdHipFrontEndLobes) == 168, "mirrored by raytracingdenoiser_amd/api.py"); // 5 planes of 24 bytes + 8 + 5 strides
+static_assert(sizeof(NrdHipDirectSignal) == 104 && sizeof(NrdHipFrontEndDirect) == 216, "mirrored by raytracingdenoiser_amd/api.py"); // 3 planes of 24 bytes + 3 strides + 8; two of them + 8
 static_assert(sizeof(NrdHipCoverageDesc) == 88 && sizeof(NrdHipCoverageReport) == 28, "mirrored by raytracingdenoiser_amd/api.py");
 #endif
 

@@ -194,6 +194,13 @@ public:
     inline bool PackInputsLobes(const NrdHipFrontEndDesc& desc, const NrdHipFrontEndLobes& lobes, const NrdHipFrontEndOptions* options = nullptr, const NrdHipFrontEndSplit* split = nullptr) {
         return nrdHipPackInputsLobes(&desc, options, split, &lobes, m_Stream) == (uint32_t)Result::SUCCESS;
     }
+    // Combined denoising of direct and indirect lighting, the README's "GREATER TIPS" rule (nrdHipPackInputsDirect): the descriptor's signal planes are the INDIRECT ones, "direct"
+    // holds the direct ones; the radiance is summed, the specular hit distance stays the indirect one, the diffuse one is mixed by the direct share of the luminance, capped by
+    // direct.maxHitDistContribution (NRD_HIP_DIRECT_MAX_CONTRIBUTION_DEFAULT). options / samples / split may be NULL; guideShift as in "PackInputsDecimated", default 0
+    inline bool PackInputsDirect(const NrdHipFrontEndDesc& desc, const NrdHipFrontEndDirect& direct, const NrdHipFrontEndOptions* options = nullptr, const NrdHipFrontEndSamples* samples = nullptr,
+        const NrdHipFrontEndSplit* split = nullptr, uint32_t guideShift = 0) {
+        return nrdHipPackInputsDirect(&desc, options, samples, split, &direct, guideShift, m_Stream) == (uint32_t)Result::SUCCESS;
+    }
     // ... and the audit of the dithering that chose the lobes (nrdHipCheckHitDistCoverage): sizeof( NrdHipCoverageReport ) bytes of the caller's device memory are filled in stream
     // order; holes[ s ] != 0 = pixels of signal s with no valid hit distance in the area the reconstruction searches
     inline bool CheckHitDistCoverage(const NrdHipCoverageDesc& desc, void* deviceReport) { return nrdHipCheckHitDistCoverage(&desc, deviceReport, m_Stream) == (uint32_t)Result::SUCCESS; }

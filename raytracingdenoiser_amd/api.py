@@ -346,6 +346,18 @@ class HipFrontEndLobes(C.Structure):  # include/NRDHip.h NrdHipFrontEndLobes
                 ("lobeLayerBytes", C.c_uint64), ("probabilityLayerBytes", C.c_uint64)]
 
 
+DIRECT_MAX_CONTRIBUTION_DEFAULT = 0.5  # include/NRDHip.h NRD_HIP_DIRECT_MAX_CONTRIBUTION_DEFAULT
+
+
+class HipDirectSignal(C.Structure):  # include/NRDHip.h NrdHipDirectSignal
+    _fields_ = [("radianceHitDist", HipPlaneDesc), ("hitDist", HipPlaneDesc), ("direction", HipPlaneDesc), ("radianceHitDistLayerBytes", C.c_uint64), ("hitDistLayerBytes", C.c_uint64),
+                ("directionLayerBytes", C.c_uint64), ("samplesNum", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HipFrontEndDirect(C.Structure):  # include/NRDHip.h NrdHipFrontEndDirect
+    _fields_ = [("diffuse", HipDirectSignal), ("specular", HipDirectSignal), ("maxHitDistContribution", C.c_float), ("reserved", C.c_uint32)]
+
+
 class HipCoverageSignal(C.Structure):  # include/NRDHip.h NrdHipCoverageSignal
     _fields_ = [("plane", HipPlaneDesc)]
 
@@ -360,6 +372,7 @@ class HipCoverageReport(C.Structure):  # include/NRDHip.h NrdHipCoverageReport
 
 
 assert C.sizeof(HipFrontEndLobes) == 168 and C.sizeof(HipCoverageDesc) == 88 and C.sizeof(HipCoverageReport) == 28
+assert C.sizeof(HipDirectSignal) == 104 and C.sizeof(HipFrontEndDirect) == 216
 
 
 class LightType(enum.IntEnum):  # include/NRDHip.h NRD_HIP_LIGHT_*
@@ -443,7 +456,8 @@ NRD_HIP_SYMBOLS = ["nrdHipCreateExecutor", "nrdHipDestroyExecutor", "nrdHipBindR
                    "nrdHipPackInputsEx", "nrdHipResolveOutputsEx", "nrdHipPackInputsSamples", "nrdHipPackInputsSplit", "nrdHipResolveOutputsSplit",
                    "nrdHipCheckInputs", "nrdHipCheckInputsAsync", "nrdHipGetInputRuleString", "nrdHipPackShadowLights", "nrdHipResolveShadowLights",
                    "nrdHipPackGuides", "nrdHipCreateExecutorLayered", "nrdHipBindResourceLayers", "nrdHipGetPoolPlaneLayer", "nrdHipGetLayersNum",
-                   "nrdHipPackInputsDecimated", "nrdHipResolveOutputsUpsampled", "nrdHipPackInputsLobes", "nrdHipCheckHitDistCoverage"]
+                   "nrdHipPackInputsDecimated", "nrdHipResolveOutputsUpsampled", "nrdHipPackInputsLobes", "nrdHipCheckHitDistCoverage",
+                   "nrdHipPackInputsDirect"]
 
 _libs = {}
 
@@ -528,6 +542,8 @@ def load_library(path=None):
     lib.nrdHipResolveOutputsUpsampled.restype = C.c_uint32
     lib.nrdHipPackInputsLobes.argtypes = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSplit), P(HipFrontEndLobes), C.c_void_p]
     lib.nrdHipPackInputsLobes.restype = C.c_uint32
+    lib.nrdHipPackInputsDirect.argtypes = [P(HipFrontEndDesc), P(HipFrontEndOptions), P(HipFrontEndSamples), P(HipFrontEndSplit), P(HipFrontEndDirect), C.c_uint32, C.c_void_p]
+    lib.nrdHipPackInputsDirect.restype = C.c_uint32
     lib.nrdHipCheckHitDistCoverage.argtypes, lib.nrdHipCheckHitDistCoverage.restype = [P(HipCoverageDesc), C.c_void_p, C.c_void_p], C.c_uint32
     lib.nrdHipPackShadowLights.argtypes, lib.nrdHipPackShadowLights.restype = [P(HipShadowLightsPackDesc), C.c_void_p], C.c_uint32
     lib.nrdHipResolveShadowLights.argtypes, lib.nrdHipResolveShadowLights.restype = [P(HipShadowLightsResolveDesc), C.c_void_p], C.c_uint32

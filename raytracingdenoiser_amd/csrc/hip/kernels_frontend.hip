@@ -10,6 +10,8 @@
 // DECIMATED instantiation of the pack body (the G-buffer planes read at every second texel) and the two upsampling resolve kernels (nearest Z among the low texels around a pixel).
 // nrdHipPackInputsLobes (one traced lobe per sample: the probabilistic diffuse / specular split) launches the kernels of the split call when `lobes` is NULL, else the LOBES
 // instantiation of the pack body: both signals built from one traced plane set, each traced byte loaded once. (Its audit, nrdHipCheckHitDistCoverage: kernels_coverage.hip.)
+// nrdHipPackInputsDirect (combined direct and indirect lighting) launches the kernels of the decimated call when no signal has a direct plane, else a DIRECT instantiation of the
+// pack body in its samples + split form: a signal with a direct plane adds the packed direct term to its packed indirect samples and mixes the diffuse hit distance.
 //
 // Arithmetic: include/NRD.hip.h and nothing else -- its contract, and the reference text it is pinned to, is unfused IEEE fp32 with correctly rounded
 // division and square root. The product builds its device sources with -ffp-contract=on, hence the pragma below, in front of every include: no statement
@@ -65,7 +67,9 @@ enum : uint32_t {
     // nrdHipResolveOutputsSplit: the outputs (kSplitAlbedo / kSplitRf0 are its inputs)
     kSplitDiffOut = 1u << 9, kSplitSpecOut = 1u << 10, kSplitComposed = 1u << 11, kSplitViewVector = 1u << 12, kSplitDiffFactor = 1u << 13, kSplitSpecFactor = 1u << 14,
     // nrdHipPackInputsLobes: the traced planes of NrdHipFrontEndLobes (host side only: the kernel gets their texel sizes in LobeArgs)
-    kSplitLobeIn = 1u << 15, kSplitLobeDir = 1u << 16
+    kSplitLobeIn = 1u << 15, kSplitLobeDir = 1u << 16,
+    // nrdHipPackInputsDirect: the direct planes of NrdHipFrontEndDirect (host side only: the kernel gets their texel sizes in DirectSignal)
+    kSplitDirectDiffIn = 1u << 17, kSplitDirectDiffDir = 1u << 18, kSplitDirectSpecIn = 1u << 19, kSplitDirectSpecDir = 1u << 20
 };
 struct SplitArgs {
     FePlane roughness, diffHitDist, specHitDist;
@@ -78,6 +82,19 @@ struct LobeArgs {
     uint64_t inLayer, hitDistLayer, dirLayer, lobeLayer, probLayer;
     uint32_t num;               // >= 1
     uint32_t inBytes, dirBytes; // 12 or 16
+};
+
+// nrdHipPackInputsDirect: the direct planes of one signal (in absent: the signal has no direct term and is packed by the code of the other kernels) and their layers
+struct DirectSignal {
+    FePlane in, hitDist, dir; // hitDist: `.w` of an RGB32_SFLOAT `in`, diffuse signal with maxContribution > 0 only; dir: the SH modes
+    uint64_t inLayer, hitDistLayer, dirLayer;
+    uint32_t num;               // 1 (one direct texel under every sample) or the signal's own sample count
+    uint32_t inBytes, dirBytes; // 12 or 16
+};
+struct DirectArgs {
+    DirectSignal diff, spec;
+    float maxContribution;  // 0: the diffuse hit distance stays the indirect one, no direct hit distance is consumed
+    uint32_t multiSample;   // the call without `direct` would take the samples kernels (else: the plain ones, whose specular hit distance is not run through the averaging rule)
 };
 
 struct ResolveSplitArgs {
@@ -236,6 +253,65 @@ __device__ __forceinline__ void AddSample(SampleSums& sums, float4 s, float4 d, 
     sums.p1 = make_float4(sums.p1.x + p1.x, sums.p1.y + p1.y, sums.p1.z + p1.z, sums.p1.w + p1.w);
 }
 
+// ---- combined direct and indirect lighting (nrdHipPackInputsDirect; the per-pixel rules are spelled out in NRDHip.h) ---------------------------------------------------
+// the packers' own first line
+__device__ __forceinline__ float3 SanitizedRadiance(float3 r) { return _NRD_IsInvalid(r) ? make_float3(0.0f, 0.0f, 0.0f) : nrd_hip_detail::clamp(r, 0.0f, NRD_FP16_MAX); }
+__device__ __forceinline__ float ClampToHalfRange(float v) { return fminf(fmaxf(v, -NRD_FP16_MAX), NRD_FP16_MAX); }
+// C = clamp( P_i + P_d ): the store codec never rounds a sum of two clamped terms to infinity. keepW: .w carries the hit distance and is not a sum
+__device__ __forceinline__ float4 AddClamped(float4 a, float4 b, bool keepW) {
+    return make_float4(ClampToHalfRange(a.x + b.x), ClampToHalfRange(a.y + b.y), ClampToHalfRange(a.z + b.z), keepW ? a.w : ClampToHalfRange(a.w + b.w));
+}
+
+// what one direct texel contributes: P_d, and ( h_d, L_d ) for the diffuse hit distance
+struct DirectTerm {
+    float4 p0, p1;
+    float hitDist, lum;
+};
+// t: the direct texel ( .w consumed only with needHitDist: it may hold anything otherwise ), d: its direction
+template <bool SPEC, uint32_t MODE>
+__device__ __forceinline__ DirectTerm PackDirectTerm(float4 t, float4 d, bool needHitDist, float trim, float viewZ, float r, float4 hitDistParams, bool demodulate, float3 factor) {
+    float3 radiance = Xyz(t);
+    float hitDist = needHitDist ? t.w : 0.0f;
+    if (trim > 0.0f)
+        hitDist = NRD_FrontEnd_TrimHitDistance(hitDist, trim);
+    if (demodulate)
+        radiance = make_float3(radiance.x / factor.x, radiance.y / factor.y, radiance.z / factor.z);
+    DirectTerm term;
+    term.p1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    term.p0 = PackSample<SPEC, MODE>(radiance, 0.0f, Xyz(d), viewZ, r, hitDistParams, term.p1);
+    term.hitDist = hitDist;
+    term.lum = _NRD_Luminance(SanitizedRadiance(radiance));
+    return term;
+}
+
+// AddSample of a signal with a direct term. perSample: the term is this sample's own and is added here (else it is added once, to the mean: ReduceSignal); mix: the diffuse
+// hit distance takes the direct one in; averaging: the specular hit distance goes through NRD_FrontEnd_SpecHitDistAveraging_* (else there is one sample and it is kept as it is)
+template <bool SPEC, uint32_t MODE>
+__device__ __forceinline__ void AddSampleDirect(SampleSums& sums, float4 s, float4 d, const DirectTerm& term, bool perSample, bool mix, bool averaging, float maxContribution, float trim, float viewZ,
+    float r, float4 hitDistParams, bool demodulate, float3 factor) {
+    float3 radiance = Xyz(s);
+    float hitDist = s.w;
+    if (trim > 0.0f)
+        hitDist = NRD_FrontEnd_TrimHitDistance(hitDist, trim);
+    if (demodulate)
+        radiance = make_float3(radiance.x / factor.x, radiance.y / factor.y, radiance.z / factor.z);
+    if (SPEC) {
+        if (averaging)
+            NRD_FrontEnd_SpecHitDistAveraging_Add(sums.specHitDist, hitDist);
+        else
+            sums.specHitDist = hitDist;
+    } else if (mix)
+        hitDist = NRD_HIP_MixDiffuseHitDist(hitDist, term.hitDist, _NRD_Luminance(SanitizedRadiance(radiance)), term.lum, maxContribution);
+    float4 p1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 p0 = PackSample<SPEC, MODE>(radiance, hitDist, Xyz(d), viewZ, r, hitDistParams, p1);
+    if (perSample) {
+        p0 = AddClamped(p0, term.p0, true);
+        p1 = AddClamped(p1, term.p1, false);
+    }
+    sums.p0 = make_float4(sums.p0.x + p0.x, sums.p0.y + p0.y, sums.p0.z + p0.z, sums.p0.w + p0.w);
+    sums.p1 = make_float4(sums.p1.x + p1.x, sums.p1.y + p1.y, sums.p1.z + p1.z, sums.p1.w + p1.w);
+}
+
 // a sample texel, read whole: one global_load_dwordx4 per lane in every mode (a mode that consumes .w or .xyz alone would else get a narrower load of the same sectors,
 // and a 16-byte lane stride with it: the wave still touches the whole 1 KiB segment)
 __device__ __forceinline__ float4 LoadSampleTexel(const Plane& layer, int x, int y) {
@@ -256,9 +332,13 @@ struct SplitSignal {
     bool wFromCompanion;
 };
 
-template <bool SPEC, uint32_t MODE, bool SPLIT>
+// DIRECT (nrdHipPackInputsDirect, a signal that has a direct plane): each sample's packed texel takes in the packed direct term of layer s of `ds` -- loaded with the indirect
+// loads of its batch, a 16-byte texel whole -- or, when `ds` holds one layer, the mean takes in the one term, loaded once in front of the loop.
+template <bool SPEC, uint32_t MODE, bool SPLIT, bool DIRECT = false>
 __device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, uint64_t inLayer, uint64_t dirLayer, const SplitSignal& sp, uint32_t num,
-    float trim, int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor) {
+    float trim, int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor, const DirectSignal& ds = DirectSignal{},
+    float maxContribution = 0.0f, bool averaging = true) {
+    static_assert(!DIRECT || SPLIT, "the direct call takes the split form of the body");
     constexpr bool kRadiance = MODE != NRD_HIP_SIGNAL_REBLUR_OCCLUSION && MODE != NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION; // (else .xyz is not consumed: not loaded by the split form)
     constexpr bool kDirection = MODE == NRD_HIP_SIGNAL_REBLUR_SH || MODE == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION || MODE == NRD_HIP_SIGNAL_RELAX_SH;
     constexpr bool kSh = MODE == NRD_HIP_SIGNAL_REBLUR_SH || MODE == NRD_HIP_SIGNAL_RELAX_SH;
@@ -286,31 +366,86 @@ __device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& d
         const float3 c = LoadXyz32F(dirLayerPlane, x, y, sp.dirBytes);
         return make_float4(c.x, c.y, c.z, 0.0f);
     };
+    // DIRECT: where this lane's direct texel, its .w (an RGB32_SFLOAT plane's companion) and its direction live in a layer
+    const bool mix = DIRECT && !SPEC && maxContribution > 0.0f, perSample = DIRECT && ds.num > 1u;
+    Plane directLayer = AsPlane(DIRECT ? ds.in : in, w, h), directDirLayer = AsPlane(DIRECT && kDirection ? ds.dir : in, w, h);
+    const uint8_t* directWPtr = DIRECT && mix && ds.hitDist.ptr ? ds.hitDist.ptr + TexelOffset(AsPlane(ds.hitDist, w, h), x, y, 4u, true) : nullptr;
+    auto loadDirect = [&]() {
+        float4 t;
+        if (ds.inBytes == 16u)
+            t = LoadSampleTexel(directLayer, x, y);
+        else {
+            const float3 c = LoadXyz32F(directLayer, x, y, 12u);
+            t = make_float4(c.x, c.y, c.z, 0.0f);
+            if (directWPtr) {
+                t.w = *(const float*)directWPtr;
+                directWPtr += ds.hitDistLayer;
+            }
+        }
+        directLayer.ptr += ds.inLayer;
+        return t;
+    };
+    auto loadDirectDirection = [&]() {
+        const float3 c = LoadXyz32F(directDirLayer, x, y, ds.dirBytes);
+        directDirLayer.ptr += ds.dirLayer;
+        return make_float4(c.x, c.y, c.z, 0.0f);
+    };
+    float4 directTexel = zero, directDirection = zero; // one direct layer: loaded here, packed behind the first indirect loads
+    if (DIRECT && !perSample) {
+        directTexel = loadDirect();
+        if (kDirection)
+            directDirection = loadDirectDirection();
+    }
+    DirectTerm term = {zero, zero, 0.0f, 0.0f};
     uint32_t s = 0;
     for (; s + kBatch <= num; s += kBatch) {
-        float4 t[kBatch], d[kBatch];
+        float4 t[kBatch], d[kBatch], td[kBatch], dd[kBatch];
 #pragma unroll
         for (uint32_t k = 0; k < kBatch; k++) {
             t[k] = loadSample();
             d[k] = kDirection ? loadDirection() : zero;
             layer.ptr += inLayer;
             dirLayerPlane.ptr += dirLayer;
+            if (DIRECT && perSample) {
+                td[k] = loadDirect();
+                dd[k] = kDirection ? loadDirectDirection() : zero;
+            }
         }
+        if (DIRECT && !perSample && s == 0u)
+            term = PackDirectTerm<SPEC, MODE>(directTexel, directDirection, mix, trim, viewZ, r, hitDistParams, demodulate, factor);
 #pragma unroll
-        for (uint32_t k = 0; k < kBatch; k++)
-            AddSample<SPEC, MODE>(sums, t[k], d[k], trim, viewZ, r, hitDistParams, demodulate, factor);
+        for (uint32_t k = 0; k < kBatch; k++) {
+            if (DIRECT) {
+                if (perSample)
+                    term = PackDirectTerm<SPEC, MODE>(td[k], dd[k], mix, trim, viewZ, r, hitDistParams, demodulate, factor);
+                AddSampleDirect<SPEC, MODE>(sums, t[k], d[k], term, perSample, mix, averaging, maxContribution, trim, viewZ, r, hitDistParams, demodulate, factor);
+            } else
+                AddSample<SPEC, MODE>(sums, t[k], d[k], trim, viewZ, r, hitDistParams, demodulate, factor);
+        }
     }
     for (; s < num; s++) {
         const float4 t = loadSample();
         const float4 d = kDirection ? loadDirection() : zero;
         layer.ptr += inLayer;
         dirLayerPlane.ptr += dirLayer;
-        AddSample<SPEC, MODE>(sums, t, d, trim, viewZ, r, hitDistParams, demodulate, factor);
+        if (DIRECT) {
+            if (perSample) {
+                const float4 td = loadDirect();
+                const float4 dd = kDirection ? loadDirectDirection() : zero;
+                term = PackDirectTerm<SPEC, MODE>(td, dd, mix, trim, viewZ, r, hitDistParams, demodulate, factor);
+            } else if (s == 0u)
+                term = PackDirectTerm<SPEC, MODE>(directTexel, directDirection, mix, trim, viewZ, r, hitDistParams, demodulate, factor);
+            AddSampleDirect<SPEC, MODE>(sums, t, d, term, perSample, mix, averaging, maxContribution, trim, viewZ, r, hitDistParams, demodulate, factor);
+        } else
+            AddSample<SPEC, MODE>(sums, t, d, trim, viewZ, r, hitDistParams, demodulate, factor);
     }
     const float n = float(num);
     float4 p0 = make_float4(sums.p0.x / n, sums.p0.y / n, sums.p0.z / n, sums.p0.w / n);
+    if (DIRECT && !perSample) // one direct layer: clamp( mean_s( P_i,s ) + P_d )
+        p0 = AddClamped(p0, term.p0, true);
     if (SPEC) {
-        NRD_FrontEnd_SpecHitDistAveraging_End(sums.specHitDist);
+        if (!DIRECT || averaging)
+            NRD_FrontEnd_SpecHitDistAveraging_End(sums.specHitDist);
         p0.w = PackedHitDist<MODE>(sums.specHitDist, viewZ, r, hitDistParams);
     }
     const Plane o0 = AsPlane(out0, w, h);
@@ -320,7 +455,10 @@ __device__ __forceinline__ void ReduceSignal(const FePlane& in, const FePlane& d
         StoreRGBA16Snorm(o0, xo, y, p0);
     else
         StoreRGBA16F(o0, xo, y, p0);
-    if (kSh)
+    if (kSh && DIRECT) {
+        const float4 p1 = make_float4(sums.p1.x / n, sums.p1.y / n, sums.p1.z / n, sums.p1.w / n);
+        StoreRGBA16F(AsPlane(out1, w, h), xo, y, perSample ? p1 : AddClamped(p1, term.p1, false));
+    } else if (kSh)
         StoreRGBA16F(AsPlane(out1, w, h), xo, y, make_float4(sums.p1.x / n, sums.p1.y / n, sums.p1.z / n, sums.p1.w / n));
 }
 
@@ -336,6 +474,26 @@ __device__ __forceinline__ void PackSignalSamples(uint32_t mode, const FePlane& 
         NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_SH)
         NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_OCCLUSION)
         NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_RELAX_RADIANCE)
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_RELAX_SH)
+        default:
+            break;
+    }
+}
+#undef NRD_REDUCE_SIGNAL
+
+// a signal with a direct plane (nrdHipPackInputsDirect): the radiance and SH modes alone -- the host refuses a direct plane for the others
+#define NRD_REDUCE_SIGNAL(MODE) \
+    case MODE: \
+        ReduceSignal<SPEC, MODE, true, true>(in, dirPlane, out0, out1, inLayer, dirLayer, sp, num, trim, x, xo, y, w, h, viewZ, roughness, hitDistParams, demodulate, factor, ds, maxContribution, averaging); \
+        break;
+template <bool SPEC>
+__device__ __forceinline__ void PackSignalDirect(uint32_t mode, const FePlane& in, const FePlane& dirPlane, const FePlane& out0, const FePlane& out1, uint64_t inLayer, uint64_t dirLayer,
+    const SplitSignal& sp, uint32_t num, float trim, int x, int xo, int y, int w, int h, float viewZ, float roughness, float4 hitDistParams, bool demodulate, float3 factor, const DirectSignal& ds,
+    float maxContribution, bool averaging) {
+    switch (mode) { // wave-uniform: a kernel argument
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_RADIANCE)
+        NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_REBLUR_SH)
         NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_RELAX_RADIANCE)
         NRD_REDUCE_SIGNAL(NRD_HIP_SIGNAL_RELAX_SH)
         default:
@@ -497,8 +655,12 @@ __device__ __forceinline__ float ClampToHalf(float v) { return isnan(v) ? v : fm
 // (normalRoughness and its roughness companion, viewZ, materialID, motion, albedo, rf0) are full-size planes of which pixel ( x, y ) reads texel ( gx, gy ) = ( 2x, 2y ) -- inside
 // them because w = ( W + 1 ) >> 1, h = ( H + 1 ) >> 1 (held by the host). Only that load coordinate differs: the view vector of the demodulation is that of ( x, y ) in w x h.
 // LOBES (nrdHipPackInputsLobes): both signals come from one traced plane set (`lo`, which the other kernels never look at) through PackLobes; everything else is the plain body.
-template <bool CHECKERBOARD, bool SAMPLES, bool SPLIT, bool DECIMATED = false, bool LOBES = false>
-__device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& sa, const SplitArgs& sp, uint32_t diffCell, uint32_t frameIndex, const LobeArgs& lo = LobeArgs{}) {
+// DIRECT (nrdHipPackInputsDirect, the samples + split form of the body): a signal that has a direct plane in `di` (which the other kernels never look at) goes through
+// PackSignalDirect; one that has none takes the very code it takes without `direct` -- that of the samples kernels, or of the plain ones where di.multiSample is 0 -- and no load more.
+template <bool CHECKERBOARD, bool SAMPLES, bool SPLIT, bool DECIMATED = false, bool LOBES = false, bool DIRECT = false>
+__device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& sa, const SplitArgs& sp, uint32_t diffCell, uint32_t frameIndex, const LobeArgs& lo = LobeArgs{},
+    const DirectArgs& di = DirectArgs{}) {
+    static_assert(!DIRECT || (SAMPLES && SPLIT && !LOBES), "the direct call takes the samples + split form of the body");
     static_assert(!(DECIMATED && CHECKERBOARD), "checkerboarding and decimation are not combined");
     static_assert(!LOBES || (!CHECKERBOARD && !SAMPLES && !DECIMATED), "the lobes call has sample layers of its own and is neither checkerboarded nor decimated");
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
@@ -542,12 +704,26 @@ __device__ __forceinline__ void PackPixel(const PackArgs& a, const SampleArgs& s
     else if (SAMPLES) {
         const SplitSignal diffSplit = {sp.diffHitDist, sp.diffHitDistLayer, SplitTexelBytes(sp.rgb, kSplitDiffIn), SplitTexelBytes(sp.rgb, kSplitDiffDir), (sp.rgb & kSplitDiffIn) != 0u};
         const SplitSignal specSplit = {sp.specHitDist, sp.specHitDistLayer, SplitTexelBytes(sp.rgb, kSplitSpecIn), SplitTexelBytes(sp.rgb, kSplitSpecDir), (sp.rgb & kSplitSpecIn) != 0u};
-        if (a.diffMode && diffHere)
-            PackSignalSamples<false, SPLIT>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sa.diffInLayer, sa.diffDirLayer, diffSplit, sa.diffNum, sa.trim, x, xo, y, w, h, viewZ, roughness,
-                a.hitDistParams, a.demodulate != 0u, diffFactor);
-        if (a.specMode && (!CHECKERBOARD || !diffHere))
-            PackSignalSamples<true, SPLIT>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, sa.specInLayer, sa.specDirLayer, specSplit, sa.specNum, sa.trim, x, xo, y, w, h, viewZ, roughness,
-                a.hitDistParams, a.demodulate != 0u, specFactor);
+        if (a.diffMode && diffHere) {
+            if (DIRECT && di.diff.in.ptr)
+                PackSignalDirect<false>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sa.diffInLayer, sa.diffDirLayer, diffSplit, sa.diffNum, sa.trim, x, xo, y, w, h, viewZ, roughness,
+                    a.hitDistParams, a.demodulate != 0u, diffFactor, di.diff, di.maxContribution, di.multiSample != 0u);
+            else if (DIRECT && !di.multiSample)
+                PackSignal<false, SPLIT>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sp.diffHitDist, sp.rgb, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, diffFactor);
+            else
+                PackSignalSamples<false, SPLIT>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sa.diffInLayer, sa.diffDirLayer, diffSplit, sa.diffNum, sa.trim, x, xo, y, w, h, viewZ, roughness,
+                    a.hitDistParams, a.demodulate != 0u, diffFactor);
+        }
+        if (a.specMode && (!CHECKERBOARD || !diffHere)) {
+            if (DIRECT && di.spec.in.ptr)
+                PackSignalDirect<true>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, sa.specInLayer, sa.specDirLayer, specSplit, sa.specNum, sa.trim, x, xo, y, w, h, viewZ, roughness,
+                    a.hitDistParams, a.demodulate != 0u, specFactor, di.spec, 0.0f, di.multiSample != 0u);
+            else if (DIRECT && !di.multiSample)
+                PackSignal<true, SPLIT>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, sp.specHitDist, sp.rgb, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, specFactor);
+            else
+                PackSignalSamples<true, SPLIT>(a.specMode, a.specIn, a.specDir, a.specOut0, a.specOut1, sa.specInLayer, sa.specDirLayer, specSplit, sa.specNum, sa.trim, x, xo, y, w, h, viewZ, roughness,
+                    a.hitDistParams, a.demodulate != 0u, specFactor);
+        }
     } else {
         if (a.diffMode && diffHere)
             PackSignal<false, SPLIT>(a.diffMode, a.diffIn, a.diffDir, a.diffOut0, a.diffOut1, sp.diffHitDist, sp.rgb, x, xo, y, w, h, viewZ, roughness, a.hitDistParams, a.demodulate != 0u, diffFactor);
@@ -600,6 +776,20 @@ __global__ void __launch_bounds__(256) PackDecimatedSamplesSplitKernel(const Pac
 
 // nrdHipPackInputsLobes: the split form of the body (an RGB32_SFLOAT G-buffer plane is a uniform branch on a bit of sp.rgb), the two signals from the traced planes of `lo`
 __global__ void __launch_bounds__(256) PackLobesKernel(const PackArgs a, const SplitArgs sp, const LobeArgs lo) { PackPixel<false, false, true, false, true>(a, SampleArgs{}, sp, 0u, 0u, lo); }
+
+// nrdHipPackInputsDirect with a direct plane: the samples + split form of the body (one sample layer and four-channel planes are uniform branches of it), plain, checkerboarded
+// and decimated
+__global__ void __launch_bounds__(256) PackDirectKernel(const PackArgs a, const SampleArgs sa, const SplitArgs sp, const DirectArgs di) {
+    PackPixel<false, true, true, false, false, true>(a, sa, sp, 0u, 0u, LobeArgs{}, di);
+}
+
+__global__ void __launch_bounds__(256) PackDirectCheckerboardKernel(const PackArgs a, const SampleArgs sa, const SplitArgs sp, const DirectArgs di, const uint32_t diffCell, const uint32_t frameIndex) {
+    PackPixel<true, true, true, false, false, true>(a, sa, sp, diffCell, frameIndex, LobeArgs{}, di);
+}
+
+__global__ void __launch_bounds__(256) PackDirectDecimatedKernel(const PackArgs a, const SampleArgs sa, const SplitArgs sp, const DirectArgs di) {
+    PackPixel<false, true, true, true, false, true>(a, sa, sp, 0u, 0u, LobeArgs{}, di);
+}
 
 __device__ __forceinline__ float4 LoadSignalTexel(const FePlane& p, bool wide, int x, int y, int w, int h) {
     return wide ? LoadRGBA32F(AsPlane(p, w, h), x, y) : LoadRGBA16F(AsPlane(p, w, h), x, y);
@@ -1060,11 +1250,47 @@ uint32_t CheckSamples(const NrdHipSignalSamples& s, uint32_t mode, const char* n
     return (uint32_t)nrd::Result::SUCCESS;
 }
 
+// the rules of one signal of NrdHipFrontEndDirect; num: the signal's own sample count. Returns whether the signal has a direct term
+bool DirectSignalPlanes(Checker& c, const NrdHipDirectSignal& s, const char* name, uint32_t mode, uint32_t num, bool spec, float maxContribution, uint32_t inBit, uint32_t dirBit, DirectSignal& out) {
+    const std::string n = std::string("direct: ") + name;
+    if (s.reserved)
+        c.Error(nrd::Result::INVALID_ARGUMENT, (n + ".reserved").c_str(), "must be 0");
+    if (!s.radianceHitDist.data) { // no direct term: nothing else of the signal may be given
+        Refuse(c, s.hitDist, (n + ".hitDist").c_str(), "given without radianceHitDist");
+        Refuse(c, s.direction, (n + ".direction").c_str(), "given without radianceHitDist");
+        return false;
+    }
+    if (mode == NRD_HIP_SIGNAL_NONE || mode == NRD_HIP_SIGNAL_REBLUR_OCCLUSION || mode == NRD_HIP_SIGNAL_REBLUR_DIRECTIONAL_OCCLUSION)
+        c.Error(nrd::Result::INVALID_ARGUMENT, (n + ".radianceHitDist").c_str(), "given for a signal whose mode is NONE or an occlusion mode: there is no radiance to weigh the direct term by");
+    out.num = s.samplesNum ? s.samplesNum : 1u;
+    if (out.num != 1u && out.num != num)
+        c.Error(nrd::Result::INVALID_ARGUMENT, (n + ".samplesNum").c_str(), "neither 1 nor the signal's own sample count");
+    out.in = c.CheckColour(s.radianceHitDist, (n + ".radianceHitDist").c_str(), nullptr, inBit);
+    const bool rgb = (c.rgb & inBit) != 0u;
+    if (spec)
+        Refuse(c, s.hitDist, (n + ".hitDist").c_str(), "given: the specular hit distance is the indirect one alone, a direct distance is never read");
+    else if (!(maxContribution > 0.0f))
+        Refuse(c, s.hitDist, (n + ".hitDist").c_str(), "given with maxHitDistContribution == 0: no direct hit distance is read");
+    else
+        out.hitDist = c.CheckCompanion(s.hitDist, (n + ".hitDist").c_str(), rgb, "radianceHitDist is RGB32_SFLOAT: the direct hit distance comes from this plane", (n + ".radianceHitDist").c_str());
+    if (IsSh(mode))
+        out.dir = c.CheckColour(s.direction, (n + ".direction").c_str(), "the signal's mode needs a direction plane", dirBit);
+    else
+        Refuse(c, s.direction, (n + ".direction").c_str(), "given for a mode that reads no direction");
+    out.inBytes = rgb ? 12u : 16u;
+    out.dirBytes = (c.rgb & dirBit) ? 12u : 16u;
+    CheckLayerBytes(c, out.inLayer = s.radianceHitDistLayerBytes, out.in, out.num, (n + ".radianceHitDistLayerBytes").c_str(), rgb);
+    CheckLayerBytes(c, out.hitDistLayer = s.hitDistLayerBytes, out.hitDist, out.num, (n + ".hitDistLayerBytes").c_str(), true);
+    CheckLayerBytes(c, out.dirLayer = s.directionLayerBytes, out.dir, out.num, (n + ".directionLayerBytes").c_str(), (c.rgb & dirBit) != 0u);
+    return true;
+}
+
 // split != nullptr or splitEntry: nrdHipPackInputsSplit -- RGB32_SFLOAT planes and their companions are accepted
 // decimated: nrdHipPackInputsDecimated with guideShift = 1 -- the G-buffer planes form the full-size class of the checker, everything else the low-size one
 // lobes != nullptr: nrdHipPackInputsLobes -- both signals come from the traced planes of `lobes` (samples == nullptr: the sample layers are those of `lobes`)
+// direct != nullptr: nrdHipPackInputsDirect -- the signals' own planes are the indirect ones, `direct` holds the direct ones
 uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples, const NrdHipFrontEndSplit* split, bool splitEntry, void* hipStream,
-    bool decimated = false, const NrdHipFrontEndLobes* lobes = nullptr) {
+    bool decimated = false, const NrdHipFrontEndLobes* lobes = nullptr, const NrdHipFrontEndDirect* direct = nullptr) {
     using F = nrd::Format;
     static const NrdHipFrontEndSplit noSplit = {};
     const NrdHipFrontEndSplit& sd = split ? *split : noSplit;
@@ -1085,6 +1311,10 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsLobes: lobes: samplesNum: more than 64 sample layers");
     if (lobes && lobes->reserved)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsLobes: lobes: reserved: must be 0");
+    if (direct && direct->reserved)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsDirect: direct: reserved: must be 0");
+    if (direct && !(direct->maxHitDistContribution >= 0.0f && direct->maxHitDistContribution <= 1.0f)) // (a NaN fails every comparison)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsDirect: direct: maxHitDistContribution: NaN or outside [0, 1]");
     SampleArgs sa = {};
     sa.diffNum = sa.specNum = 1u;
     if (samples) {
@@ -1099,7 +1329,7 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
         sa.trim = samples->hitDistTrimThreshold;
     }
     const bool multiSample = sa.diffNum > 1u || sa.specNum > 1u || sa.trim > 0.0f; // else: the kernels of nrdHipPackInputsEx, the same bytes, no extra loads
-    const char* entry = lobes ? "nrdHipPackInputsLobes" : decimated ? "nrdHipPackInputsDecimated" : splitEntry ? "nrdHipPackInputsSplit" : "nrdHipPackInputs";
+    const char* entry = direct ? "nrdHipPackInputsDirect" : lobes ? "nrdHipPackInputsLobes" : decimated ? "nrdHipPackInputsDecimated" : splitEntry ? "nrdHipPackInputsSplit" : "nrdHipPackInputs";
     Checker c{entry};
     c.split = splitEntry;
     PackArgs a = {};
@@ -1154,6 +1384,14 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
         CheckLayerBytes(c, lo.lobeLayer = lobes->lobeLayerBytes, lo.lobe, lo.num, "lobes: lobeLayerBytes", true);
         CheckLayerBytes(c, lo.probLayer = lobes->probabilityLayerBytes, lo.prob, lo.num, "lobes: probabilityLayerBytes", true);
     }
+    DirectArgs di = {};
+    bool hasDirect = false;
+    if (direct) {
+        di.maxContribution = direct->maxHitDistContribution;
+        di.multiSample = multiSample ? 1u : 0u;
+        hasDirect |= DirectSignalPlanes(c, direct->diffuse, "diffuse", d->diffuse.mode, sa.diffNum, false, di.maxContribution, kSplitDirectDiffIn, kSplitDirectDiffDir, di.diff);
+        hasDirect |= DirectSignalPlanes(c, direct->specular, "specular", d->specular.mode, sa.specNum, true, di.maxContribution, kSplitDirectSpecIn, kSplitDirectSpecDir, di.spec);
+    }
     if (multiSample && samples && splitEntry) { // the same rules, in dwords where the stack holds RGB32_SFLOAT texels, and for the companions
         CheckLayerBytes(c, sa.diffInLayer = samples->diffuse.radianceHitDistLayerBytes, a.diffIn, sa.diffNum, "samples: diffuse.radianceHitDistLayerBytes", (c.rgb & kSplitDiffIn) != 0u);
         CheckLayerBytes(c, sa.diffDirLayer = samples->diffuse.directionLayerBytes, a.diffDir, sa.diffNum, "samples: diffuse.directionLayerBytes", (c.rgb & kSplitDiffDir) != 0u);
@@ -1192,6 +1430,15 @@ uint32_t PackInputs(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* op
     if (lobes) {
         sp.rgb = c.rgb;
         hipLaunchKernelGGL(PackLobesKernel, grid, block, 0, (hipStream_t)hipStream, a, sp, lo);
+    } else if (hasDirect) { // (without a direct plane: the kernels of the call without `direct` below, the same bytes)
+        sp.rgb = c.rgb;
+        if (decimated)
+            hipLaunchKernelGGL(PackDirectDecimatedKernel, grid, block, 0, (hipStream_t)hipStream, a, sa, sp, di);
+        else if (checkerboardMode)
+            hipLaunchKernelGGL(PackDirectCheckerboardKernel, grid, block, 0, (hipStream_t)hipStream, a, sa, sp, di,
+                checkerboardMode == (uint32_t)nrd::CheckerboardMode::BLACK ? 0u : 1u, options ? options->frameIndex & 1u : 0u);
+        else
+            hipLaunchKernelGGL(PackDirectKernel, grid, block, 0, (hipStream_t)hipStream, a, sa, sp, di);
     } else if (decimated) { // the decimated twins: plain, samples and their split forms (checkerboarding was refused above)
         sp.rgb = c.rgb;
         if (c.rgb && multiSample)
@@ -1254,6 +1501,13 @@ extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsDecim
     if (guideShift > 1u)
         return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsDecimated: guideShift: 0 (the call is nrdHipPackInputsSplit) or 1 (G-buffer planes of twice the size, read at every second texel)");
     return PackInputs(d, options, samples, split, true, hipStream, guideShift == 1u);
+}
+
+extern "C" __attribute__((visibility("default"))) uint32_t nrdHipPackInputsDirect(const NrdHipFrontEndDesc* d, const NrdHipFrontEndOptions* options, const NrdHipFrontEndSamples* samples,
+    const NrdHipFrontEndSplit* split, const NrdHipFrontEndDirect* direct, uint32_t guideShift, void* hipStream) {
+    if (guideShift > 1u)
+        return Fail(nrd::Result::INVALID_ARGUMENT, "nrdHipPackInputsDirect: guideShift: 0 or 1 (G-buffer planes of twice the size, read at every second texel)");
+    return PackInputs(d, options, samples, split, true, hipStream, guideShift == 1u, nullptr, direct);
 }
 
 namespace {

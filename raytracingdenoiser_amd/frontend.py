@@ -201,7 +201,7 @@ def _reuse(out, key, like, shape, dtype):
 
 
 # ---- front end -------------------------------------------------------------------------------------------------------------------------------------------
-def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0, lobes=None, **kw):
+def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.CheckerboardMode.OFF, frame_index=0, lobes=None, direct=None, **kw):
     """see describe_pack; launches on `stream` (a torch.cuda.Stream or a raw handle; default: the current stream) and returns the packed planes. Three-channel arrays, (xyz, w)
     pairs and [N, H, W, 3] stacks are read where they lie through nrdHipPackInputsSplit -- no copy, no allocation (in_place=False: widened into [.., 4] copies first, as before;
     that path allocates, so a raw stream handle suits it with four-channel inputs only); four-channel arguments take the calls they always took.
@@ -213,7 +213,9 @@ def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.Checkerboa
     read at every second texel of every second row; the signals, distance_to_occluder and translucency are traced at the low size [(H + 1) >> 1, (W + 1) >> 1], which is the size
     of every packed plane returned; common_settings (demodulation) is that of the low-size frame.
     lobes= (one traced lobe per pixel: the probabilistic diffuse / specular split, NRDHip.h nrdHipPackInputsLobes): a dict of pack_lobes' arguments, or what pack_lobes returned.
-    diffuse and specular are then dict(mode=SignalMode) alone -- both are built from the one traced plane set in the same launch."""
+    diffuse and specular are then dict(mode=SignalMode) alone -- both are built from the one traced plane set in the same launch.
+    direct= (combined denoising of direct and indirect lighting, NRDHip.h nrdHipPackInputsDirect): a dict of pack_direct's arguments, or what pack_direct returned. The planes of
+    diffuse / specular are then the INDIRECT ones; the direct radiance is added to each signal in the same launch and the diffuse hit distance is mixed by the reference's rule."""
     given = inspect.signature(describe_pack).bind(normal_roughness, viewz, *args, **kw).arguments
     in_place = given.get("in_place")
     in_place = PACK_IN_PLACE if in_place is None else bool(in_place)
@@ -223,7 +225,16 @@ def pack_inputs(normal_roughness, viewz, *args, checkerboard_mode=api.Checkerboa
         lib = kw.get("lib") or api.load_library()
         layered = any(_layers(sig[k])[0] for sig in (given.get("diffuse"), given.get("specular")) if sig for k in ("radiance_hitdist", "direction") if sig.get(k) is not None)
         split = pack_split(normal_roughness, given.get("diffuse"), given.get("specular")) if in_place else None
-        if lobes is not None:
+        if direct is not None:  # one entry point for plain, sampled, split and decimated planes, like nrdHipPackInputsDecimated
+            assert lobes is None, "direct: combining with lobes is out of scope"
+            di, keep_direct = pack_direct(**direct) if isinstance(direct, dict) else direct
+            in_place_here = split is not None and _anything_split(d, split)
+            samples = pack_samples(given.get("diffuse"), given.get("specular"), given.get("hit_dist_trim", 0.0), in_place=in_place_here)
+            options = pack_options(checkerboard_mode, frame_index)
+            split = split if in_place_here else api.HipFrontEndSplit()
+            _check(lib, lib.nrdHipPackInputsDirect(C.byref(d), C.byref(options), C.byref(samples), C.byref(split), C.byref(di), int(given.get("guide_shift", 0)),
+                                                   _stream(viewz, kw.get("stream"))), "nrdHipPackInputsDirect")
+        elif lobes is not None:
             assert int(given.get("guide_shift", 0)) == 0 and given.get("hit_dist_trim", 0.0) == 0.0, "lobes: neither decimation nor a trim threshold"
             lo, keep_lobes = pack_lobes(**lobes) if isinstance(lobes, dict) else lobes
             options = pack_options(checkerboard_mode, frame_index)
@@ -309,6 +320,38 @@ def pack_lobes(radiance_hit_dist, lobe, probability=None, direction=None):
     return lo, keep
 
 
+def pack_direct(diffuse=None, specular=None, max_hit_dist_contribution=api.DIRECT_MAX_CONTRIBUTION_DEFAULT):
+    """(api.HipFrontEndDirect, arrays it points into) for nrdHipPackInputsDirect, next to a descriptor of describe_pack whose diffuse / specular planes are the INDIRECT ones.
+    diffuse / specular: the signal's direct plane, or dict(radiance_hitdist=, direction=) in the SH modes, or None (no direct term). Everything is read where it lies, one layer
+    [H, W, ..] under every sample or an [N, H, W, ..] stack with the signal's own N (the layer stride is stride(0)): radiance_hitdist float32 [.., 4] -- direct radiance and the
+    distance to the sampled light -- or a (radiance [.., 3], hit_dist [..]) pair, or radiance [.., 3] alone where no direct distance is read (the specular signal always;
+    the diffuse one with max_hit_dist_contribution = 0); direction float32 [.., 3] or [.., 4]: the direction to the light.
+    max_hit_dist_contribution in [0, 1]: the cap of the weight with which the diffuse hit distance moves from the indirect to the direct one (0.5; the reference's README:
+    "0.65 works good as well"); 0 keeps the indirect one."""
+    di, keep = api.HipFrontEndDirect(), [diffuse, specular]
+    di.maxHitDistContribution = float(max_hit_dist_contribution)
+
+    def stack(t, plane_ndim):
+        return (t[0], t.shape[0], _stride0_bytes(t)) if t.ndim > plane_ndim else (t, 1, 0)
+
+    for which, sig, dst in (("diffuse", diffuse, di.diffuse), ("specular", specular, di.specular)):
+        if sig is None:
+            continue
+        sig = sig if isinstance(sig, dict) else dict(radiance_hitdist=sig)
+        xyz, w = sig["radiance_hitdist"] if _is_pair(sig["radiance_hitdist"]) else (sig["radiance_hitdist"], None)
+        layer, dst.samplesNum, dst.radianceHitDistLayerBytes = stack(xyz, 3)
+        dst.radianceHitDist = _xyz_plane(layer, "direct %s radiance_hitdist" % which)
+        if w is not None:
+            layer, n, dst.hitDistLayerBytes = stack(w, 2)
+            assert n == dst.samplesNum, "direct %s: hit_dist and radiance must have the same number of layers" % which
+            dst.hitDist = _fp32_plane(layer, 1, "direct %s hit_dist" % which)
+        if sig.get("direction") is not None:
+            layer, n, dst.directionLayerBytes = stack(sig["direction"], 3)
+            assert n == dst.samplesNum, "direct %s: direction and radiance must have the same number of layers" % which
+            dst.direction = _xyz_plane(layer, "direct %s direction" % which)
+    return di, keep
+
+
 # Whether pack_inputs takes three-channel input where it lies by default (in_place=None). Decided by tools/frontend_bench.py --split (DESIGN.md section 3.4, the `split` object of
 # profiles/frontend_bench.json): at 2560 x 1440 the in-place call takes 0.068 ms against 0.119 ms of widening + 0.066 ms of the four-channel call.
 PACK_IN_PLACE = True
@@ -339,7 +382,7 @@ def _anything_split(d, split):
 
 def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffuse=None, specular=None, albedo=None, rf0=None, distance_to_occluder=None, translucency=None,
                   common_settings=None, hit_dist_params=HIT_DIST_PARAMS, viewz_scale=1.0, tan_of_light_angular_radius=0.0, out=None, stream=None, lib=None, hit_dist_trim=0.0,
-                  in_place=None, guide_shift=0):
+                  in_place=None, guide_shift=0, direct=None):
     """The descriptor of one nrdHipPackInputs launch, without launching: (packed planes, api.HipFrontEndDesc, arrays the descriptor points into besides its arguments) -- for a
     caller that launches the same frame layout repeatedly through the C-ABI itself. fp32 inputs: normal_roughness [H, W, 4] (or a (normal [H, W, 3], roughness [H, W]) pair), viewz [H, W], material_id [H, W],
     motion [H, W, 4] or [H, W, 2], albedo / rf0 / translucency [H, W, 4] or [H, W, 3], distance_to_occluder [H, W]; diffuse / specular: dict(mode=SignalMode,
@@ -353,10 +396,13 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
     pack_samples(..., in_place=True): a relaunch after the caller refreshed its tensors packs the new values. (A bare [H, W, 3] normal_roughness / radiance_hitdist, which has
     no w anywhere, is still widened with zeros.) A signal in the occlusion mode may give radiance_hitdist=(None, hit_dist).
     guide_shift=1: the descriptor is for nrdHipPackInputsDecimated( ..., guideShift = 1 ) alone -- the G-buffer arguments are full-size, everything else and every output low-size
-    (see pack_inputs)."""
+    (see pack_inputs).
+    direct= (what pack_direct returned, or a dict of its arguments): the descriptor is for nrdHipPackInputsDirect, its diffuse / specular planes are the indirect ones, and the
+    third value returned ends with the api.HipFrontEndDirect to pass next to it."""
     in_place = bool(in_place)
     d = api.HipFrontEndDesc()
     keep = []  # widened copies must outlive the launch call
+    di = None if direct is None else pack_direct(**direct) if isinstance(direct, dict) else direct
     nr, d.normalRoughness = _rgba_arg(normal_roughness, "normal_roughness", in_place, needs_w=True)
     keep.append(nr)
     h, w = viewz.shape
@@ -412,7 +458,7 @@ def describe_pack(normal_roughness, viewz, material_id=None, motion=None, diffus
         dst.out0 = output(slot0, (h, w) if ch == 1 else (h, w, ch), dtype, fmt)
         if slot1 is not None:
             dst.out1 = output(slot1, (h, w, 4), "float16", F.RGBA16_SFLOAT)
-    return res, d, keep + [common_settings]
+    return res, d, keep + [common_settings] + ([] if di is None else [di[1], di[0]])
 
 
 # ---- hit-distance coverage of a probabilistic split ----------------------------------------------------------------------------------------------------------

@@ -25,8 +25,12 @@ alternating rounds, medians; and whole frames (pack + denoise + resolve, default
 signals, one traced plane, a lobe byte and a probability per pixel. Five alternating rounds of (a) nrdHipPackInputsLobes, (b) nrdHipPackInputs producing the same outputs from two
 prepared RGBA32_SFLOAT planes, (c) the torch chain that prepares those planes, (d) nrdHipCheckHitDistCoverage with area 2 on both packed signals; the copy rate of the same run,
 each row's spread over the rounds, and whether (a) is slower than (b) by more than that spread.
+--direct is a run of its own that adds the `direct` and `isa_direct` objects to the output file (--isa-only: the second one alone, without a GPU): combined direct and indirect
+lighting at 2560 x 1440, REBLUR_RADIANCE on both signals, RGBA32_SFLOAT planes. Five alternating rounds of (a) nrdHipPackInputsDirect, (b) what a host writes today -- the torch
+composition of the README's rule (sum, two luminances, ratio, clamp, lerp, where) into two RGBA32_SFLOAT planes followed by nrdHipPackInputs -- and the two halves of (b) alone;
+the fused call's bytes per pixel and its fraction of the copy rate of the same run. The run fails if (a) is slower than (b).
 usage: python tools/frontend_bench.py [--width 2560 --height 1440 --reps 300 --warmup 20] [--out profiles/frontend_bench.json] [--isa-only] [--rejitter [--ab-library PATH]] [--samples [N ...]] [--split]
-       [--check-inputs] [--shadow-lights] [--guides] [--upsample] [--lobes]"""
+       [--check-inputs] [--shadow-lights] [--guides] [--upsample] [--lobes] [--direct]"""
 import argparse
 import ctypes as C
 import json
@@ -1052,6 +1056,142 @@ def lobes_main(args):
     assert not result["lobes"]["pack_lobes_slower_than_plain_beyond_the_spread"], "nrdHipPackInputsLobes is slower than the plain pack it replaces by more than the run-to-run spread"
 
 
+DIRECT_KERNELS = {"PackDirectKernel": "pack_direct", "PackDirectCheckerboardKernel": "pack_direct_checkerboard", "PackDirectDecimatedKernel": "pack_direct_decimated"}
+DIRECT_READ = {"normal_roughness RGBA32_SFLOAT": 16, "viewZ R32_SFLOAT": 4, "diffuse indirect RGBA32_SFLOAT": 16, "specular indirect RGBA32_SFLOAT": 16, "diffuse direct RGBA32_SFLOAT": 16,
+               "specular direct RGBA32_SFLOAT": 16}
+DIRECT_WRITE = {"IN_NORMAL_ROUGHNESS": 4, "IN_VIEWZ R32_SFLOAT": 4, "IN_DIFF_RADIANCE_HITDIST RGBA16_SFLOAT": 8, "IN_SPEC_RADIANCE_HITDIST RGBA16_SFLOAT": 8}
+
+
+def direct_isa():
+    """static facts about the three kernels behind nrdHipPackInputsDirect (the `isa_direct` object of profiles/frontend_bench.json), as isa(): "pack_direct",
+    "pack_direct_checkerboard" and "pack_direct_decimated", with their 12- and 16-byte loads"""
+    with tempfile.TemporaryDirectory() as tmp:
+        listing = os.path.join(tmp, "kernels_frontend.s")
+        flags = [f for f in B._flags(SRC) if f not in ("-x", "hip")]
+        subprocess.run([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-x", "hip", SRC, "-o", listing], check=True, capture_output=True, text=True)
+        stats = isa_stats.parse(listing)
+    out = {}
+    for mangled, k in stats.items():
+        for kernel, name in DIRECT_KERNELS.items():
+            if kernel in mangled:
+                c = k["counter"]
+                out[name] = dict(_facts(k), global_load_dwordx4=c.get("global_load_dwordx4", 0), global_load_dwordx3=c.get("global_load_dwordx3", 0), global_load_dword=c.get("global_load_dword", 0))
+    assert set(out) == set(DIRECT_KERNELS.values()), sorted(out)
+    return out
+
+
+def _update_record(path, result):
+    record = {}
+    if os.path.exists(path):  # the other fields of the record are another run's: kept as they are
+        with open(path) as fp:
+            record = json.load(fp)
+    record.update(result)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fp:
+        json.dump(record, fp, indent=1)
+        fp.write("\n")
+
+
+def direct_main(args):
+    """--direct: see the module text"""
+    result = {"isa_direct": direct_isa()}
+    if args.isa_only:
+        _update_record(args.out, result)
+        print(json.dumps(result))
+        return
+    import torch
+
+    from raytracingdenoiser_amd import api, frontend
+
+    if not torch.cuda.is_available():
+        raise SystemExit("frontend_bench.py measures on the GPU: none is visible (--isa-only needs none)")
+    w, h = args.width, args.height
+    px = w * h
+    S, R = api.SignalMode, api.ResourceType
+    g = torch.Generator(device="cuda").manual_seed(7)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    normal = torch.nn.functional.normalize(rand(h, w, 3) - 0.5, dim=-1)
+    nr = torch.cat([normal, rand(h, w, 1) * 0.95 + 0.05], -1).contiguous()
+    viewz = rand(h, w) * 49.0 + 1.0
+    traced = lambda: torch.cat([rand(h, w, 3) * 4.0, rand(h, w, 1) * 29.9 + 0.1], -1).contiguous()
+    indirect, lit = (traced(), traced()), (traced(), traced())  # (diffuse, specular)
+    for plane in lit:  # a quarter of the pixels sampled no light
+        plane[rand(h, w) < 0.25] = float("nan")
+    max_contribution = api.DIRECT_MAX_CONTRIBUTION_DEFAULT
+    lib, stream = api.load_library(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sig = lambda plane: dict(mode=S.REBLUR_RADIANCE, radiance_hitdist=plane)
+    packed, desc, keep0 = frontend.describe_pack(nr, viewz, diffuse=sig(indirect[0]), specular=sig(indirect[1]))
+    di, keep1 = frontend.pack_direct(lit[0], lit[1], max_contribution)
+    options, samples, split = frontend.pack_options(), api.HipFrontEndSamples(), api.HipFrontEndSplit()
+    composed = (torch.empty_like(indirect[0]), torch.empty_like(indirect[1]))
+    plain_packed, plain_desc, keep2 = frontend.describe_pack(nr, viewz, diffuse=sig(composed[0]), specular=sig(composed[1]))
+    luma = torch.tensor([0.2126, 0.7152, 0.0722], device="cuda")
+
+    def compose():  # what a tensor host does today before the plain call: the README's rule in torch, two full RGBA32_SFLOAT planes
+        for spec in (False, True):
+            ind, d = indirect[spec], torch.nan_to_num(lit[spec], nan=0.0, posinf=0.0, neginf=0.0)
+            rad = ind[..., :3] + d[..., :3]
+            hit = ind[..., 3]
+            if not spec:
+                li, ld = (ind[..., :3].clamp(0.0, 65504.0) * luma).sum(-1), (d[..., :3].clamp(0.0, 65504.0) * luma).sum(-1)
+                c = (ld / (ld + li + 1e-6)).clamp(max=max_contribution)
+                hit = torch.where((c > 0) & (hit > 0) & (d[..., 3] > 0), hit + (d[..., 3] - hit) * c, hit)
+            torch.cat([rad, hit.unsqueeze(-1)], -1, out=composed[spec])
+
+    def pack_direct():
+        assert lib.nrdHipPackInputsDirect(C.byref(desc), C.byref(options), C.byref(samples), C.byref(split), C.byref(di), 0, stream) == 0, lib.nrdHipGetLastFrontEndError()
+
+    def pack_plain():
+        assert lib.nrdHipPackInputs(C.byref(plain_desc), stream) == 0, lib.nrdHipGetLastFrontEndError()
+
+    def host_path():
+        compose()
+        pack_plain()
+
+    pack_direct()
+    host_path()
+    torch.cuda.synchronize()
+    for rt in packed:  # the two paths pack the same frame: what is timed is the same work (the host sums before it packs: fp16 roundings apart)
+        a, b = packed[rt][0].float(), plain_packed[rt][0].float()
+        assert bool(torch.isfinite(a).all()) and torch.allclose(a, b, rtol=1e-2, atol=1e-2), rt
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(args.reps):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / args.reps
+
+    rows = {"pack_direct_ms": pack_direct, "host_path_ms": host_path, "torch_compose_ms": compose, "pack_plain_ms": pack_plain}
+    rounds = [{k: timed(fn) for k, fn in rows.items()} for _ in range(5)]
+    best = {k: min(r[k] for r in rounds) for k in rows}
+    median = {k: sorted(r[k] for r in rounds)[2] for k in rows}
+    spread = {k: (max(r[k] for r in rounds) - min(r[k] for r in rounds)) / min(r[k] for r in rounds) for k in rows}
+    gbps = C.c_double()
+    assert lib.nrdHipMeasureCopyBandwidth(256 << 20, 20, stream, C.byref(gbps)) == 0
+    rate = lambda bytes_per_px, ms: bytes_per_px * px / (ms * 1e-3) / 1e9
+    direct_bytes = sum(DIRECT_READ.values()) + sum(DIRECT_WRITE.values())
+    result["direct"] = dict(
+        best=best, median=median, run_to_run_spread=spread, rounds=rounds, device=torch.cuda.get_device_name(0), width=w, height=h, reps=args.reps, warmup=args.warmup,
+        times_are="device events around --reps back-to-back calls, per call; five rounds with the four rows alternating inside each round; spread = ( max - min ) / min of a row over the rounds",
+        scene="REBLUR_RADIANCE on both signals, RGBA32_SFLOAT planes, maxHitDistContribution 0.5, a quarter of the direct texels NaN (no light sampled); host_path_ms = torch_compose_ms's "
+              "work followed by pack_plain_ms's, timed as one row",
+        read_bytes_per_pixel=DIRECT_READ, write_bytes_per_pixel=DIRECT_WRITE, pack_direct_bytes_per_pixel=direct_bytes,
+        pack_direct_gigabytes_per_second=rate(direct_bytes, best["pack_direct_ms"]), copy_gigabytes_per_second=gbps.value,
+        pack_direct_fraction_of_copy_rate=rate(direct_bytes, best["pack_direct_ms"]) / gbps.value,
+        fraction_is_not="a share of HBM bandwidth: the working set partly fits the memory-side cache, as for pack and resolve (DESIGN.md section 3.4)",
+        pack_direct_over_host_path=median["pack_direct_ms"] / median["host_path_ms"], pack_direct_slower_than_host_path=bool(median["pack_direct_ms"] > median["host_path_ms"]))
+    _update_record(args.out, result)
+    print(json.dumps({k: v for k, v in result["direct"].items() if k != "rounds"}))
+    print(json.dumps(result["isa_direct"]))
+    assert not result["direct"]["pack_direct_slower_than_host_path"], "nrdHipPackInputsDirect is slower than the torch composition and the plain pack it replaces"
+
+
 def synth_pack(raw, synth, torch):
     """the packing of synth.render_frame for REBLUR_DIFFUSE_SPECULAR on the raw values: its packers, elementwise torch operations with fp32 intermediates"""
     out = {"normal_roughness": synth.pack_normal_roughness(raw["normal"], raw["roughness"], raw["material"]).contiguous(), "viewz": raw["viewz"].clone(),
@@ -1136,6 +1276,8 @@ def main():
                     "--height say otherwise) against the copy rate and the same recipes as torch elementwise operations; adds the `shadow_lights` and `isa_shadow_lights` objects to --out")
     ap.add_argument("--guides", action="store_true", help="a run of its own: nrdHipPackGuides on RGB32_SFLOAT position planes against the copy rate, next to the four shadow-light "
                     "calls on planes of the same size, the whole set three times; adds the `guides` and `isa_guides` objects to --out and leaves its other fields as they are")
+    ap.add_argument("--direct", action="store_true", help="a run of its own: nrdHipPackInputsDirect against the torch composition of the README's rule followed by nrdHipPackInputs; "
+                    "adds the `direct` and `isa_direct` objects to --out (--isa-only: isa_direct alone, no GPU needed)")
     ap.add_argument("--lobes", action="store_true", help="a run of its own: nrdHipPackInputsLobes against nrdHipPackInputs on two prepared planes and the torch chain that prepares them, "
                     "and nrdHipCheckHitDistCoverage against the copy rate; adds the `lobes` and `isa_lobes` objects to --out")
     ap.add_argument("--upsample", action="store_true", help="a run of its own: nrdHipResolveOutputsUpsampled (half-size planes to --width x --height) against the plain resolve of the same "
@@ -1145,6 +1287,8 @@ def main():
     args.width, args.height = args.width or default_size[0], args.height or default_size[1]
     if args.lobes:
         return lobes_main(args)
+    if args.direct:
+        return direct_main(args)
     if args.upsample:
         return upsample_main(args)
     if args.guides:
